@@ -1,6 +1,7 @@
 """Headline benchmark: grid-cell Lyapunov checks per second (BASELINE.json).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C4] [--num-points P] [--n-gp G]
+                    [--dump-outputs DIR]
 
 Default workload (BASELINE.json configs[3] / SURVEY 8d "C4"): cart-pole state grid 128^4 (2.68e8
 cells), 1024-point shared-kernel RBF GP over [x, u] (p = 5 inputs, 4 outputs), quadratic LQR
@@ -19,6 +20,10 @@ C5-policy (the other sweep of that loop: evaluation of the greedy table policy).
 otherwise bench.py launches the N ranks itself (``torch.multiprocessing.spawn``), backend ``nccl``
 (= RCCL over xGMI) when every rank has its own GPU, ``gloo`` when ranks have to share a device.
 The grid is sharded by contiguous index ranges: total work is fixed, so scaling is "strong".
+
+``--dump-outputs DIR``: after the timed steps, what the last of them handed its caller is written
+as ``DIR/<name>.npy`` (float32 / float64; see ``step_outputs``), so that two builds can be compared
+output for output - the inputs are seeded and the same for the same arguments.
 """
 
 import argparse
@@ -39,6 +44,8 @@ HBM_PEAK_GBPS = 8000.0              # MI355X_MICROARCH.md: 8 TB/s spec (6.3 TB/s
 HEADLINE_METRIC = "grid-cell Lyapunov checks/sec + ms/safe_set-update, 4D 128^4 grid, 1k-pt GP"
 CONFIGS = ("C1", "C2", "C2-table", "C2-table-large", "C2-table-stack", "C2-notebook", "C2-table-det", "C3", "C4", "C4-lin",
            "C4-det", "C5", "C5-policy")
+DUMP_SAMPLE = 1 << 21               # --dump-outputs: cells kept of a longer per-cell output
+DUMP_LIMIT = 64 << 20               # --dump-outputs: bytes of all files together
 
 
 def flops_per_check(n, p, d_out, heads=1):
@@ -442,7 +449,7 @@ def run_rank(args, rank, world, local_rank, backend):
     dist_utils.start_timing()                     # device events around every collective
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        result = step()
     own_elapsed = time.perf_counter() - t0        # this rank's host clock before the barrier
     barrier()
     elapsed = time.perf_counter() - t0
@@ -479,6 +486,11 @@ def run_rank(args, rank, world, local_rank, backend):
         raise SystemExit("bench.py: the ranks ran different kernels: %r" % [r["kernel"] for r in ranks_info])
 
     # ---- everything below is outside the timed region --------------------------------------
+    outputs, capture_s = None, 0.0
+    if args.dump_outputs and rank == 0:      # (local reads on every rank: no collective behind them)
+        t1 = time.perf_counter()
+        outputs = step_outputs(kind, obj, result)
+        capture_s = time.perf_counter() - t1
     if kind == "lyapunov":
         from safe_learning_amd.benchmarks import initial_safe_mask
         extra["safe_cells"] = int(obj.safe_count)
@@ -550,7 +562,8 @@ def run_rank(args, rank, world, local_rank, backend):
         if args.successor_cache != "off":
             # wall clock of the whole loop from V = 0: filling sweep + warm-up + timed steps + the rest
             torch.cuda.synchronize()
-            extra["time_to_convergence_s"] = time.perf_counter() - loop_t0
+            # (the copy of --dump-outputs is not part of the loop)
+            extra["time_to_convergence_s"] = time.perf_counter() - loop_t0 - capture_s
             extra["steady_sweep_ms"] = 1e3 * elapsed / args.steps
             extra["successor_cache"] = obj.successor_cache_info
 
@@ -639,6 +652,8 @@ def run_rank(args, rank, world, local_rank, backend):
         if world == 1 and not args.no_cpu_baseline and kind != "policy":
             # (the policy-evaluation line has no CPU leg of its own: C5's is the same oracle sweep)
             out["cpu_baseline"] = cpu_baseline(kind, case, min_cells=args.cpu_cells)
+        if outputs is not None:
+            out["dump_outputs"] = dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(out), flush=True)
     if grouped:
         dist.barrier()
@@ -651,6 +666,42 @@ def _popcount(words):
     x = words.view(torch.uint8)
     table = torch.tensor([bin(i).count("1") for i in range(256)], dtype=torch.int64, device=x.device)
     return table[x.long()].sum()
+
+
+def step_outputs(kind, obj, result):
+    """What one step handed its caller, as float32 / float64 arrays (``--dump-outputs``).
+
+    lyapunov: ``safe_set`` (0 / 1), ``c_max``, ``safe_count``; bellman: ``value_function`` and the
+    greedy ``policy`` per vertex, ``residual`` (the return value of ``value_iteration``); policy:
+    ``value_function``, ``residual``.  A grid of more than DUMP_SAMPLE cells keeps a seeded sample of
+    cells, fixed by the grid size, whose indices are ``cell_index``."""
+    if kind == "lyapunov":
+        per_cell = {"safe_set": (obj.safe_set, np.float32)}
+        scalars = {"c_max": obj.c_max, "safe_count": obj.safe_count}
+    else:
+        per_cell = {"value_function": (obj.value_function.parameters.reshape(-1), np.float64)}
+        if kind == "bellman":
+            per_cell["policy"] = (obj.policy.parameters.reshape(-1), np.float64)
+        scalars = {"residual": result}
+    out = {name: np.array([value], dtype=np.float64) for name, value in scalars.items()}
+    n = obj.discretization.nindex
+    index = slice(None)
+    if n > DUMP_SAMPLE:
+        index = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+        out["cell_index"] = index.astype(np.float64)
+    for name, (values, dtype) in per_cell.items():
+        out[name] = np.ascontiguousarray(values[index], dtype=dtype)
+    return out
+
+
+def dump_outputs(directory, outputs):
+    total = sum(array.nbytes for array in outputs.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT))
+    os.makedirs(directory, exist_ok=True)
+    for name, array in outputs.items():
+        np.save(os.path.join(directory, name + ".npy"), array)
+    return sorted(outputs)
 
 
 def roofline(args, kind, case, dyn, d, cells_per_launch, avg_ms, world):
@@ -811,7 +862,13 @@ def parse_args(argv=None):
                          "inputs incl. the full tau, kept to show that the cost does not depend on them")
     ap.add_argument("--backend", default=None,
                     help="torch.distributed backend; default nccl (= RCCL), gloo if ranks share a GPU")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (at most 64 MB; "
+                         "a seeded sample of the cells of a larger grid)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # Environment variables under which a bench line is not what the shipped library does: a development

@@ -317,8 +317,47 @@ def check_live(count, seed):
     print("LIVE OK: %d scenarios compared" % count)
 
 
+# (scenarios, seed) of the random comparisons of tests/test_oracle_live_reference.py
+LIVE_RUNS = ((8, 21), (8, 22))
+LIVE_OUT = os.path.join(HERE, "reference_live_policy_iteration.npz")
+
+
+def record_live():
+    """The reference's runs of the LIVE_RUNS scenarios -> LIVE_OUT (scenario parameters and records)."""
+    ref = numpy_tf.load_reference(examples=True)
+    arrays, index = {}, []
+    for count, seed in LIVE_RUNS:
+        for scenario in random_scenarios(count, seed):
+            key = "seed%d/%s" % (seed, scenario["name"])
+            records = reference_run(scenario, ref)
+            for k, record in enumerate(records):
+                arrays["%s/record%d" % (key, k)] = np.asarray(record)
+            meta = dict(scenario)
+            meta["steps"] = [list(step) for step in scenario["steps"]]
+            index.append(dict(seed=seed, key=key, records=len(records),
+                              scenario=jsonable(meta, arrays, key + "/scenario")))
+            print("%-40s records %d" % (key, len(records)))
+    arrays["_index"] = np.array(json.dumps(index))
+    np.savez_compressed(LIVE_OUT, **arrays)
+    print("wrote %s (%d arrays, %.1f KiB)" % (LIVE_OUT, len(arrays), os.path.getsize(LIVE_OUT) / 1024.0))
+
+
+def live_fixture():
+    """LIVE_OUT as [(seed, scenario, records)] in the order recorded."""
+    fixture = np.load(LIVE_OUT)
+    out = []
+    for entry in json.loads(str(fixture["_index"])):
+        scenario = from_jsonable(entry["scenario"], fixture)
+        scenario["steps"] = [tuple(step) for step in scenario["steps"]]
+        records = [fixture["%s/record%d" % (entry["key"], k)] for k in range(entry["records"])]
+        out.append((entry["seed"], scenario, records))
+    return out
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "--check-live":
         check_live(int(sys.argv[2]), int(sys.argv[3]))
+    elif len(sys.argv) > 1 and sys.argv[1] == "--record-live":
+        record_live()
     else:
         main()

@@ -389,50 +389,129 @@ def random_scenarios(count, seed):
     return out
 
 
-def check_live(count, seed):
-    """Reference and oracle side by side on random scenarios, in this process (no fixture)."""
+def reference_run(scenario, ref):
+    """A random scenario on the reference's ``Lyapunov`` -> (value table, records), or None where
+    two cells have the same value (the tie order is unpinned)."""
+    from tests import cases
+    case = scenario["case"]
+    policy, dynamics, value, lv = reference_specs(case, ref)
+    ref.config.gp_batch_size = scenario["batch"]
+    grid = ref.functions.GridWorld(case["limits"], case["num_points"])
+    lyap = ref.lyapunov.Lyapunov(grid, value, dynamics, case["lf"], lv, case["tau"], policy,
+                                 initial_set=cases.initial_safe_mask(case), adaptive=scenario["adaptive"])
+    if len(np.unique(lyap.values)) != len(lyap.values):
+        return None
+    records = replay(scenario, lyap, dynamics, ref.lyapunov.get_safe_sample,
+                     lambda obj: obj.feed_dict[obj.c_max])
+    return lyap.values, records
+
+
+def oracle_run(scenario):
+    """The same scenario on ``oracle.Lyapunov`` -> (value table, records)."""
     import oracle
     from oracle import np_lyapunov
     from tests import cases
+    case = scenario["case"]
+    np_lyapunov.config.gp_batch_size = scenario["batch"]
+    policy, dynamics, value, lv = cases.oracle_specs(case)
+    lyap = oracle.Lyapunov(oracle.GridWorld(case["limits"], case["num_points"]), value, dynamics,
+                           case["lf"], lv, case["tau"], policy, initial_set=cases.initial_safe_mask(case))
+    lyap.adaptive = scenario["adaptive"]
+    records = replay(scenario, lyap, dynamics, oracle.get_safe_sample, lambda obj: obj.c_max)
+    return lyap.values, records
+
+
+def check_records(scenario, got, want):
+    """Value tables and every record bit for bit (a sample's bound under GP dynamics, a posterior
+    standard deviation, to 1e-10)."""
+    name, case = scenario["name"], scenario["case"]
+    (values, records), (want_values, want_records) = got, want
+    assert np.array_equal(values, want_values), name
+    assert len(records) == len(want_records), name
+    for k, (a, b) in enumerate(zip(records, want_records)):
+        assert sorted(a) == sorted(b), "%s step %d" % (name, k)
+        for key in b:
+            if key == "bound" and case["dynamics"]["kind"] == "gp":
+                assert np.allclose(a[key], b[key], rtol=1e-10, atol=0), (name, k, key)
+                continue
+            assert np.array_equal(a[key], b[key]), "%s step %d %s" % (name, k, key)
+
+
+# (scenarios, seed) of the random comparisons of tests/test_oracle_live_reference.py
+LIVE_RUNS = ((8, 11), (8, 12))
+LIVE_OUT = os.path.join(HERE, "reference_live_safe_sets.npz")
+
+
+def check_live(count, seed):
+    """Reference and oracle side by side on random scenarios, in this process (no fixture)."""
     ref = numpy_tf.load_reference(examples=True)
     compared = 0
     for scenario in random_scenarios(count, seed):
-        name, case = scenario["name"], scenario["case"]
-        initial = cases.initial_safe_mask(case)
-        # the reference's run
-        policy, dynamics, value, lv = reference_specs(case, ref)
-        ref.config.gp_batch_size = scenario["batch"]
-        grid = ref.functions.GridWorld(case["limits"], case["num_points"])
-        lyap = ref.lyapunov.Lyapunov(grid, value, dynamics, case["lf"], lv, case["tau"], policy,
-                                     initial_set=initial, adaptive=scenario["adaptive"])
-        if len(np.unique(lyap.values)) != len(lyap.values):
-            print("%s: equal values on the grid, skipped (tie order is unpinned)" % name)
+        want = reference_run(scenario, ref)
+        if want is None:
+            print("%s: equal values on the grid, skipped (tie order is unpinned)" % scenario["name"])
             continue
-        want = replay(scenario, lyap, dynamics, ref.lyapunov.get_safe_sample,
-                      lambda obj: obj.feed_dict[obj.c_max])
-        # the oracle's
-        np_lyapunov.config.gp_batch_size = scenario["batch"]
-        opolicy, odynamics, ovalue, olv = cases.oracle_specs(case)
-        olyap = oracle.Lyapunov(oracle.GridWorld(case["limits"], case["num_points"]), ovalue,
-                                odynamics, case["lf"], olv, case["tau"], opolicy, initial_set=initial)
-        olyap.adaptive = scenario["adaptive"]
-        got = replay(scenario, olyap, odynamics, oracle.get_safe_sample, lambda obj: obj.c_max)
-        assert np.array_equal(olyap.values, lyap.values), name
-        for k, (a, b) in enumerate(zip(got, want)):
-            for key in b:
-                if key == "bound" and case["dynamics"]["kind"] == "gp":     # a posterior std
-                    assert np.allclose(a[key], b[key], rtol=1e-10, atol=0), (name, k, key)
-                    continue
-                assert np.array_equal(a[key], b[key]), "%s step %d %s" % (name, k, key)
+        check_records(scenario, oracle_run(scenario), want)
         compared += 1
         print("%-34s cells %5d batch %3d safe %s%s" % (
-            name, grid.nindex, scenario["batch"], [int(r["safe_set"].sum()) for r in want],
+            scenario["name"], len(want[0]), scenario["batch"],
+            [int(r["safe_set"].sum()) for r in want[1] if "safe_set" in r],
             "  adaptive" if scenario["adaptive"] else ""))
     print("LIVE OK: %d scenarios compared" % compared)
+
+
+def record_live():
+    """The reference's runs of the LIVE_RUNS scenarios -> LIVE_OUT (scenario parameters, value
+    table and records; a scenario with tied values is stored as skipped)."""
+    ref = numpy_tf.load_reference(examples=True)
+    arrays, index = {}, []
+    for count, seed in LIVE_RUNS:
+        for scenario in random_scenarios(count, seed):
+            key = "seed%d/%s" % (seed, scenario["name"])
+            run = reference_run(scenario, ref)
+            meta = {k: v for k, v in scenario.items() if k != "case"}
+            meta["steps"] = [list(step) for step in scenario["steps"]]
+            index.append(dict(seed=seed, key=key, skipped=run is None, records=0 if run is None else len(run[1]),
+                              meta=jsonable(meta, arrays, key + "/meta"),
+                              case=jsonable(scenario["case"], arrays, key + "/case")))
+            if run is None:
+                continue
+            arrays[key + "/values"] = run[0]
+            for k, record in enumerate(run[1]):
+                for name, val in record.items():
+                    arrays["%s/step%d/%s" % (key, k, name)] = val
+            print("%-40s safe %s" % (key, [int(r["safe_set"].sum()) for r in run[1] if "safe_set" in r]))
+    arrays["_index"] = np.array(json.dumps(index))
+    arrays["_numpy_version"] = np.array(np.__version__)
+    np.savez_compressed(LIVE_OUT, **arrays)
+    print("wrote %s (%d arrays, %.1f KiB)" % (LIVE_OUT, len(arrays), os.path.getsize(LIVE_OUT) / 1024.0))
+
+
+def live_fixture():
+    """LIVE_OUT as [(seed, scenario, (value table, records) or None)] in the order recorded."""
+    fixture = np.load(LIVE_OUT)
+    out = []
+    for entry in json.loads(str(fixture["_index"])):
+        key = entry["key"]
+        scenario = from_jsonable(entry["meta"], fixture)
+        scenario["steps"] = [tuple(step) for step in scenario["steps"]]
+        scenario["case"] = from_jsonable(entry["case"], fixture)
+        run = None
+        if not entry["skipped"]:
+            records = []
+            for k in range(entry["records"]):
+                prefix = "%s/step%d/" % (key, k)
+                records.append({name[len(prefix):]: fixture[name] for name in fixture.files
+                                if name.startswith(prefix)})
+            run = (fixture[key + "/values"], records)
+        out.append((entry["seed"], scenario, run))
+    return out
 
 
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "--check-live":
         check_live(int(sys.argv[2]), int(sys.argv[3]))
+    elif len(sys.argv) > 1 and sys.argv[1] == "--record-live":
+        record_live()
     else:
         main()

@@ -4,6 +4,7 @@ on small cases (the oracle is the thing timed there - allowed for bench.py's cpu
 import os
 import sys
 
+import pytest
 
 from conftest import ROOT
 
@@ -121,3 +122,48 @@ def test_bench_refuses_diagnostic_environments():
     assert sorted({f for f, _ in calls}) == ["sl_common.h", "sl_kernels.hip"], calls
     known = set(bench.REFUSED_ENV) | set(bench.AB_ENV) | {"SL_PROBE_BLOCKS_PER_CU", "SL_BELLMAN4_POLICY_VERBOSE"}
     assert names - known == set(), names - known
+
+
+def test_steps_and_warmup_are_checked():
+    for flags in (["--steps", "0"], ["--steps", "-1"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(flags)
+    args = bench.parse_args(["--steps", "7", "--warmup", "0", "--dump-outputs", "out"])
+    assert args.steps == 7 and args.warmup == 0 and args.dump_outputs == "out"
+    assert bench.parse_args([]).dump_outputs is None
+
+
+def test_step_outputs_are_a_fixed_sample_within_the_limit(tmp_path):
+    """--dump-outputs: float32 / float64 files, a grid larger than DUMP_SAMPLE cut to the same
+    seeded sample of cells in every run, the values of the sampled cells, at most DUMP_LIMIT bytes."""
+    from types import SimpleNamespace
+    import numpy as np
+    n = bench.DUMP_SAMPLE + 12345
+    mask = np.random.default_rng(5).random(n) < 0.3
+    lyap = SimpleNamespace(safe_set=mask, c_max=0.25, safe_count=int(mask.sum()),
+                           discretization=SimpleNamespace(nindex=n))
+    out = bench.step_outputs("lyapunov", lyap, None)
+    assert sorted(out) == ["c_max", "cell_index", "safe_count", "safe_set"]
+    index = out["cell_index"].astype(np.int64)
+    assert len(index) == bench.DUMP_SAMPLE and (np.diff(index) > 0).all() and index[-1] < n
+    assert np.array_equal(index, bench.step_outputs("lyapunov", lyap, None)["cell_index"])
+    assert out["safe_set"].dtype == np.float32 and np.array_equal(out["safe_set"], mask[index])
+    assert out["c_max"].tolist() == [0.25] and out["safe_count"].tolist() == [mask.sum()]
+    # the Bellman sweep: value table and greedy policy per vertex, the residual; a small grid whole
+    m = 1000
+    table = lambda values: SimpleNamespace(parameters=values.reshape(-1, 1))     # noqa: E731
+    rl = SimpleNamespace(value_function=table(np.linspace(-3, 0, m)), policy=table(np.linspace(-1, 1, m)),
+                         discretization=SimpleNamespace(nindex=m))
+    small = bench.step_outputs("bellman", rl, 1.5e-3)
+    assert sorted(small) == ["policy", "residual", "value_function"]
+    assert np.array_equal(small["value_function"], np.linspace(-3, 0, m)) and small["residual"].tolist() == [1.5e-3]
+    assert sorted(bench.step_outputs("policy", rl, 0.5)) == ["residual", "value_function"]
+    names = bench.dump_outputs(str(tmp_path / "dump"), out)
+    assert names == sorted(out)
+    for name in names:
+        saved = np.load(tmp_path / "dump" / (name + ".npy"))
+        assert saved.dtype in (np.float32, np.float64) and np.array_equal(saved, out[name])
+    assert sum(a.nbytes for a in out.values()) <= bench.DUMP_LIMIT
+    big = {"x": np.zeros(bench.DUMP_LIMIT // 8 + 1)}
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), big)

@@ -131,3 +131,32 @@ def test_bench_c5_runs_to_convergence():
     two = _run("--config", "C5", "--num-points", "10", "--n-gp", "128", "--steps", "3",
                "--no-cpu-baseline", "--max-sweeps", "2500", "--gpus", "2")
     assert two["config"]["sweeps_to_convergence"] == cfg["sweeps_to_convergence"]
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs: what the last timed step handed its caller - the same for any number of steps
+    and ranks, in agreement with the line's own figures."""
+    import numpy as np
+
+    def load(out, name):
+        return {key: np.load(tmp_path / name / (key + ".npy")) for key in out["dump_outputs"]}
+
+    small = ["--num-points", "24", "--n-gp", "300", "--warmup", "1", "--no-cpu-baseline"]
+    one = _run(*small, "--steps", "3", "--dump-outputs", str(tmp_path / "one"))
+    assert one["steps"] == 3 and one["ms_per_step"] > 0
+    assert one["dump_outputs"] == ["c_max", "safe_count", "safe_set"]
+    got = load(one, "one")
+    assert got["safe_set"].dtype == np.float32 and got["safe_set"].shape == (24 ** 4,)
+    assert got["safe_set"].sum() == got["safe_count"][0] == one["config"]["safe_cells"]
+    assert got["c_max"][0] == one["config"]["c_max"]
+    two = _run(*small, "--steps", "1", "--gpus", "2", "--dump-outputs", str(tmp_path / "two"))
+    assert two["dump_outputs"] == one["dump_outputs"]
+    for key, array in load(two, "two").items():
+        assert np.array_equal(array, got[key]), key
+    c5 = _run("--config", "C5", "--num-points", "10", "--n-gp", "128", "--steps", "3", "--no-cpu-baseline",
+              "--max-sweeps", "40", "--dump-outputs", str(tmp_path / "c5"))
+    assert c5["dump_outputs"] == ["policy", "residual", "value_function"]
+    got = load(c5, "c5")
+    assert got["value_function"].shape == got["policy"].shape == (10 ** 4,)
+    assert np.isfinite(got["value_function"]).all() and got["residual"][0] > 0
+    assert np.isin(got["policy"], np.linspace(-1, 1, 9)).all()

@@ -1,45 +1,68 @@
-"""Reference and oracle side by side on random scenarios - only where ``/root/reference`` exists
-(the build container; the GPU box has no checkout and skips).
+"""Reference and oracle side by side on random scenarios.
 
-``tests/golden/make_reference_safe_sets.py --check-live N SEED`` runs the reference's own
-``Lyapunov`` (behind ``tests/golden/numpy_tf.py``) and ``oracle.Lyapunov`` on N seeded random
-scenarios - grid sizes and limits, tau, batch size, linear / Euler / GP / stacked-GP dynamics, the
-adaptive branch, hand-marked cells, ``can_shrink`` on and off - and requires value tables, safe sets,
-``c_max`` and refinement arrays to be equal bit for bit after every call.  It runs in a process of
-its own: loading the reference patches NumPy-1 aliases into the interpreter.  (A sweep of 200
-scenarios, seeds 2-6, was clean when the fixtures were committed.)
+``tests/golden/make_reference_safe_sets.py --record-live`` ran the reference's own ``Lyapunov``
+(behind ``tests/golden/numpy_tf.py``) on the seeded random scenarios of its ``LIVE_RUNS`` - grid
+sizes and limits, tau, batch size, linear / Euler / GP / stacked-GP dynamics, the adaptive branch,
+hand-marked cells, ``can_shrink`` on and off - and stored the scenarios with the value tables, safe
+sets, ``c_max`` and refinement arrays after every call in
+``tests/golden/reference_live_safe_sets.npz``.  Here ``oracle.Lyapunov`` replays them and has to
+be equal bit for bit.  (``--check-live N SEED`` runs both sides on other seeds where the
+reference checkout exists; a sweep of 200 scenarios, seeds 2-6, was clean when the fixtures were
+committed.)
 """
 
+import importlib.util
 import os
-import subprocess
 import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from conftest import GOLDEN_DIR
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/safe_learning"),
-                    reason="the reference checkout exists in the build container only")
+def _generator(name):
+    sys.path.insert(0, GOLDEN_DIR)
+    try:
+        spec = importlib.util.spec_from_file_location(name, os.path.join(GOLDEN_DIR, name + ".py"))
+        module = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(module)
+    finally:
+        sys.path.remove(GOLDEN_DIR)
+    return module
+
+
+SAFE_SETS = _generator("make_reference_safe_sets")
+POLICY_ITERATION = _generator("make_reference_policy_iteration")
+
+
+@pytest.fixture
+def batch_size():
+    from oracle import np_lyapunov
+    saved = np_lyapunov.config.gp_batch_size
+    yield
+    np_lyapunov.config.gp_batch_size = saved
+
+
 @pytest.mark.parametrize("seed", [11, 12])
-def test_oracle_equals_the_reference_on_random_scenarios(seed):
-    script = os.path.join(ROOT, "tests", "golden", "make_reference_safe_sets.py")
-    res = subprocess.run([sys.executable, script, "--check-live", "8", str(seed)], cwd=ROOT,
-                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-    assert res.returncode == 0, res.stdout[-3000:]
-    assert "LIVE OK" in res.stdout, res.stdout[-3000:]
+def test_oracle_equals_the_reference_on_random_scenarios(seed, batch_size):
+    runs = [(scenario, want) for s, scenario, want in SAFE_SETS.live_fixture() if s == seed]
+    assert len(runs) == {s: count for count, s in SAFE_SETS.LIVE_RUNS}[seed]
+    for scenario, want in runs:
+        assert want is not None, "%s: recorded without a comparison (tied values)" % scenario["name"]
+        SAFE_SETS.check_records(scenario, SAFE_SETS.oracle_run(scenario), want)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/safe_learning"),
-                    reason="the reference checkout exists in the build container only")
 @pytest.mark.parametrize("seed", [21, 22])
 def test_oracle_policy_iteration_equals_the_reference_on_random_scenarios(seed):
-    """The same for ``PolicyIteration`` (``make_reference_policy_iteration.py --check-live``): random
-    value / policy grids (equal or not), action sets, discounts, rewards, constraint callbacks,
-    Lyapunov penalties, ``bellmann_error``.  (120 scenarios, seeds 1-4, were clean when committed;
-    the first sweep found the one difference there was: ``bellmann_error`` summed pairwise.)"""
-    script = os.path.join(ROOT, "tests", "golden", "make_reference_policy_iteration.py")
-    res = subprocess.run([sys.executable, script, "--check-live", "8", str(seed)], cwd=ROOT,
-                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-    assert res.returncode == 0, res.stdout[-3000:]
-    assert "LIVE OK" in res.stdout, res.stdout[-3000:]
+    """The same for ``PolicyIteration`` (``make_reference_policy_iteration.py --record-live``,
+    ``tests/golden/reference_live_policy_iteration.npz``): random value / policy grids (equal or
+    not), action sets, discounts, rewards, constraint callbacks, Lyapunov penalties,
+    ``bellmann_error``.  (120 scenarios, seeds 1-4, were clean when committed; the first sweep found
+    the one difference there was: ``bellmann_error`` summed pairwise.)"""
+    runs = [(scenario, want) for s, scenario, want in POLICY_ITERATION.live_fixture() if s == seed]
+    assert len(runs) == {s: count for count, s in POLICY_ITERATION.LIVE_RUNS}[seed]
+    for scenario, want in runs:
+        got = POLICY_ITERATION.oracle_run(scenario)
+        assert len(got) == len(want), scenario["name"]
+        for k, (a, b) in enumerate(zip(got, want)):
+            assert POLICY_ITERATION.records_match(a, b, scenario["case"]), "%s record %d" % (scenario["name"], k)

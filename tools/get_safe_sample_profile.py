@@ -1,5 +1,5 @@
 import os, sys, warnings, cProfile, pstats
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import safe_learning_amd as sl
 from safe_learning_amd.benchmarks import build_lyapunov, table_case
