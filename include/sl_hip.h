@@ -162,6 +162,13 @@ SL_API int  sl_timing_collect(sl_ctx* ctx, int channel, double* h_ms, int capaci
 
 /* ---- model upload (copies; replaces the TF graph build of lyapunov.py:431-443) --------- */
 SL_API int  sl_model_set(sl_ctx* ctx, const sl_model_desc* h_model);
+/* A policy table (SL_POLICY_TABLE: policy.d_table, or the slot-1 table of SL_POLICY_TRI) was
+ * overwritten IN PLACE.  What the sweeps derive from the policy alone - k_bellman4_policy's distinct
+ * actions and tile order, the select arrays of the successor cache - is kept between calls until the
+ * policy changes, and sl_model_set sees a change only in the description's bytes: the same pointer
+ * with new values is the same description.  Call this after such an edit (before the next sweep);
+ * handing in another pointer (sl_model_set, sl_tri_set_table) needs no call. */
+SL_API int  sl_policy_touch(sl_ctx* ctx);
 
 /* GP head `head` of the dynamics (FunctionStack: one head per output column,
  * functions.py:278-291; a shared-kernel multi-output GPRCached is one head with dout = D).
@@ -218,10 +225,11 @@ SL_API int  sl_gp_configure(sl_ctx* ctx, int nheads, double beta);
 SL_API int  sl_tri_set(sl_ctx* ctx, int slot, const sl_grid_desc* h_grid, int nsimplex,
                 const int32_t* h_simplices, const double* h_hyperplanes,
                 const double* h_discrete_points, int project, int ncols, const double* d_table);
-/* New vertex values for a slot whose grid stays.  Call it again whenever the values of the POLICY
- * table (slot 1) change, also when they were overwritten in place: what the policy-evaluation
- * sweep derives from the policy alone is kept between sweeps until this, sl_tri_set(slot 1) or an
- * sl_model_set with another policy description says that the policy is a new one. */
+/* New vertex values for a slot whose grid stays.  Call it (or sl_policy_touch) whenever the values of
+ * the POLICY table (slot 1) change, also when they were overwritten in place: what the
+ * policy-evaluation sweep derives from the policy alone is kept between sweeps until this,
+ * sl_policy_touch, sl_tri_set(slot 1) or an sl_model_set with another policy description says that
+ * the policy is a new one. */
 SL_API int  sl_tri_set_table(sl_ctx* ctx, int slot, const double* d_table);
 
 /* LyapunovNetwork (examples/utilities.py:85-104): h_kernels = per-layer kernel matrices
@@ -474,7 +482,8 @@ SL_API int  sl_bellman_sweep(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actions,
  * vertex - gather and combine from it.  Their results are bit-identical to the uncached kernels'.
  * The cache is dropped by whatever changes a successor: sl_model_set with another grid / dynamics
  * description, sl_gp_set_head[_kernel], sl_gp_append_point, sl_gp_configure with another head count,
- * sl_tri_set(slot 0); sl_tri_set_table, the reward, gamma and the policy may change freely.
+ * sl_tri_set(slot 0); sl_tri_set_table, the reward, gamma and the policy may change freely (a policy
+ * table overwritten in place: announce it with sl_policy_touch, the select arrays are per policy).
  *   max_bytes < 0: default budget (a quarter of the device's memory); 0: no cache (frees it);
  *   otherwise the largest allocation allowed - a sweep whose cache would not fit recomputes. */
 SL_API int  sl_successor_cache_configure(sl_ctx* ctx, int64_t max_bytes);

@@ -115,7 +115,7 @@ S_PREFIX, S_REMAINING, S_KEY_V, S_KEY_I, S_RANK, S_NONE = range(6)
 EXPORTS = [
     "sl_version", "sl_ctx_create", "sl_ctx_destroy", "sl_last_error", "sl_ctx_synchronize",
     "sl_last_kernel",
-    "sl_model_set", "sl_gp_set_head", "sl_gp_set_head_kernel", "sl_gp_append_point", "sl_gp_configure", "sl_tri_set", "sl_tri_set_table",
+    "sl_model_set", "sl_policy_touch", "sl_gp_set_head", "sl_gp_set_head_kernel", "sl_gp_append_point", "sl_gp_configure", "sl_tri_set", "sl_tri_set_table",
     "sl_network_set", "sl_policy_network_set", "sl_values", "sl_lyap_sweep", "sl_lyap_finalize", "sl_select_pass",
     "sl_values_implicit", "sl_fold_results", "sl_lyap_finalize_dev", "sl_refinement_carry", "sl_select_begin",
     "sl_select_hist", "sl_select_digit",
@@ -158,6 +158,7 @@ def load_library():
     lib.sl_ctx_destroy.argtypes = [C.c_void_p]
     lib.sl_ctx_synchronize.argtypes = [C.c_void_p]
     lib.sl_model_set.argtypes = [C.c_void_p, C.POINTER(ModelDesc)]
+    lib.sl_policy_touch.argtypes = [C.c_void_p]
     lib.sl_gp_set_head.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    c_double_p, c_double_p, c_double_p, C.c_double, c_double_p]
     lib.sl_gp_set_head_kernel.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -299,6 +300,10 @@ class Context(object):
     # ---- model ---------------------------------------------------------------------------
     def model_set(self, desc):
         self.check(self.lib.sl_model_set(self.handle, C.byref(desc)), "sl_model_set")
+
+    def policy_touch(self):
+        """``sl_policy_touch``: the policy table the model points at was overwritten in place."""
+        self.check(self.lib.sl_policy_touch(self.handle), "sl_policy_touch")
 
     def gp_set_head(self, head, X, Linv, alpha, col0, variance, lengthscales):
         X, pX = _as_c(X)

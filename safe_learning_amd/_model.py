@@ -16,6 +16,14 @@ from .functions import (AbsFunction, CartPole, ConstantFunction, FunctionStack,
                         _is_plain_rbf)
 
 
+def _kernel_key(kern, p):
+    """The hyper-parameters of a GP kernel as the engine receives them (bytes)."""
+    if _is_plain_rbf(kern, p):
+        return (float(kern.variance), np.asarray(kern.lengthscales, dtype=np.float64).tobytes())
+    return tuple((kind, product, variance.tobytes(), inv_ls.tobytes())
+                 for kind, product, variance, inv_ls in kern._factors(p))
+
+
 class ModelBuilder(object):
     """Keeps the engine's model in sync with a set of specs."""
 
@@ -28,6 +36,7 @@ class ModelBuilder(object):
         self._tri_structure = [None, None]
         self._net_signature = None
         self._policy_table = None
+        self._policy_source = None         # (tensor, its state) of a tensor policy used in place
         self._policy_net_signature = None
 
     # ---- pieces --------------------------------------------------------------------------
@@ -78,6 +87,7 @@ class ModelBuilder(object):
                     self.grid.nindex, -1)).to(self.ctx.torch_device)
             m = table.shape[1]
             pd.kind = _hip.POLICY_TABLE
+            self._announce_in_place_edit(inner, table)
             self._policy_table = table
             pd.d_table = self._policy_table.data_ptr()
         else:
@@ -93,6 +103,28 @@ class ModelBuilder(object):
             for a in range(m):
                 pd.lower[a], pd.upper[a] = float(lower[a]), float(upper[a])
         return m
+
+    def _announce_in_place_edit(self, inner, table):
+        """A tensor the engine reads in place (``table`` shares its storage) keeps its pointer when
+        the caller edits it, so the model description does not change: the engine would go on
+        using what it derived from the old values (sl_policy_touch, include/sl_hip.h).  Its version
+        counter moves with every in-place write (also through a view), so that is announced here;
+        another tensor object on the same storage may have been written through any alias and is
+        announced as well.  A copied table (NumPy, another device or dtype) is a new pointer at
+        every upload."""
+        if not (isinstance(inner, type(table)) and inner.data_ptr() == table.data_ptr()):
+            self._policy_source = None
+            return
+        try:
+            version = inner._version
+        except RuntimeError:                      # an inference tensor counts no versions
+            version = None
+        state = (table.data_ptr(), tuple(inner.shape), inner.dtype, inner.device, version)
+        old = self._policy_source
+        if old is not None and old[1][0] == state[0] and (
+                old[0] is not inner or old[1] != state or version is None):
+            self.ctx.policy_touch()
+        self._policy_source = (inner, state)
 
     def _write_dynamics(self, desc, dynamics, m):
         d = self.grid.ndim
@@ -121,8 +153,11 @@ class ModelBuilder(object):
             raise TypeError('unsupported dynamics spec %r' % (dynamics,))
 
     def _upload_gp(self, heads, beta, p):
-        # _version / _table_version are process-wide unique tokens (functions._TOKENS), never reused
-        signature = tuple((gp._version, col0) for gp, _, col0 in heads) + (beta,)
+        # _version / _table_version are process-wide unique tokens (functions._TOKENS), never reused.
+        # The kernel's hyper-parameters are plain attributes that a caller may assign at any time
+        # without update_cache(): the reference feeds the kernel live at every call (functions.py
+        # :438-450) with the cached factors, so their values are part of the signature.
+        signature = tuple((gp._version, col0, _kernel_key(gp.kern, p)) for gp, _, col0 in heads) + (beta,)
         if signature == self._gp_signature:
             return
         old = self._gp_signature
@@ -132,9 +167,10 @@ class ModelBuilder(object):
             if gp.X.shape[1] != p:
                 raise ValueError('GP inputs have %d columns, expected state+action = %d'
                                  % (gp.X.shape[1], p))
-            if same_heads and old[h][0] == gp._version:
+            same_kernel = same_heads and old[h][2] == signature[h][2]
+            if same_kernel and old[h][0] == gp._version:
                 continue                                # this head is already on the device
-            if (same_heads and h not in self._gp_placeholder
+            if (same_kernel and h not in self._gp_placeholder
                     and self._follow_appends(h, gp, old[h][0])):
                 continue                                # add_data_point: new rows only
             X, Linv, alpha = gp.X, gp.cholesky_inverse, gp.alpha

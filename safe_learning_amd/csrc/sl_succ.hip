@@ -22,7 +22,9 @@
 // Policy evaluation (n_actions == 0) with a table policy whose value at every vertex is one of the
 // cached actions (the greedy policies of the loop) selects that action's entry: k_succ_select maps
 // every vertex to its action once per policy (keys rounded to 2^-40 like k_bellman4_policy), the
-// vertex's own interpolated value V(x_i) of the Bellman error comes from slot A.
+// vertex's own interpolated value V(x_i) of the Bellman error comes from slot A.  Once per policy means
+// once per ctx->policy_token: a table overwritten in place keeps its pointer and description, so its
+// owner announces the edit with sl_policy_touch.
 //
 // Validity: ctx->dynamics_token (grid, dynamics description, GP heads, structure of the value
 // triangulation - bumped by sl_model_set / sl_gp_* / sl_tri_set(0)), the range and the action set.
@@ -505,6 +507,15 @@ int sl_succ_sweep(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actions, const doub
         sl_note_kernel(ctx, false, "k_bellman_cached<d=%d, %s> (successor cache, %d actions)", variant,
                        policy ? "policy" : "max", S.n_actions);
     *done = 1;
+    return SL_OK;
+}
+
+// A policy table was overwritten in place: same pointer, same description, new values.  Whatever the
+// sweeps derived from the policy alone (the select arrays here, k_bellman4_policy's action list and
+// tile order) is keyed on policy_token and must be derived again.
+extern "C" int sl_policy_touch(sl_ctx* ctx) {
+    if (!ctx) return sl_fail(ctx, SL_ERR_INVALID, "sl_policy_touch: NULL context");
+    ++ctx->policy_token;
     return SL_OK;
 }
 

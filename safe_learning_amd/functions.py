@@ -631,7 +631,10 @@ class Triangulation(DeterministicFunction):
 
     As in the reference only ONE unit cell is triangulated (SciPy/Qhull on the cell's corners,
     ``functions.py:1019-1022``) and reused for every cell.  ``parameters`` is the ``[nindex, k]``
-    vertex table; the device copy is refreshed whenever it is assigned."""
+    vertex table; the device copy is refreshed whenever it is ASSIGNED.  The array it returns is a
+    read-only view: a write into it (``tri.parameters[i] = v``) raises ``ValueError`` instead of
+    leaving the device table old (in the reference ``parameters`` is a ``tf.Variable``, which
+    cannot be written in place either) - assign a new array: ``tri.parameters = values``."""
 
     _role = 'value'
 
@@ -684,9 +687,14 @@ class Triangulation(DeterministicFunction):
 
     @property
     def parameters(self):
-        """``[nindex, k]`` vertex table on the host; after a sweep that left the table on the GPU
-        (value iteration, policy improvement) it is copied back on first access."""
-        return self._host_parameters()
+        """``[nindex, k]`` vertex table on the host, read-only; after a sweep that left the table on
+        the GPU (value iteration, policy improvement) it is copied back on first access."""
+        table = self._host_parameters()
+        if table is None:
+            return None
+        view = table.view()
+        view.flags.writeable = False
+        return view
 
     @parameters.setter
     def parameters(self, values):
