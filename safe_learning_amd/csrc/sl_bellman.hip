@@ -20,7 +20,6 @@ __global__ __launch_bounds__(SL_BLOCK) void k_bellman(
     SlSuccDev sc = sc_in;
     if (AMAX == 0) sc.w = nullptr;
     extern __shared__ __attribute__((aligned(16))) double smem[];   // E table [head][n_pad][A]
-    __shared__ double red_max[SL_BLOCK / 64], red_sum[SL_BLOCK / 64];
     const SlDims nd = sl_dims<DT, MT>(M);
     const int d = nd.d, m = nd.m, p = nd.p;
     constexpr bool ACTIONS = AMAX > 0;
@@ -169,20 +168,7 @@ __global__ __launch_bounds__(SL_BLOCK) void k_bellman(
             lsum = fma(diff, diff, lsum);
         }
     }
-    // ---- residual statistics ----------------------------------------------------------------------
-    for (int off = 32; off >= 1; off >>= 1) {
-        lmax = fmax(lmax, __shfl_xor(lmax, off, 64));
-        lsum += __shfl_xor(lsum, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) { red_max[threadIdx.x >> 6] = lmax; red_sum[threadIdx.x >> 6] = lsum; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < SL_BLOCK / 64; ++w) { lmax = fmax(lmax, red_max[w]); lsum += red_sum[w]; }
-        // non-negative doubles order like their bit patterns
-        atomicMax(reinterpret_cast<unsigned long long*>(&stats[0]),
-                  (unsigned long long)__double_as_longlong(lmax));
-        atomicAdd(&stats[1], lsum);
-    }
+    sl_residual_reduce<SL_BLOCK, true>(lmax, lsum, stats, threadIdx.x >> 6);
 }
 
 // =============================================================================================
@@ -278,7 +264,6 @@ __global__ __launch_bounds__(64 * SL_BM_WAVES) void k_bellman_mfma(
     // barriers instead of wavefront-local ordering
     // sc.w != 0: the located successors go to the successor cache (sl_succ.hip)
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    __shared__ double red_max[SL_BM_WAVES], red_sum[SL_BM_WAVES];
     constexpr int SL_BM_SUB = SL_BM_SUB_OF(NCB * NH);
     const SlDims nd = sl_dims<DT, 1>(M);
     const int d = nd.d, p = nd.p, A = n_actions;
@@ -472,18 +457,7 @@ __global__ __launch_bounds__(64 * SL_BM_WAVES) void k_bellman_mfma(
             SL_BM_SYNC();
         }
     }
-    for (int o = 32; o >= 1; o >>= 1) {
-        lmax = fmax(lmax, __shfl_xor(lmax, o, 64));
-        lsum += __shfl_xor(lsum, o, 64);
-    }
-    if (lane == 0) { red_max[wave] = lmax; red_sum[wave] = lsum; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < SL_BM_WAVES; ++w) { lmax = fmax(lmax, red_max[w]); lsum += red_sum[w]; }
-        atomicMax(reinterpret_cast<unsigned long long*>(&stats[0]),
-                  (unsigned long long)__double_as_longlong(lmax));
-        atomicAdd(&stats[1], lsum);
-    }
+    sl_residual_reduce<64 * SL_BM_WAVES, true>(lmax, lsum, stats, wave);
 }
 
 #undef SL_BM_SYNC
@@ -505,7 +479,6 @@ __global__ __launch_bounds__(64 * SL_BM_WAVES) void k_bellman_policy_mfma(
     const SlDevModel M, const SlGpDev gp, SlAux aux, SlBellmanPack pk, int64_t lo, int64_t hi,
     const double* __restrict__ pack, double* __restrict__ v_new, double* __restrict__ stats) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    __shared__ double red_max[SL_BM_WAVES], red_sum[SL_BM_WAVES];
     const SlDims nd = sl_dims<DT, 1>(M);
     const int d = nd.d, p = nd.p;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -689,55 +662,31 @@ __global__ __launch_bounds__(64 * SL_BM_WAVES) void k_bellman_policy_mfma(
             lsum = fma(diff, diff, lsum);
         }
     }
-    for (int o = 32; o >= 1; o >>= 1) {
-        lmax = fmax(lmax, __shfl_xor(lmax, o, 64));
-        lsum += __shfl_xor(lsum, o, 64);
-    }
-    if (lane == 0) { red_max[wave] = lmax; red_sum[wave] = lsum; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < SL_BM_WAVES; ++w) { lmax = fmax(lmax, red_max[w]); lsum += red_sum[w]; }
-        atomicMax(reinterpret_cast<unsigned long long*>(&stats[0]),
-                  (unsigned long long)__double_as_longlong(lmax));
-        atomicAdd(&stats[1], lsum);
-    }
+    sl_residual_reduce<64 * SL_BM_WAVES, true>(lmax, lsum, stats, wave);
 }
 
-// Sets *done = 1 when the matrix-core path handled the sweep (one GP head whose outputs span the
-// state, at most 96 (action, output) columns); otherwise the caller runs the VALU kernel.
-static int bellman_mfma(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actions, double* d_v_new,
-                        int32_t* d_argmax, double* d_q, double* d_stats, int* done) {
-    *done = 0;
+// heads with a sum-of-products kernel: the matrix-core sweeps generate RBF values (state and action
+// factors); such models take k_bellman's one-(x, u)-at-a-time path
+static bool has_other_kernels(const sl_ctx* ctx) {
+    for (int h = 0; h < ctx->h_gp.nheads; ++h)
+        if (ctx->gp_heads[h].d_kernel) return true;
+    return false;
+}
+
+// The 16x16x4 kernels: one GP head whose outputs span the state, at most 96 (action, output)
+// columns, or a FunctionStack of 2 (d = 2) / 4 (d = 4) single-output heads.
+static int bellman_mfma(sl_ctx* ctx, const SlBellmanArgs& b) {
     const SlDevModel& M = ctx->h_model;
-    if (ctx->env.bellman_mfma == 0) return SL_OK;
-    const int nheads = ctx->h_gp.nheads;
-    if (M.m.policy.m != 1 || nheads < 1 || nheads > SL_BM_HEADS) return SL_OK;
+    const int64_t lo = b.lo, hi = b.hi;
+    const int n_actions = b.n_actions, nheads = ctx->h_gp.nheads;
     const int variant = sl_dim_variant_of(M);
-    if (variant != 4 && variant != 2) return SL_OK;        // compiled for 2 and 4 state dimensions
-    const SlGpHeadHost& hh = ctx->gp_heads[0];
     const int d = M.m.grid.d;
     SlBellmanPack pk;
     memset(&pk, 0, sizeof(pk));
     const bool policy_mode = n_actions == 0;
-    if (!policy_mode) {
-        // the 4x4x4 kernel (sl_bellman4.hip) takes the sweeps it is built for
-        int done4 = 0;
-        const int rc4 = sl_bellman4_launch(ctx, lo, hi, n_actions, d_v_new, d_argmax, d_q, d_stats, &done4);
-        if (rc4 != SL_OK) return rc4;
-        if (done4) { *done = 1; return SL_OK; }
-    }
-    if (policy_mode) {
-        // worthwhile for piecewise-constant policies; one shared-input head
-        const int pkind = M.m.policy.kind;
-        if (pkind != SL_POLICY_TRI && pkind != SL_POLICY_TABLE && pkind != SL_POLICY_CONST) return SL_OK;
-        // few distinct actions, last axis a multiple of 64 cells: the 4x4x4 kernel (sl_bellman4.hip)
-        int done4 = 0;
-        const int rc4 = sl_bellman4_policy_launch(ctx, lo, hi, d_v_new, d_stats, &done4);
-        if (rc4 != SL_OK) return rc4;
-        if (done4) { *done = 1; return SL_OK; }
+    if (policy_mode)
         for (int h = 0; h < nheads; ++h)
-            if (ctx->gp_heads[h].dout > SL_D) return SL_OK;
-    }
+            if (ctx->gp_heads[h].dout > SL_D) return SL_DECLINED;
     // one head with D outputs (1, 3 or 6 column blocks), or a FunctionStack of 2 (d = 2) / 4 (d = 4)
     // single-output heads with one column block each
     int ncb = 0, n_pad_max = 0;
@@ -746,8 +695,8 @@ static int bellman_mfma(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actions, doub
         ncb = c > ncb ? c : ncb;
         n_pad_max = ctx->gp_heads[h].n_pad > n_pad_max ? ctx->gp_heads[h].n_pad : n_pad_max;
     }
-    if (ncb > 6) return SL_OK;
-    if (!policy_mode && nheads > 1 && (ncb > 1 || nheads != d)) return SL_OK;
+    if (ncb > 6) return SL_DECLINED;
+    if (!policy_mode && nheads > 1 && (ncb > 1 || nheads != d)) return SL_DECLINED;
     const int ncb_t = policy_mode ? 0 : (ncb <= 1 ? 1 : (ncb <= 3 ? 3 : 6));
     pk.ncb = ncb_t;
     pk.nheads = nheads;
@@ -764,21 +713,14 @@ static int bellman_mfma(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actions, doub
             pk.toff[h][k] = toff;
             toff += (int64_t)M.m.grid.num_points[k] * n_pad;
         }
-        if (toff + 4 * (int64_t)n_pad * M.m.grid.num_points[d - 1] > 0x0fffffffll) return SL_OK;
+        if (toff + 4 * (int64_t)n_pad * M.m.grid.num_points[d - 1] > 0x0fffffffll) return SL_DECLINED;
         cursor += toff;
     }
     const size_t lds = policy_mode
         ? sizeof(double) * (size_t)SL_BM_WAVES * (n_pad_max + 64 * 16 + SL_BP_MAXG)
         : sizeof(double) * (size_t)SL_BM_WAVES * SL_BM_SUB_OF(ncb_t * nheads) * pk.rowlen;
-    if (lds + sizeof(SlTri) + 512 > 160 * 1024) return SL_OK;
-    const size_t need = sizeof(double) * (size_t)cursor;
-    if (need > ctx->scratch_bytes) {
-        if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
-        ctx->d_scratch = nullptr;
-        ctx->scratch_bytes = 0;
-        SL_HIP_CHECK(ctx, hipMalloc(&ctx->d_scratch, need));
-        ctx->scratch_bytes = need;
-    }
+    if (lds + sizeof(SlTri) + 512 > 160 * 1024) return SL_DECLINED;
+    SL_HIP_CHECK(ctx, sl_grow(ctx, &ctx->d_scratch, &ctx->scratch_bytes, sizeof(double) * (size_t)cursor));
     double* pack = reinterpret_cast<double*>(ctx->d_scratch);
     hipLaunchKernelGGL(k_bellman_pack, dim3(512), dim3(256), 0, ctx->stream, ctx->h_model, ctx->h_gp,
                        pk, n_actions, ctx->d_actions, pack);
@@ -795,13 +737,12 @@ static int bellman_mfma(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actions, doub
                                                   hipFuncAttributeMaxDynamicSharedMemorySize,     \
                                                   (int)lds));                                     \
             hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * SL_BM_WAVES), lds, ctx->stream,      \
-                               ctx->h_model, ctx->h_gp, aux, pk, lo, hi, pack, d_v_new, d_stats); \
+                               ctx->h_model, ctx->h_gp, aux, pk, lo, hi, pack, b.v_new, b.stats); \
         } while (0)
         if (variant == 4) SL_BP_LAUNCH(4); else SL_BP_LAUNCH(2);
 #undef SL_BP_LAUNCH
         SL_HIP_CHECK(ctx, hipGetLastError());
         sl_note_kernel(ctx, false, "k_bellman_policy_mfma<d=%d>", variant == 4 ? 4 : 2);
-        *done = 1;
         return SL_OK;
     }
     const int bm_flags = sl_diag_flags("SL_BM_FLAGS");  // (development builds only: 0 in the shipped library)
@@ -819,7 +760,7 @@ static int bellman_mfma(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actions, doub
                                               (int)lds));                                         \
         hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * SL_BM_WAVES), lds, ctx->stream,          \
                            ctx->h_model, ctx->h_gp, aux, pk, lo, hi, n_actions, ctx->d_actions,   \
-                           pack, d_v_new, d_argmax, d_q, d_stats, bm_flags, fill);                \
+                           pack, b.v_new, b.argmax, b.q, b.stats, bm_flags, fill);                \
     } while (0)
 #define SL_BM_DIMS(N_)                                  \
     do {                                                \
@@ -837,13 +778,62 @@ static int bellman_mfma(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actions, doub
     SL_HIP_CHECK(ctx, hipGetLastError());
     sl_note_kernel(ctx, false, "k_bellman_mfma<d=%d, column blocks=%d, heads=%d>", variant == 4 ? 4 : 2,
                    nheads > 1 ? 1 : ncb_t, nheads);
-    *done = 1;
     return SL_OK;
 }
 
-static int bellman_sweep_uncached(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actions,
-                                  const double* h_actions, double* d_v_new, int32_t* d_argmax,
-                                  double* d_q, double* d_stats, bool is_gp, bool other_kernels);
+// k_bellman: any model, one thread per vertex.  Never declines.
+static int bellman_valu(sl_ctx* ctx, const SlBellmanArgs& b) {
+    const SlDevModel& M = ctx->h_model;
+    const int64_t lo = b.lo, hi = b.hi;
+    const int n_actions = b.n_actions;
+    const bool factorised = M.m.dynamics.kind == SL_DYN_GP && !has_other_kernels(ctx);
+    const int amax = n_actions == 0 ? 0 : (n_actions <= 3 ? 3 : (n_actions <= 9 ? 9 : SL_MAX_ACTIONS));
+    size_t lds = 0;                               // the action-factor table
+    if (n_actions > 0 && factorised)
+        for (int h = 0; h < ctx->h_gp.nheads; ++h) lds += sizeof(double) * (size_t)ctx->gp_heads[h].n_pad * amax;
+    if (lds > 150 * 1024)
+        return sl_fail(ctx, SL_ERR_UNSUPPORTED, "sl_bellman_sweep: action-factor table needs %zu "
+                                                "bytes of LDS", lds);
+    int64_t blocks64 = (hi - lo + SL_BLOCK - 1) / SL_BLOCK;
+    const int cap = ctx->num_cu * 4;
+    const int blocks = (int)(blocks64 < cap ? blocks64 : cap);
+    SlAux aux{ctx->d_tri, ctx->d_net};
+    const int variant = sl_dim_variant_of(M);
+#define SL_BELLMAN(ACT, D_, M_)                                                                  \
+    do {                                                                                         \
+        auto kern = k_bellman<ACT, D_, M_>;                                                      \
+        if (lds > 48 * 1024)                                                                     \
+            SL_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),           \
+                                                  hipFuncAttributeMaxDynamicSharedMemorySize,    \
+                                                  (int)lds));                                    \
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(SL_BLOCK), lds, ctx->stream, ctx->h_model,   \
+                           ctx->h_gp, aux, lo, hi, n_actions, ctx->d_actions, b.v_new, b.argmax, \
+                           b.q, b.stats, fill);                                                  \
+    } while (0)
+#define SL_BELLMAN_DIMS(AM_)                                     \
+    do {                                                        \
+        if (variant == 4) SL_BELLMAN(AM_, 4, 1);                \
+        else if (variant == 2) SL_BELLMAN(AM_, 2, 1);           \
+        else if (variant == 1) SL_BELLMAN(AM_, 1, 1);           \
+        else SL_BELLMAN(AM_, 0, 0);                             \
+    } while (0)
+    // (DT = 0, the runtime-dimension flavour, locates through sl_tri_eval: nothing to cache)
+    SlSuccDev fill;
+    memset(&fill, 0, sizeof(fill));
+    if (ctx->succ.filling && variant != 0) {
+        fill = sl_succ_view(ctx);
+        ctx->succ.filled = true;
+    }
+    sl_note_kernel(ctx, false, "k_bellman<actions<=%d, d=%d>", amax, variant);
+    if (amax == 3) SL_BELLMAN_DIMS(3);
+    else if (amax == 9) SL_BELLMAN_DIMS(9);
+    else if (amax == SL_MAX_ACTIONS) SL_BELLMAN_DIMS(SL_MAX_ACTIONS);
+    else SL_BELLMAN_DIMS(0);
+#undef SL_BELLMAN_DIMS
+#undef SL_BELLMAN
+    SL_HIP_CHECK(ctx, hipGetLastError());
+    return SL_OK;
+}
 
 extern "C" int sl_bellman_sweep(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actions,
                                 const double* h_actions, double* d_v_new, int32_t* d_argmax,
@@ -875,11 +865,6 @@ extern "C" int sl_bellman_sweep(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actio
     const bool is_gp = M.m.dynamics.kind == SL_DYN_GP;
     if (is_gp && ctx->h_gp.nheads < 1)
         return sl_fail(ctx, SL_ERR_INVALID, "sl_bellman_sweep: GP dynamics without heads");
-    // heads with a sum-of-products kernel: the matrix-core sweeps generate RBF values (state and
-    // action factors); such models take k_bellman's one-(x, u)-at-a-time path
-    bool other_kernels = false;
-    if (is_gp)
-        for (int h = 0; h < ctx->h_gp.nheads; ++h) other_kernels = other_kernels || ctx->gp_heads[h].d_kernel;
     SL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     SL_HIP_CHECK(ctx, hipMemsetAsync(d_stats, 0, 2 * sizeof(double), ctx->stream));
     ctx->last_kernel[0] = 0;
@@ -887,89 +872,35 @@ extern "C" int sl_bellman_sweep(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actio
     // policy evaluation with a network policy: one action per vertex first (a max sweep ignores the policy)
     SlPolicyTableScope network_policy(ctx, n_actions == 0 ? lo : 0, n_actions == 0 ? hi : 0, nullptr);
     if (network_policy.rc) return network_policy.rc;
+    const SlBellmanArgs b{lo, hi, n_actions, h_actions, d_v_new, d_argmax, d_q, d_stats};
     // The successors of (vertex, action) do not depend on the value table
     // (reinforcement_learning.py:89-104): a sweep over a range / action set / dynamics that an
     // earlier max sweep located is served from the successor cache (sl_succ.hip); otherwise a max
-    // sweep fills it on its way (the kernels that can: k_bellman_lookup, k_bellman).
-    {
-        int done = 0;
-        int rc = sl_succ_sweep(ctx, lo, hi, n_actions, h_actions, d_v_new, d_argmax, d_q, d_stats, &done);
-        if (rc) return rc;
-        if (done) return SL_OK;
+    // sweep fills it on its way (the kernels that can: k_bellman_lookup, k_bellman_mfma, k_bellman).
+    int rc = sl_succ_sweep(ctx, b);
+    if (rc != SL_DECLINED) return rc;
+    if (n_actions > 0) {
+        SL_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_actions, h_actions, sizeof(double) * n_actions * M.m.policy.m,
+                                         hipMemcpyHostToDevice, ctx->stream));
+        SL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     }
     ctx->succ.filling = ctx->succ.filled = false;
     if (n_actions > 0) ctx->succ.filling = sl_succ_begin_fill(ctx, lo, hi, n_actions, h_actions).w != nullptr;
-    const int rc_sweep = bellman_sweep_uncached(ctx, lo, hi, n_actions, h_actions, d_v_new, d_argmax, d_q,
-                                                d_stats, is_gp, other_kernels);
-    if (rc_sweep == SL_OK && ctx->succ.filling && ctx->succ.filled) sl_succ_commit(ctx);
+    // The matrix-core kernels generate the RBF values of GP heads (no sum-of-products kernels) on a
+    // 2-D or 4-D grid with one action dimension; policy evaluation takes them for piecewise-constant
+    // policies only.  SL_BELLMAN_MFMA=0 keeps every sweep on k_bellman.
+    const int variant = sl_dim_variant_of(M), pkind = M.m.policy.kind;
+    const bool matrix_cores =
+        is_gp && !has_other_kernels(ctx) && ctx->env.bellman_mfma != 0 && M.m.policy.m == 1 &&
+        ctx->h_gp.nheads <= SL_BM_HEADS && (variant == 4 || variant == 2) &&
+        (n_actions > 0 || pkind == SL_POLICY_TRI || pkind == SL_POLICY_TABLE || pkind == SL_POLICY_CONST);
+    rc = SL_DECLINED;
+    if (matrix_cores) rc = n_actions > 0 ? sl_bellman4_launch(ctx, b) : sl_bellman4_policy_launch(ctx, b);
+    if (rc == SL_DECLINED && matrix_cores) rc = bellman_mfma(ctx, b);
+    if (rc == SL_DECLINED) rc = bellman_valu(ctx, b);
+    if (rc == SL_OK && ctx->succ.filling && ctx->succ.filled) sl_succ_commit(ctx);
     ctx->succ.filling = ctx->succ.filled = false;
-    return rc_sweep;
-}
-
-static int bellman_sweep_uncached(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actions,
-                                  const double* h_actions, double* d_v_new, int32_t* d_argmax,
-                                  double* d_q, double* d_stats, bool is_gp, bool other_kernels) {
-    const SlDevModel& M = ctx->h_model;
-    size_t lds = 0;
-    int amax = 0;
-    if (n_actions > 0) {
-        SL_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_actions, h_actions,
-                                         sizeof(double) * n_actions * M.m.policy.m,
-                                         hipMemcpyHostToDevice, ctx->stream));
-        SL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        amax = n_actions <= 3 ? 3 : (n_actions <= 9 ? 9 : SL_MAX_ACTIONS);
-        if (is_gp && !other_kernels)
-            for (int h = 0; h < ctx->h_gp.nheads; ++h)
-                lds += sizeof(double) * (size_t)ctx->gp_heads[h].n_pad * amax;
-    }
-    if (is_gp && !other_kernels) {                // dense K_nm @ alpha contraction on the matrix cores
-        int done = 0;
-        int rc = bellman_mfma(ctx, lo, hi, n_actions, d_v_new, d_argmax, d_q, d_stats, &done);
-        if (rc) return rc;
-        if (done) return SL_OK;
-    }
-    if (lds > 150 * 1024)
-        return sl_fail(ctx, SL_ERR_UNSUPPORTED, "sl_bellman_sweep: action-factor table needs %zu "
-                                                "bytes of LDS", lds);
-    int64_t blocks64 = (hi - lo + SL_BLOCK - 1) / SL_BLOCK;
-    const int cap = ctx->num_cu * 4;
-    const int blocks = (int)(blocks64 < cap ? blocks64 : cap);
-    SlAux aux{ctx->d_tri, ctx->d_net};
-    const int variant = sl_dim_variant_of(M);
-#define SL_BELLMAN(ACT, D_, M_)                                                                  \
-    do {                                                                                         \
-        auto kern = k_bellman<ACT, D_, M_>;                                                      \
-        if (lds > 48 * 1024)                                                                     \
-            SL_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),           \
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize,    \
-                                                  (int)lds));                                    \
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(SL_BLOCK), lds, ctx->stream, ctx->h_model,   \
-                           ctx->h_gp, aux, lo, hi, n_actions, ctx->d_actions, d_v_new, d_argmax, \
-                           d_q, d_stats, fill);                                                  \
-    } while (0)
-#define SL_BELLMAN_DIMS(AM_)                                     \
-    do {                                                        \
-        if (variant == 4) SL_BELLMAN(AM_, 4, 1);                \
-        else if (variant == 2) SL_BELLMAN(AM_, 2, 1);           \
-        else if (variant == 1) SL_BELLMAN(AM_, 1, 1);           \
-        else SL_BELLMAN(AM_, 0, 0);                             \
-    } while (0)
-    // (DT = 0, the runtime-dimension flavour, locates through sl_tri_eval: nothing to cache)
-    SlSuccDev fill;
-    memset(&fill, 0, sizeof(fill));
-    if (ctx->succ.filling && variant != 0) {
-        fill = sl_succ_view(ctx);
-        ctx->succ.filled = true;
-    }
-    sl_note_kernel(ctx, false, "k_bellman<actions<=%d, d=%d>", amax, variant);
-    if (amax == 3) SL_BELLMAN_DIMS(3);
-    else if (amax == 9) SL_BELLMAN_DIMS(9);
-    else if (amax == SL_MAX_ACTIONS) SL_BELLMAN_DIMS(SL_MAX_ACTIONS);
-    else SL_BELLMAN_DIMS(0);
-#undef SL_BELLMAN_DIMS
-#undef SL_BELLMAN
-    SL_HIP_CHECK(ctx, hipGetLastError());
-    return SL_OK;
+    return rc;
 }
 
 // =============================================================================================
@@ -1058,13 +989,7 @@ extern "C" int sl_eval_points(sl_ctx* ctx, int what, int64_t n, const double* d_
     // run the sweep kernels over the point list; d_out receives the per-point record
     // [decrease, threshold, mean[d], err[d]]
     const size_t need = sizeof(uint64_t) * (size_t)((n + 63) / 64) + sizeof(sl_sweep_result);
-    if (need > ctx->scratch_bytes) {
-        if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
-        ctx->d_scratch = nullptr;
-        ctx->scratch_bytes = 0;
-        SL_HIP_CHECK(ctx, hipMalloc(&ctx->d_scratch, need));
-        ctx->scratch_bytes = need;
-    }
+    SL_HIP_CHECK(ctx, sl_grow(ctx, &ctx->d_scratch, &ctx->scratch_bytes, need));
     sl_sweep_result* res = reinterpret_cast<sl_sweep_result*>(ctx->d_scratch);
     uint64_t* bits = reinterpret_cast<uint64_t*>(res + 1);
     return sl_sweep_any(ctx, 0, n, nullptr, nullptr, bits, res, d_out, d_points);

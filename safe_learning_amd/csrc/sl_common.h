@@ -40,8 +40,7 @@ struct SlEnv {
     int gp4_seeds = -1;              // SL_GP4_SEEDS=0: every k_x chunk from the exponentials
     int gp4_tickets = -1;            // SL_GP4_TICKETS=0/1: fixed tile list / tile counter
     int bellman_mfma = -1;           // SL_BELLMAN_MFMA=0: Bellman sweeps on the FP64-VALU kernel
-    int bellman4 = -1, bellman4_policy = -1, bellman4_policy_cache = -1, bellman4_policy_verbose = -1;
-    int bellman4_ragged = -1, bellman4_quarter = -1, bellman4_split = -1, bellman4_round = -1;
+    int bellman4 = -1, bellman4_policy = -1, bellman4_ragged = -1;
     int bellman4_shared = -1;        // SL_BELLMAN4*: see DESIGN.md "Environment switches"
     int probe_blocks_per_cu = -1;    // SL_PROBE_BLOCKS_PER_CU (sl_debug_fp64_rate)
     int succ_cache = -1;             // SL_SUCC_CACHE=0: no successor cache
@@ -175,9 +174,22 @@ SlSuccDev sl_succ_view(const sl_ctx* ctx);
 // budget, shapes the cache does not take); marks the cache invalid until sl_succ_commit
 SlSuccDev sl_succ_begin_fill(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actions, const double* h_actions);
 void sl_succ_commit(sl_ctx* ctx);
-// *done = 1 when the sweep was served from the cache
-int sl_succ_sweep(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actions, const double* h_actions,
-                  double* d_v_new, int32_t* d_argmax, double* d_q, double* d_stats, int* done);
+
+// The arguments of one sl_bellman_sweep call (include/sl_hip.h), handed to each of its launchers in
+// turn: the successor cache (sl_succ_sweep), the 4x4x4 kernels (sl_bellman4_launch /
+// sl_bellman4_policy_launch), the 16x16x4 kernels and k_bellman.  A launcher returns SL_DECLINED
+// to leave the sweep to the next one, otherwise SL_OK or an error.
+struct SlBellmanArgs {
+    int64_t lo, hi;
+    int n_actions;             // 0: policy evaluation
+    const double* h_actions;   // [n_actions] (host; ctx->d_actions holds the uploaded copy)
+    double* v_new;             // [hi - lo]
+    int32_t* argmax;           // [hi - lo] or null
+    double* q;                 // [hi - lo][n_actions] or null
+    double* stats;             // [2]: max |V_new - V_old|, Bellman error (policy evaluation)
+};
+#define SL_DECLINED 1          // internal only: the public codes are 0 and negative
+int sl_succ_sweep(sl_ctx* ctx, const SlBellmanArgs& b);
 
 // Brackets an entry point's launches with a pair of events when sl_timing_configure asked for it
 // (bench.py's kernel durations: recorded by the library on its own stream, no host objects per call)
@@ -231,10 +243,8 @@ bool sl_gp_small_supports(sl_ctx* ctx, const SlDevModel& model);
 int sl_gp_small_launch(sl_ctx* ctx, const SlDevModel& model, int64_t lo, int64_t hi,
                        const uint64_t* d_init_bits, const double* d_values, uint64_t* d_neg_bits,
                        int* nblocks, double* d_dbg, const double* d_points);
-int sl_bellman4_launch(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actions, double* d_v_new,
-                       int32_t* d_argmax, double* d_q, double* d_stats, int* done);
-int sl_bellman4_policy_launch(sl_ctx* ctx, int64_t lo, int64_t hi, double* d_v_new, double* d_stats,
-                              int* done);
+int sl_bellman4_launch(sl_ctx* ctx, const SlBellmanArgs& b);
+int sl_bellman4_policy_launch(sl_ctx* ctx, const SlBellmanArgs& b);
 int sl_nn_values_launch(sl_ctx* ctx, int64_t lo, int64_t hi, double* d_values);
 int sl_nn_check_launch(sl_ctx* ctx, int64_t lo, int64_t hi, const uint64_t* d_init_bits,
                        const double* d_values, const double* d_records, uint64_t* d_neg_bits,
@@ -247,6 +257,29 @@ int sl_nn_check_launch(sl_ctx* ctx, int64_t lo, int64_t hi, const uint64_t* d_in
             return sl_fail((ctx), SL_ERR_HIP, "%s failed: %s (%s:%d)", #call,               \
                            hipGetErrorString(e__), __FILE__, __LINE__);                     \
     } while (0)
+
+// Grows a context-owned device buffer to at least `need` bytes (min_bytes at least when it
+// allocates).  The contents are not kept; the stream is synchronised before an old buffer is freed.
+// On failure *buf is null and *bytes 0 (the HIP error is returned, and left as the last error).
+template <typename T>
+hipError_t sl_grow(sl_ctx* ctx, T** buf, size_t* bytes, size_t need, size_t min_bytes = 0) {
+    if (need <= *bytes) return hipSuccess;
+    if (*buf) {
+        const hipError_t e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) return e;
+        (void)hipFree(*buf);
+    }
+    *buf = nullptr;
+    *bytes = 0;
+    const size_t alloc = need > min_bytes ? need : min_bytes;
+    const hipError_t e = hipMalloc(buf, alloc);
+    if (e != hipSuccess) {
+        *buf = nullptr;
+        return e;
+    }
+    *bytes = alloc;
+    return hipSuccess;
+}
 
 // The model (and the GP head table) travel BY VALUE in the kernel-argument segment: every field
 // is then fetched with scalar loads and used as an SGPR operand.  Only the large tables
@@ -288,6 +321,35 @@ __device__ __forceinline__ void sl_block_reduce_key(uint64_t& v, int64_t& i, uin
         for (int w = 1; w < nw; ++w) {
             if (IS_MIN) sl_key_min(v, i, sv[w], si[w]); else sl_key_max(v, i, sv[w], si[w]);
         }
+    }
+}
+
+// ---- residual statistics of the Bellman sweeps ----------------------------------------------
+// stats[0] = max(stats[0], max of lmax over the workgroup): non-negative doubles order like their
+// bit patterns, so an integer atomicMax does it.  SUM: stats[1] += sum of lsum over the workgroup.
+// Called once by every thread of the THREADS-thread workgroup, after its last cell; wave =
+// threadIdx.x >> 6 (the caller's own copy: a scalar where it has one).
+template <int THREADS, bool SUM>
+__device__ __forceinline__ void sl_residual_reduce(double lmax, double lsum, double* stats, int wave) {
+    constexpr int NW = THREADS / 64;
+    __shared__ double red_max[NW], red_sum[NW];
+    for (int off = 32; off >= 1; off >>= 1) {
+        lmax = fmax(lmax, __shfl_xor(lmax, off, 64));
+        if (SUM) lsum += __shfl_xor(lsum, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red_max[wave] = lmax;
+        if (SUM) red_sum[wave] = lsum;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < NW; ++w) {
+            lmax = fmax(lmax, red_max[w]);
+            if (SUM) lsum += red_sum[w];
+        }
+        atomicMax(reinterpret_cast<unsigned long long*>(&stats[0]),
+                  (unsigned long long)__double_as_longlong(lmax));
+        if (SUM) atomicAdd(&stats[1], lsum);
     }
 }
 

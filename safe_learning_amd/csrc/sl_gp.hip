@@ -535,13 +535,7 @@ extern "C" int sl_gp_append_point(sl_ctx* ctx, int head, const double* h_x, cons
     SL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     SL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     const size_t need = sizeof(double) * (size_t)(n + 1 + hh.p + hh.dout);
-    if (need > ctx->scratch_bytes) {
-        if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
-        ctx->d_scratch = nullptr;
-        ctx->scratch_bytes = 0;
-        SL_HIP_CHECK(ctx, hipMalloc(&ctx->d_scratch, need));
-        ctx->scratch_bytes = need;
-    }
+    SL_HIP_CHECK(ctx, sl_grow(ctx, &ctx->d_scratch, &ctx->scratch_bytes, need));
     std::vector<double> stage((size_t)(n + 1 + hh.p + hh.dout));
     for (int c = 0; c <= n; ++c) stage[c] = h_linv_row[c];
     for (int q = 0; q < hh.p; ++q) stage[n + 1 + q] = h_x[q] / hh.lengthscales[q];   // as sl_gp_set_head

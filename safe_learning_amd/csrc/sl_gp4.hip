@@ -946,14 +946,7 @@ static int launch4(sl_ctx* ctx, const SlDevModel& model, int64_t lo, int64_t hi,
     }
     const size_t head_bytes = 16;                               // the tile counter
     const size_t seed_bytes = head_bytes + (size_t)gp4::RUNS * blocks * seed_chunks * gp4::W * 128 * sizeof(double);
-    if (seed_bytes > ctx->gp4_seed_bytes) {
-        SL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->d_gp4_seeds) (void)hipFree(ctx->d_gp4_seeds);
-        ctx->d_gp4_seeds = nullptr;
-        ctx->gp4_seed_bytes = 0;
-        SL_HIP_CHECK(ctx, hipMalloc(&ctx->d_gp4_seeds, seed_bytes));
-        ctx->gp4_seed_bytes = seed_bytes;
-    }
+    SL_HIP_CHECK(ctx, sl_grow(ctx, &ctx->d_gp4_seeds, &ctx->gp4_seed_bytes, seed_bytes));
     // SL_GP4_SEEDS=0: every generation from scratch (same k_x bit for bit: the test of that)
     double* seeds = ctx->env.gp4_seeds == 0 ? nullptr : ctx->d_gp4_seeds + head_bytes / sizeof(double);
     unsigned long long* ticket = reinterpret_cast<unsigned long long*>(ctx->d_gp4_seeds);

@@ -66,12 +66,7 @@ void sl_env_read(SlEnv* e) {
     e->bellman_mfma = env_int("SL_BELLMAN_MFMA");
     e->bellman4 = env_int("SL_BELLMAN4");
     e->bellman4_policy = env_int("SL_BELLMAN4_POLICY");
-    e->bellman4_policy_cache = env_int("SL_BELLMAN4_POLICY_CACHE");
-    e->bellman4_policy_verbose = env_int("SL_BELLMAN4_POLICY_VERBOSE");
     e->bellman4_ragged = env_int("SL_BELLMAN4_RAGGED");
-    e->bellman4_quarter = env_int("SL_BELLMAN4_QUARTER");
-    e->bellman4_split = env_int("SL_BELLMAN4_SPLIT");
-    e->bellman4_round = env_int("SL_BELLMAN4_ROUND");
     e->bellman4_shared = env_int("SL_BELLMAN4_SHARED");
     e->probe_blocks_per_cu = env_int("SL_PROBE_BLOCKS_PER_CU");
     e->succ_cache = env_int("SL_SUCC_CACHE");
@@ -836,13 +831,7 @@ int sl_sweep_any(sl_ctx* ctx, int64_t lo, int64_t hi, const uint64_t* d_init_bit
             const int d = ctx->h_model.m.grid.d;
             const size_t need = sizeof(double) * (size_t)(hi - lo) * (2 + 2 * d) +
                                 sizeof(uint64_t) * (size_t)((hi - lo + 63) / 64 + 1);
-            if (need > ctx->records_bytes) {
-                if (ctx->d_records) (void)hipFree(ctx->d_records);
-                ctx->d_records = nullptr;
-                ctx->records_bytes = 0;
-                SL_HIP_CHECK(ctx, hipMalloc(&ctx->d_records, need));
-                ctx->records_bytes = need;
-            }
+            SL_HIP_CHECK(ctx, sl_grow(ctx, &ctx->d_records, &ctx->records_bytes, need));
             double* rec = reinterpret_cast<double*>(ctx->d_records);
             uint64_t* tmp_bits = reinterpret_cast<uint64_t*>(rec + (size_t)(hi - lo) * (2 + 2 * d));
             SlDevModel posterior_only = sl_posterior_only(ctx->h_model);
@@ -862,13 +851,7 @@ int sl_sweep_any(sl_ctx* ctx, int64_t lo, int64_t hi, const uint64_t* d_init_bit
         const size_t rec_doubles = (size_t)(hi - lo) * (2 + 2 * d), act_doubles = (size_t)(hi - lo) * m;
         const size_t need = sizeof(double) * (rec_doubles + act_doubles) +
                             sizeof(uint64_t) * (size_t)((hi - lo + 63) / 64 + 1);
-        if (need > ctx->records_bytes) {
-            if (ctx->d_records) (void)hipFree(ctx->d_records);
-            ctx->d_records = nullptr;
-            ctx->records_bytes = 0;
-            SL_HIP_CHECK(ctx, hipMalloc(&ctx->d_records, need));
-            ctx->records_bytes = need;
-        }
+        SL_HIP_CHECK(ctx, sl_grow(ctx, &ctx->d_records, &ctx->records_bytes, need));
         double* rec = reinterpret_cast<double*>(ctx->d_records);
         double* act = rec + rec_doubles;
         uint64_t* tmp_bits = reinterpret_cast<uint64_t*>(act + act_doubles);

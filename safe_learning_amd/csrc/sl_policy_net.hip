@@ -126,15 +126,11 @@ SlPolicyTableScope::SlPolicyTableScope(sl_ctx* c, int64_t lo, int64_t hi, const 
     const size_t need = sizeof(double) * (size_t)(hi - lo) * m;
     if (need > ctx->policy_actions_bytes) {
         if (hipSetDevice(ctx->device) != hipSuccess) { rc = sl_fail(ctx, SL_ERR_HIP, "hipSetDevice failed"); return; }
-        if (ctx->d_policy_actions) (void)hipFree(ctx->d_policy_actions);
-        ctx->d_policy_actions = nullptr;
-        ctx->policy_actions_bytes = 0;
-        if (hipMalloc(&ctx->d_policy_actions, need) != hipSuccess) {
+        if (sl_grow(ctx, &ctx->d_policy_actions, &ctx->policy_actions_bytes, need) != hipSuccess) {
             (void)hipGetLastError();
             rc = sl_fail(ctx, SL_ERR_NOMEM, "network policy: %zu bytes for the action table", need);
             return;
         }
-        ctx->policy_actions_bytes = need;
     }
     double* act = reinterpret_cast<double*>(ctx->d_policy_actions);
     hipLaunchKernelGGL(k_policy_network, dim3(sl_grid_blocks(hi - lo)), dim3(SL_BLOCK), 0, ctx->stream, M, net,

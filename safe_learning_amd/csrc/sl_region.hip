@@ -202,13 +202,7 @@ extern "C" int sl_lyapunov_region(sl_ctx* ctx, const double* d_values, int64_t s
     SL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     // scratch: [c_ub, changed] + the two stop nodes + the picked last pop
     const size_t need = 5 * sizeof(double);
-    if (need > ctx->scratch_bytes) {
-        if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
-        ctx->d_scratch = nullptr;
-        ctx->scratch_bytes = 0;
-        SL_HIP_CHECK(ctx, hipMalloc(&ctx->d_scratch, 4096));
-        ctx->scratch_bytes = 4096;
-    }
+    SL_HIP_CHECK(ctx, sl_grow(ctx, &ctx->d_scratch, &ctx->scratch_bytes, need, 4096));
     double* state = reinterpret_cast<double*>(ctx->d_scratch);
     long long* stop = reinterpret_cast<long long*>(state + 2);
     const int blocks = sl_grid_blocks(g.nindex);

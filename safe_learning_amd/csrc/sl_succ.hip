@@ -260,6 +260,8 @@ __global__ __launch_bounds__(256) void k_bellman_cached(
             lsum = fma(diff, diff, lsum);
         }
     }
+    // (not sl_residual_reduce: max sweeps reduce their zero lsum too, which keeps this kernel's code
+    // and LDS size as they are)
     for (int o = 32; o >= 1; o >>= 1) {
         lmax = fmax(lmax, __shfl_xor(lmax, o, 64));
         lsum += __shfl_xor(lsum, o, 64);
@@ -398,34 +400,33 @@ __global__ __launch_bounds__(256) void k_succ_policy_miss(
     }
 }
 
-int sl_succ_sweep(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actions, const double* h_actions,
-                  double* d_v_new, int32_t* d_argmax, double* d_q, double* d_stats, int* done) {
-    *done = 0;
+int sl_succ_sweep(sl_ctx* ctx, const SlBellmanArgs& b) {
+    const int64_t lo = b.lo, hi = b.hi;
     auto& S = ctx->succ;
     if (!S.enabled || !S.valid || !S.d || S.token != ctx->dynamics_token || S.lo != lo || S.hi != hi)
-        return SL_OK;
+        return SL_DECLINED;
     const SlDevModel& M = ctx->h_model;
     const int variant = sl_dim_variant_of(M);
-    if (variant != S.d_state || M.m.policy.m != S.m) return SL_OK;
+    if (variant != S.d_state || M.m.policy.m != S.m) return SL_DECLINED;
     const SlSuccDev sc = sl_succ_view(ctx);
     const int64_t n = hi - lo;
     SlAux aux{ctx->d_tri, ctx->d_net};
     const int64_t nblk = (n + 255) / 256;
     const int blocks = (int)(nblk < 32 * (int64_t)ctx->num_cu ? nblk : 32 * (int64_t)ctx->num_cu);
-    const bool policy = n_actions == 0;
+    const bool policy = b.n_actions == 0;
     double* usel = nullptr;
     int8_t* asel = nullptr;
     int32_t* miss_list = nullptr;
     int64_t nmiss = 0;
     if (!policy) {
-        if (n_actions != S.n_actions ||
-            memcmp(h_actions, S.actions, sizeof(double) * (size_t)n_actions) != 0)
-            return SL_OK;
+        if (b.n_actions != S.n_actions ||
+            memcmp(b.h_actions, S.actions, sizeof(double) * (size_t)b.n_actions) != 0)
+            return SL_DECLINED;
     } else {
         // closed-form policies take values outside any finite set; a per-vertex table or an
         // interpolated table (the greedy policies of the loop) is matched against the cached actions
         const int pk = M.m.policy.kind;
-        if (pk != SL_POLICY_TRI && pk != SL_POLICY_TABLE) return SL_OK;
+        if (pk != SL_POLICY_TRI && pk != SL_POLICY_TABLE) return SL_DECLINED;
         // [n] policy values, [n] action indices, the miss counter, the miss list (n / 8 + 64 entries:
         // a policy that misses more often than that is not the loop's greedy table)
         const int64_t cap = n / 8 + 64;
@@ -433,17 +434,10 @@ int sl_succ_sweep(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actions, const doub
         const size_t off_count = off_asel + (((size_t)n + 15) & ~(size_t)15);
         const size_t off_list = off_count + 16;
         const size_t need = off_list + sizeof(int32_t) * (size_t)cap;
-        if (need > S.select_bytes) {
-            if (S.d_select) (void)hipFree(S.d_select);
-            S.d_select = nullptr;
-            S.select_bytes = 0;
-            S.select_valid = false;
-            if (hipMalloc(&S.d_select, need) != hipSuccess) {
-                (void)hipGetLastError();
-                S.d_select = nullptr;
-                return SL_OK;
-            }
-            S.select_bytes = need;
+        if (need > S.select_bytes) S.select_valid = false;           // (a new buffer holds nothing)
+        if (sl_grow(ctx, &S.d_select, &S.select_bytes, need) != hipSuccess) {
+            (void)hipGetLastError();                                  // out of memory: no cache
+            return SL_DECLINED;
         }
         char* base = reinterpret_cast<char*>(S.d_select);
         usel = reinterpret_cast<double*>(base);
@@ -472,13 +466,13 @@ int sl_succ_sweep(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actions, const doub
             S.select_lo = lo;
             S.select_hi = hi;
         }
-        if (!S.select_usable) return SL_OK;
+        if (!S.select_usable) return SL_DECLINED;
         nmiss = S.select_misses;
     }
 #define SL_CACHED(D_, P_)                                                                          \
     hipLaunchKernelGGL((k_bellman_cached<D_, P_>), dim3(blocks), dim3(256), 0, ctx->stream,        \
-                       ctx->h_model, aux, sc, lo, hi, S.n_actions, usel, asel, d_v_new, d_argmax,  \
-                       d_q, d_stats)
+                       ctx->h_model, aux, sc, lo, hi, S.n_actions, usel, asel, b.v_new, b.argmax,  \
+                       b.q, b.stats)
 #define SL_CACHED_D(P_)                                                                            \
     do {                                                                                           \
         if (variant == 4) SL_CACHED(4, P_); else if (variant == 3) SL_CACHED(3, P_);               \
@@ -493,7 +487,7 @@ int sl_succ_sweep(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actions, const doub
         const int mblocks = (int)(mblk < 8 * (int64_t)ctx->num_cu ? mblk : 8 * (int64_t)ctx->num_cu);
 #define SL_MISS(D_)                                                                                \
     hipLaunchKernelGGL(k_succ_policy_miss<D_>, dim3(mblocks), dim3(256), 0, ctx->stream,           \
-                       ctx->h_model, ctx->h_gp, aux, sc, lo, nmiss, miss_list, usel, d_v_new, d_stats)
+                       ctx->h_model, ctx->h_gp, aux, sc, lo, nmiss, miss_list, usel, b.v_new, b.stats)
         if (variant == 4) SL_MISS(4); else if (variant == 3) SL_MISS(3);
         else if (variant == 2) SL_MISS(2); else SL_MISS(1);
 #undef SL_MISS
@@ -506,7 +500,6 @@ int sl_succ_sweep(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actions, const doub
     else
         sl_note_kernel(ctx, false, "k_bellman_cached<d=%d, %s> (successor cache, %d actions)", variant,
                        policy ? "policy" : "max", S.n_actions);
-    *done = 1;
     return SL_OK;
 }
 

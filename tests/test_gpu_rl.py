@@ -329,10 +329,9 @@ def test_bellman_sweep_4x4x4_kernel(sl, name, kw, nv, na, monkeypatch):
     actions = np.linspace(-1, 1, na)[:, None]
     results = {}
     # "1": k_bellman4s (B operand shared by the workgroup) + k_bellman_lookup (shipped); "split":
-    # k_bellman4 + k_bellman_lookup; "fused": k_bellman4 with its own epilogue; "0": the 16x16x4 kernel
-    for flag in ("1", "split", "fused", "0"):
+    # k_bellman4 + k_bellman_lookup; "0": the 16x16x4 kernel
+    for flag in ("1", "split", "0"):
         monkeypatch.setenv("SL_BELLMAN4", "0" if flag == "0" else "1")
-        monkeypatch.setenv("SL_BELLMAN4_SPLIT", "0" if flag == "fused" else "1")
         monkeypatch.setenv("SL_BELLMAN4_SHARED", "1" if flag == "1" else "0")
         rl, orl, vf, ovf = _rl_pair(sl, case, nv)
         q = rl.discrete_policy_optimization(actions, return_values=True)
@@ -352,8 +351,6 @@ def test_bellman_sweep_4x4x4_kernel(sl, name, kw, nv, na, monkeypatch):
     assert_allclose(q4, q16, rtol=1e-11, atol=1e-13)
     # the shared-B kernel multiplies (Bt P_j) T_last instead of Bt (P_j T_last): last-bit differences
     assert_allclose(results["split"][0], q4, rtol=1e-12, atol=1e-14)
-    assert_array_equal(results["fused"][0], results["split"][0])    # same GEMM, same per-pair arithmetic
-    assert_array_equal(results["fused"][1], results["split"][1])
     top2 = np.sort(oq, axis=1)[:, -2:]
     tie = np.abs(top2[:, 1] - top2[:, 0]) <= 1e-9 * np.abs(top2[:, 1])
     assert not np.any((best4 != actions[obest, 0]) & ok & ~tie)
