@@ -472,6 +472,36 @@ SL_API int  sl_bits_to_indices(sl_ctx* ctx, int64_t n, const uint64_t* d_bits, c
 SL_API int  sl_bellman_sweep(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actions, const double* h_actions,
                       double* d_v_new, int32_t* d_argmax, double* d_q, double* d_stats);
 
+/* ---- exact policy evaluation: V = r + gamma P V ------------------------------------------ *
+ * sl_policy_operator: the rows of vertices [lo,hi) of the value grid for the current policy -
+ * successor = dynamics mean at (x_i, policy(x_i)) located in the value triangulation exactly as
+ * sl_bellman_sweep(n_actions = 0) locates it.  Column-major ELL, K = d + 1 entries per row:
+ *   d_cols [K][hi-lo] vertex indices, d_w [K][hi-lo] weights (negated for a value spec with
+ *   `negate`), d_r [hi-lo] rewards, d_stats[2] = {rows with a negative barycentric weight,
+ *   kappa = gamma * max_i sum_k |w_ik|}.  Grids of 1 to 4 dimensions, at most 2^31 - 1 vertices.
+ * sl_value_solve: solves (I - gamma P) v = r for any ELL operator of n rows, k <= 16 entries
+ *   (cols in [0, n)), d_v = start on entry, on return the iterate whose residual is reported.
+ *   Stops when ||r + gamma P v - v||_inf <= tol * ||r||_inf (r = 0: v = 0), when an iterate is not
+ *   finite (residual_inf = +inf: diverging, kappa > 1) or when the next step would exceed
+ *   max_matvecs operator applications, residuals included (converged = 0; not an error).  method SL_SOLVE_GMRES: restarted GMRES(restart),
+ *   a cycle whose true residual is above kappa^steps times the cycle's start is followed by
+ *   `restart` Jacobi steps from the better iterate (kappa < 1 only); SL_SOLVE_JACOBI: the
+ *   fixed-point iteration v <- r + gamma P v alone.  bound = residual_inf / (1 - kappa) bounds
+ *   ||v - v*||_inf when kappa < 1 (+inf otherwise).  Deterministic: no atomics. */
+enum sl_solve_method { SL_SOLVE_GMRES = 0, SL_SOLVE_JACOBI = 1 };
+typedef struct sl_value_solve_stats {
+    int64_t iterations;           /* Arnoldi steps + Jacobi steps                                  */
+    int64_t matvecs;              /* operator applications, residuals included                     */
+    int64_t cycles, jacobi_cycles;   /* restart cycles / of them safeguard Jacobi cycles (gmres)   */
+    double residual_inf, bound, kappa;
+    int32_t converged, reserved;
+} sl_value_solve_stats;
+SL_API int  sl_policy_operator(sl_ctx* ctx, int64_t lo, int64_t hi, int32_t* d_cols, double* d_w,
+                               double* d_r, double* d_stats);
+SL_API int  sl_value_solve(sl_ctx* ctx, int64_t n, int k, const int32_t* d_cols, const double* d_w,
+                           const double* d_r, double gamma, double* d_v, double tol, int64_t max_matvecs,
+                           int restart, int method, sl_value_solve_stats* out);
+
 /* Successor cache of sl_bellman_sweep.  The next state of (vertex, action) - and where it falls in the
  * value grid: rectangle, unit-cell simplex, barycentric weights - does not depend on the value table
  * (reinforcement_learning.py:89-104; the table enters at :101 only), and a value-iteration loop

@@ -103,6 +103,16 @@ class SuccessorCacheStats(C.Structure):
                 ("hits", C.c_int64), ("policy_hits", C.c_int64)]
 
 
+class ValueSolveStats(C.Structure):
+    """``sl_value_solve_stats`` (include/sl_hip.h)."""
+    _fields_ = [("iterations", C.c_int64), ("matvecs", C.c_int64), ("cycles", C.c_int64),
+                ("jacobi_cycles", C.c_int64), ("residual_inf", C.c_double), ("bound", C.c_double),
+                ("kappa", C.c_double), ("converged", C.c_int32), ("reserved", C.c_int32)]
+
+
+SOLVE_GMRES, SOLVE_JACOBI = 0, 1
+
+
 # sl_sweep_result as int64 words (a torch int64[8] tensor backs it on the device)
 RESULT_WORDS = 8
 R_FAIL_V, R_FAIL_I, R_LAST_V, R_LAST_I, R_MAX_V, R_MAX_I, R_BELOW, R_SAFE = range(8)
@@ -123,7 +133,8 @@ EXPORTS = [
     "sl_adaptive_sort_keys", "sl_adaptive_analyse", "sl_adaptive_apply", "sl_adaptive_scatter",
     "sl_index_to_state", "sl_perturb_pairs", "sl_rows_sort_key", "sl_rows_duplicate_flags",
     "sl_sample_bounds", "sl_state_membership", "sl_argmax_masked", "sl_argmax_rows_masked", "sl_lyapunov_region",
-    "sl_bits_to_bytes", "sl_bytes_to_bits", "sl_bits_count", "sl_bits_to_indices", "sl_bellman_sweep", "sl_successor_cache_configure",
+    "sl_bits_to_bytes", "sl_bytes_to_bits", "sl_bits_count", "sl_bits_to_indices", "sl_bellman_sweep",
+    "sl_policy_operator", "sl_value_solve", "sl_successor_cache_configure",
     "sl_successor_cache_info", "sl_eval_points", "sl_timing_configure", "sl_timing_collect",
     "sl_comm_unique_id", "sl_comm_init", "sl_comm_destroy", "sl_allreduce_result", "sl_allgather",
     "sl_allreduce_sum_u64", "sl_allreduce_max_f64",
@@ -216,6 +227,12 @@ def load_library():
     lib.sl_bytes_to_bits.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.sl_bellman_sweep.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, c_double_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if not dev_early or hasattr(lib, "sl_value_solve"):
+        lib.sl_policy_operator.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]
+        lib.sl_value_solve.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_double, C.c_void_p, C.c_double, C.c_int64, C.c_int, C.c_int,
+                                       C.POINTER(ValueSolveStats)]
     # (a development library of another revision, SL_LIB_PATH, may lack the newest entry points: A/B
     # runs of the kernels both have; the shipped library is checked symbol by symbol, tests/test_abi.py)
     dev = bool(os.environ.get("SL_LIB_PATH"))
@@ -568,6 +585,21 @@ class Context(object):
         self.check(self.lib.sl_bellman_sweep(self.handle, lo, hi, n_act, pa, _ptr(d_v_new),
                                              _ptr(d_argmax), _ptr(d_q), _ptr(d_stats)),
                    "sl_bellman_sweep")
+
+    def policy_operator(self, lo, hi, d_cols, d_w, d_r, d_stats):
+        """``sl_policy_operator``: ELL rows ``[d + 1][hi - lo]`` of the current policy's operator."""
+        self.check(self.lib.sl_policy_operator(self.handle, lo, hi, _ptr(d_cols), _ptr(d_w), _ptr(d_r),
+                                               _ptr(d_stats)), "sl_policy_operator")
+
+    def value_solve(self, n, k, d_cols, d_w, d_r, gamma, d_v, tol, max_matvecs, restart, method):
+        """``sl_value_solve``: solves ``(I - gamma P) v = r`` in place of ``d_v``; the stats as a dict."""
+        stats = ValueSolveStats()
+        self.check(self.lib.sl_value_solve(self.handle, int(n), int(k), _ptr(d_cols), _ptr(d_w), _ptr(d_r),
+                                           float(gamma), _ptr(d_v), float(tol), int(max_matvecs),
+                                           int(restart), int(method), C.byref(stats)), "sl_value_solve")
+        out = {name: getattr(stats, name) for name, _ in ValueSolveStats._fields_ if name != "reserved"}
+        out["converged"] = bool(out["converged"])
+        return out
 
     def successor_cache_configure(self, max_bytes):
         """Budget of the Bellman sweeps' successor cache (``sl_successor_cache_configure``):
