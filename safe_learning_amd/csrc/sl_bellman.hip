@@ -665,14 +665,6 @@ __global__ __launch_bounds__(64 * SL_BM_WAVES) void k_bellman_policy_mfma(
     sl_residual_reduce<64 * SL_BM_WAVES, true>(lmax, lsum, stats, wave);
 }
 
-// heads with a sum-of-products kernel: the matrix-core sweeps generate RBF values (state and action
-// factors); such models take k_bellman's one-(x, u)-at-a-time path
-static bool has_other_kernels(const sl_ctx* ctx) {
-    for (int h = 0; h < ctx->h_gp.nheads; ++h)
-        if (ctx->gp_heads[h].d_kernel) return true;
-    return false;
-}
-
 // The 16x16x4 kernels: one GP head whose outputs span the state, at most 96 (action, output)
 // columns, or a FunctionStack of 2 (d = 2) / 4 (d = 4) single-output heads.
 static int bellman_mfma(sl_ctx* ctx, const SlBellmanArgs& b) {
@@ -786,7 +778,7 @@ static int bellman_valu(sl_ctx* ctx, const SlBellmanArgs& b) {
     const SlDevModel& M = ctx->h_model;
     const int64_t lo = b.lo, hi = b.hi;
     const int n_actions = b.n_actions;
-    const bool factorised = M.m.dynamics.kind == SL_DYN_GP && !has_other_kernels(ctx);
+    const bool factorised = M.m.dynamics.kind == SL_DYN_GP && !sl_has_other_kernels(ctx);
     const int amax = n_actions == 0 ? 0 : (n_actions <= 3 ? 3 : (n_actions <= 9 ? 9 : SL_MAX_ACTIONS));
     size_t lds = 0;                               // the action-factor table
     if (n_actions > 0 && factorised)
@@ -839,7 +831,6 @@ extern "C" int sl_bellman_sweep(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actio
                                 const double* h_actions, double* d_v_new, int32_t* d_argmax,
                                 double* d_q, double* d_stats) {
     if (!ctx) return sl_fail(nullptr, SL_ERR_INVALID, "sl_bellman_sweep: NULL context");
-    SlTimed timed(ctx, 2);
     if (!ctx->model_set) return sl_fail(ctx, SL_ERR_INVALID, "sl_bellman_sweep: call sl_model_set first");
     if (!ctx->h_tri[0].set)
         return sl_fail(ctx, SL_ERR_INVALID, "sl_bellman_sweep: value table (sl_tri_set slot 0) not set");
@@ -865,6 +856,7 @@ extern "C" int sl_bellman_sweep(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actio
     const bool is_gp = M.m.dynamics.kind == SL_DYN_GP;
     if (is_gp && ctx->h_gp.nheads < 1)
         return sl_fail(ctx, SL_ERR_INVALID, "sl_bellman_sweep: GP dynamics without heads");
+    SlTimed timed(ctx, 2);
     SL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     SL_HIP_CHECK(ctx, hipMemsetAsync(d_stats, 0, 2 * sizeof(double), ctx->stream));
     ctx->last_kernel[0] = 0;
@@ -891,7 +883,7 @@ extern "C" int sl_bellman_sweep(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actio
     // policies only.  SL_BELLMAN_MFMA=0 keeps every sweep on k_bellman.
     const int variant = sl_dim_variant_of(M), pkind = M.m.policy.kind;
     const bool matrix_cores =
-        is_gp && !has_other_kernels(ctx) && ctx->env.bellman_mfma != 0 && M.m.policy.m == 1 &&
+        is_gp && !sl_has_other_kernels(ctx) && ctx->env.bellman_mfma != 0 && M.m.policy.m == 1 &&
         ctx->h_gp.nheads <= SL_BM_HEADS && (variant == 4 || variant == 2) &&
         (n_actions > 0 || pkind == SL_POLICY_TRI || pkind == SL_POLICY_TABLE || pkind == SL_POLICY_CONST);
     rc = SL_DECLINED;
@@ -932,10 +924,6 @@ __global__ __launch_bounds__(SL_BLOCK) void k_eval_simple(const SlDevModel M, Sl
         }
     }
 }
-
-int sl_sweep_any(sl_ctx* ctx, int64_t lo, int64_t hi, const uint64_t* d_init_bits,
-                 const double* d_values, uint64_t* d_neg_bits, sl_sweep_result* d_result,
-                 double* d_dbg, const double* d_points);
 
 // rows 0 .. n-1 of a per-point action table through the policy's saturation
 __global__ __launch_bounds__(SL_BLOCK) void k_policy_rows(const SlDevModel M, int64_t n, double* __restrict__ out) {
@@ -992,5 +980,5 @@ extern "C" int sl_eval_points(sl_ctx* ctx, int what, int64_t n, const double* d_
     SL_HIP_CHECK(ctx, sl_grow(ctx, &ctx->d_scratch, &ctx->scratch_bytes, need));
     sl_sweep_result* res = reinterpret_cast<sl_sweep_result*>(ctx->d_scratch);
     uint64_t* bits = reinterpret_cast<uint64_t*>(res + 1);
-    return sl_sweep_any(ctx, 0, n, nullptr, nullptr, bits, res, d_out, d_points);
+    return sl_sweep_any(ctx, {0, n, nullptr, nullptr, bits, d_out, d_points}, res, false);
 }

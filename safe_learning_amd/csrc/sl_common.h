@@ -31,14 +31,12 @@ struct SlGpHeadHost {
 // Environment switches (A/B runs and the tests of the alternative kernels; none is needed in
 // production).  Read ONCE, by sl_ctx_create - a launch never calls getenv.  -1 = not set.
 struct SlEnv {
-    int gp_cfg = -1;                 // SL_GP_CFG=0..3: force a GP-sweep configuration
+    int gp_cfg = -1;                 // SL_GP_CFG=0/2/3: force a GP-sweep configuration
     int gp_small = -1;               // SL_GP_SMALL=0: small training sets stay on k_gp_sweep
     int gp_small_waves = -1;         // SL_GP_SMALL_WAVES=8
-    int gp_small_split = -1;         // SL_GP_SMALL_SPLIT
     int det_rows = -1;               // SL_DET_ROWS=0: linear dynamics on k_det_sweep
     int gp4_one_panel = -1;          // SL_GP4_ONE_PANEL=0: 193..256 points stay on k_gp_small
     int gp4_seeds = -1;              // SL_GP4_SEEDS=0: every k_x chunk from the exponentials
-    int gp4_tickets = -1;            // SL_GP4_TICKETS=0/1: fixed tile list / tile counter
     int bellman_mfma = -1;           // SL_BELLMAN_MFMA=0: Bellman sweeps on the FP64-VALU kernel
     int bellman4 = -1, bellman4_policy = -1, bellman4_ragged = -1;
     int bellman4_shared = -1;        // SL_BELLMAN4*: see DESIGN.md "Environment switches"
@@ -159,6 +157,14 @@ struct sl_ctx {
     } succ;
 };
 
+// a GP head has a sum-of-products kernel (sl_gp_set_head_kernel): the kernels that generate RBF values
+// (k_gp_sweep4, the matrix-core Bellman sweeps) do not take the model
+static inline bool sl_has_other_kernels(const sl_ctx* ctx) {
+    for (int h = 0; h < ctx->h_gp.nheads; ++h)
+        if (ctx->gp_heads[h].d_kernel) return true;
+    return false;
+}
+
 // device view of the successor cache of n = hi - lo vertices (slot a < A: action a, slot A: the
 // vertex itself - the interpolated V(x_i) of the Bellman error)
 struct SlSuccDev {
@@ -190,6 +196,22 @@ struct SlBellmanArgs {
 };
 #define SL_DECLINED 1          // internal only: the public codes are 0 and negative
 int sl_succ_sweep(sl_ctx* ctx, const SlBellmanArgs& b);
+
+// The arguments of one decrease-check sweep (sl_lyap_sweep over grid cells, sl_eval_points over
+// explicit points), handed to each launcher of sl_sweep_any in turn: network V, the GP three-pass
+// table path, the fused GP sweep (sl_gp_sweep_launch), k_det_rows and k_det_sweep.  A launcher
+// returns SL_DECLINED to leave the sweep to the next one, otherwise SL_OK or an error, and sets
+// *nblocks to the number of partial keys it wrote to ctx->d_partials.
+struct SlSweepArgs {
+    int64_t lo, hi;
+    const uint64_t* init_bits;   // [words] initial safe set, or null
+    const double* values;        // [hi - lo] ordering keys, or null: V of the cell
+    uint64_t* neg_bits;          // [words] out: the decrease mask
+    double* dbg;                 // [hi - lo][2 + 2d] out: per-cell records, or null
+    const double* points;        // [hi - lo][d] explicit points, or null: the grid cells
+};
+// timed: bracket the launches with the events of timing channel 0 (sl_lyap_sweep)
+int sl_sweep_any(sl_ctx* ctx, const SlSweepArgs& a, sl_sweep_result* d_result, bool timed);
 
 // Brackets an entry point's launches with a pair of events when sl_timing_configure asked for it
 // (bench.py's kernel durations: recorded by the library on its own stream, no host objects per call)
@@ -229,20 +251,12 @@ int sl_fail(sl_ctx* ctx, int code, const char* fmt, ...);
 void sl_note_kernel(sl_ctx* ctx, bool append, const char* fmt, ...);
 
 // launchers defined in the other translation units
-int sl_gp_sweep_launch(sl_ctx* ctx, const SlDevModel& model, int64_t lo, int64_t hi,
-                       const uint64_t* d_init_bits, const double* d_values, uint64_t* d_neg_bits,
-                       int* nblocks, double* d_dbg, const double* d_points);
-int sl_gp4_sweep_launch(sl_ctx* ctx, const SlDevModel& model, int64_t lo, int64_t hi,
-                        const uint64_t* d_init_bits, const double* d_values, uint64_t* d_neg_bits,
-                        int* nblocks, double* d_dbg, const double* d_points);
+int sl_gp_sweep_launch(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, int* nblocks);
+int sl_gp4_sweep_launch(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, int* nblocks);
 bool sl_gp4_supports(const SlDevModel& model);
-bool sl_det_rows_supports(const SlDevModel& model, int64_t lo, int64_t hi);
-int sl_det_rows_launch(sl_ctx* ctx, int64_t lo, int64_t hi, const uint64_t* d_init_bits,
-                       const double* d_values, uint64_t* d_neg_bits, int* nblocks);
+int sl_det_rows_launch(sl_ctx* ctx, const SlSweepArgs& a, int* nblocks);
 bool sl_gp_small_supports(sl_ctx* ctx, const SlDevModel& model);
-int sl_gp_small_launch(sl_ctx* ctx, const SlDevModel& model, int64_t lo, int64_t hi,
-                       const uint64_t* d_init_bits, const double* d_values, uint64_t* d_neg_bits,
-                       int* nblocks, double* d_dbg, const double* d_points);
+int sl_gp_small_launch(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, int* nblocks);
 int sl_bellman4_launch(sl_ctx* ctx, const SlBellmanArgs& b);
 int sl_bellman4_policy_launch(sl_ctx* ctx, const SlBellmanArgs& b);
 int sl_nn_values_launch(sl_ctx* ctx, int64_t lo, int64_t hi, double* d_values);

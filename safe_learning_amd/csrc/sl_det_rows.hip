@@ -191,7 +191,7 @@ __global__ __launch_bounds__(SL_BLOCK) void k_det_rows(
 // Models and ranges the row kernel takes: closed-form linear policy (one action), linear dynamics,
 // quadratic V, L_v a scalar or |x G^T| (per column or as one norm), scalar L_f, 1..4 state
 // dimensions, a last axis of whole bytes (multiple of 8 cells), a range of whole mask words.
-bool sl_det_rows_supports(const SlDevModel& M, int64_t lo, int64_t hi) {
+static bool supports(const SlDevModel& M, int64_t lo, int64_t hi) {
     const int d = M.m.grid.d;
     if (d < 1 || d > 4 || M.m.policy.m != 1) return false;
     if (M.m.policy.kind != SL_POLICY_LINEAR || M.m.dynamics.kind != SL_DYN_LINEAR) return false;
@@ -203,10 +203,12 @@ bool sl_det_rows_supports(const SlDevModel& M, int64_t lo, int64_t hi) {
     return (lo % 64) == 0 && hi > lo && ((hi - lo) % detrows::CPT) == 0;
 }
 
-int sl_det_rows_launch(sl_ctx* ctx, int64_t lo, int64_t hi, const uint64_t* d_init_bits,
-                       const double* d_values, uint64_t* d_neg_bits, int* nblocks) {
+// grid cells only, no records; SL_DET_ROWS=0 leaves every sweep to k_det_sweep
+int sl_det_rows_launch(sl_ctx* ctx, const SlSweepArgs& a, int* nblocks) {
     using namespace detrows;
     const SlDevModel& M = ctx->h_model;
+    const int64_t lo = a.lo, hi = a.hi;
+    if (a.dbg || a.points || ctx->env.det_rows == 0 || !supports(M, lo, hi)) return SL_DECLINED;
     const int64_t span = (int64_t)SL_BLOCK * CPT;
     int64_t blocks = (hi - lo + span - 1) / span;
     const int64_t cap = (int64_t)ctx->num_cu * 8;
@@ -216,12 +218,12 @@ int sl_det_rows_launch(sl_ctx* ctx, int64_t lo, int64_t hi, const uint64_t* d_in
     // the last mask word of a range that is not a multiple of 64 cells: whole bytes are written
     // up to the range's end, the remaining bytes of that word are cleared first
     if ((hi - lo) & 63)
-        SL_HIP_CHECK(ctx, hipMemsetAsync(d_neg_bits + ((hi - lo) >> 6), 0, sizeof(uint64_t), ctx->stream));
-    const uint8_t* init_bytes = reinterpret_cast<const uint8_t*>(d_init_bits);
-    uint8_t* neg_bytes = reinterpret_cast<uint8_t*>(d_neg_bits);
+        SL_HIP_CHECK(ctx, hipMemsetAsync(a.neg_bits + ((hi - lo) >> 6), 0, sizeof(uint64_t), ctx->stream));
+    const uint8_t* init_bytes = reinterpret_cast<const uint8_t*>(a.init_bits);
+    uint8_t* neg_bytes = reinterpret_cast<uint8_t*>(a.neg_bits);
 #define SL_ROWS(D_)                                                                                \
     hipLaunchKernelGGL(k_det_rows<D_>, dim3((unsigned)blocks), dim3(SL_BLOCK), 0, ctx->stream, M,  \
-                       lo, hi, init_bytes, d_values, neg_bytes, ctx->d_partials)
+                       lo, hi, init_bytes, a.values, neg_bytes, ctx->d_partials)
     switch (M.m.grid.d) {
         case 1: SL_ROWS(1); break;
         case 2: SL_ROWS(2); break;

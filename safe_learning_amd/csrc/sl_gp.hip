@@ -34,17 +34,17 @@ typedef double sl_d2 __attribute__((ext_vector_type(2)));
 #endif
 #define SL_GP_DOUT_MAX SL_MAX_STATE_DIM
 
-// configurations: {W wavefronts, R row blocks per wavefront, CB cell blocks}
-//   cfg 0: small n (tests)   W=4 R=1 CB=1   panel   64 rows, 16 cells
-//   cfg 1:                    W=8 R=8 CB=2   panel 1024 rows, 32 cells
-//   cfg 2:                    W=8 R=4 CB=4   panel  512 rows, 64 cells; fast-path models run
+// configurations, chosen per head at upload: {W wavefronts, R row blocks per wavefront, CB cell blocks}
+// of k_gp_sweep's panels, [0] for cfg 0, [1] for cfg 2 and 3
+//   cfg 0: <= 256 points      W=4 R=1 CB=1   panel   64 rows, 16 cells; k_gp_small where it applies
+//   cfg 2: more               W=8 R=4 CB=4   panel  512 rows, 64 cells; fast-path models run
 //                             k_gp_sweep4 instead (sl_gp4.hip: 4x4x4 MFMAs, W=4 R=8 CB=4)
 //   cfg 3:                    as cfg 2, always on this file's kernel (SL_GP_CFG=3: comparisons)
-static const int kCfgW[4] = {4, 8, 8, 8};
-static const int kCfgR[4] = {1, 8, 4, 4};
-static const int kCfgCB[4] = {1, 2, 4, 4};
+static constexpr int kCfgW[2] = {4, 8};
+static constexpr int kCfgR[2] = {1, 4};
+static constexpr int kCfgCB[2] = {1, 4};
 
-static inline int cfg_panel_rows(int cfg) { return 16 * kCfgR[cfg] * kCfgW[cfg]; }
+static inline int cfg_panel_rows(int cfg) { return 16 * kCfgR[cfg != 0] * kCfgW[cfg != 0]; }
 
 // XSG: the scaled training inputs do not fit LDS next to the k_x buffers and are read from L2
 // during generation (instantiated for the 64-cell-tile configuration only).
@@ -590,10 +590,19 @@ extern "C" int sl_gp_configure(sl_ctx* ctx, int nheads, double beta) {
     return SL_OK;
 }
 
+// one GP sweep: the model its kernel sees (the full one, or the posterior-only model of a split
+// sweep) and the sweep's arguments
+struct GpSweep {
+    const SlDevModel& model;
+    const SlSweepArgs& a;
+    int* nblocks;
+};
+
 template <int W, int R, int CB, bool GENERAL, int DT, int MT, bool XSG = false>
-static int launch_cfg(sl_ctx* ctx, const SlDevModel& model, int64_t lo, int64_t hi,
-                      const uint64_t* d_init_bits, const double* d_values, uint64_t* d_neg_bits, int* nblocks, double* d_dbg,
-                      const double* d_points) {
+static int launch_cfg(sl_ctx* ctx, const GpSweep& g) {
+    const SlDevModel& model = g.model;
+    const SlSweepArgs& a = g.a;
+    const int64_t lo = a.lo, hi = a.hi;
     constexpr int C = 16 * CB;
     const int64_t nwords = (hi - lo + 63) / 64;
     const int64_t ntiles = nwords * (64 / C);
@@ -636,20 +645,88 @@ static int launch_cfg(sl_ctx* ctx, const SlDevModel& model, int64_t lo, int64_t 
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int64_t blocks = ntiles < ctx->num_cu ? ntiles : ctx->num_cu;
     if (blocks > SL_MAX_GRID) blocks = SL_MAX_GRID;
-    *nblocks = (int)blocks;
+    *g.nblocks = (int)blocks;
     SlAux aux{ctx->d_tri, ctx->d_net};
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(W * 64), lds, ctx->stream, model,
-                       ctx->h_gp, aux, lo, hi, ntiles, d_init_bits, d_values, d_neg_bits, ctx->d_partials, d_dbg,
-                       xs_doubles, alpha_doubles, d_points, nb);
+                       ctx->h_gp, aux, lo, hi, ntiles, a.init_bits, a.values, a.neg_bits, ctx->d_partials, a.dbg,
+                       xs_doubles, alpha_doubles, a.points, nb);
     SL_HIP_CHECK(ctx, hipGetLastError());
     sl_note_kernel(ctx, false, "k_gp_sweep<W=%d, R=%d, CB=%d, general=%d, d=%d, m=%d, xs_global=%d>", W, R,
                    CB, (int)GENERAL, DT, MT, (int)XSG);
     return SL_OK;
 }
 
-int sl_gp_sweep_launch(sl_ctx* ctx, const SlDevModel& model, int64_t lo, int64_t hi,
-                       const uint64_t* d_init_bits, const double* d_values, uint64_t* d_neg_bits, int* nblocks, double* d_dbg,
-                       const double* d_points) {
+// sum-of-products heads: k_gp_small and k_gp_sweep evaluate them, k_gp_sweep4 generates RBF values
+// by recurrence
+static int gp_small_other_kernels(sl_ctx* ctx, const GpSweep& g) {
+    if (!sl_has_other_kernels(ctx) || !sl_gp_small_supports(ctx, g.model)) return SL_DECLINED;
+    return sl_gp_small_launch(ctx, g.model, g.a, g.nblocks);
+}
+
+// 225 .. 256 training points per head (capacity exactly one 256-row panel of k_gp_sweep4): the
+// factor no longer fits LDS, k_gp_small waits for its fragments from L2 (1.9 ms at 256 points on
+// 1024^2 cells, 0.6 ms at 128) while k_gp_sweep4 prefetches them two slab pairs ahead - fast-path
+// models with RBF heads take it on ONE panel (SL_GP4_ONE_PANEL=0: keep k_gp_small).  k_gp_small
+// pays for the row blocks that hold training points, the panel for its 256 rows: at 224 points
+// the two meet, below k_gp_small wins (round 6, sixteen wavefronts and the short pass first:
+// 1024^2 cells 1.39 / 1.54 / 1.71 / 1.91 ms at 200 / 224 / 240 / 256 points against 1.50 - 1.52 on the
+// panel; 48^4: 6.90 / 7.78 / 9.66 against 7.95 - profiles/r06_one_panel_ab.txt; round 5 had the
+// crossing at 200, profiles/r05_one_panel_ab.txt).
+static int gp4_one_panel(sl_ctx* ctx, const GpSweep& g) {
+    if (ctx->gp_cfg != 0 || sl_has_other_kernels(ctx) || !sl_gp4_supports(g.model) || ctx->env.gp4_one_panel == 0)
+        return SL_DECLINED;
+    for (int h = 0; h < ctx->h_gp.nheads; ++h)
+        if (ctx->gp_heads[h].n_pad != 256 || ctx->gp_heads[h].n <= 224) return SL_DECLINED;
+    return sl_gp4_sweep_launch(ctx, g.model, g.a, g.nblocks);
+}
+
+// small training sets (capacity <= 256 points per head): a wavefront per 64-cell tile
+static int gp_small_cfg0(sl_ctx* ctx, const GpSweep& g) {
+    if (ctx->gp_cfg != 0 || !sl_gp_small_supports(ctx, g.model)) return SL_DECLINED;
+    return sl_gp_small_launch(ctx, g.model, g.a, g.nblocks);
+}
+
+static int gp4_cfg2(sl_ctx* ctx, const GpSweep& g) {
+    if (ctx->gp_cfg != 2 || sl_has_other_kernels(ctx) || !sl_gp4_supports(g.model)) return SL_DECLINED;
+    return sl_gp4_sweep_launch(ctx, g.model, g.a, g.nblocks);
+}
+
+// training inputs too large to sit in LDS beside the k_x buffers: 64-cell-tile configuration
+// with the inputs read from L2 (fast-path models with 2 or 4 state dimensions)
+static int gp_sweep_xs_global(sl_ctx* ctx, const GpSweep& g) {
+    if (ctx->gp_cfg == 0) return SL_DECLINED;
+    int xs_max = 0;
+    for (int h = 0; h < ctx->h_gp.nheads; ++h) {
+        const int v = g.model.in_dim * ctx->gp_heads[h].n_pad;
+        xs_max = v > xs_max ? v : xs_max;
+    }
+    const size_t fixed = sizeof(double) * (2 * SL_GP_SLABS_PER_CHUNK * 4 * 64 + 8 * 64 +
+                                           8 * 16 * SL_GP_DOUT_MAX + 2 * 64 * SL_D + 2 * 8);
+    if (fixed + sizeof(double) * xs_max <= 160 * 1024) return SL_DECLINED;
+    const bool general = sl_model_is_general(g.model);
+    const int variant = sl_dim_variant_of(g.model);
+    if (!general && variant == 4) return launch_cfg<8, 4, 4, false, 4, 1, true>(ctx, g);
+    if (!general && variant == 2) return launch_cfg<8, 4, 4, false, 2, 1, true>(ctx, g);
+    return launch_cfg<8, 4, 4, true, 0, 0, true>(ctx, g);
+}
+
+// k_gp_sweep on the configuration's panel shape: takes every model
+template <int S>
+static int gp_sweep_shape(sl_ctx* ctx, const GpSweep& g) {
+    constexpr int W = kCfgW[S], R = kCfgR[S], CB = kCfgCB[S];
+    const int variant = sl_dim_variant_of(g.model);
+    if (sl_model_is_general(g.model))
+        return variant == 2 ? launch_cfg<W, R, CB, true, 2, 1>(ctx, g) : launch_cfg<W, R, CB, true, 0, 0>(ctx, g);
+    switch (variant) {
+        case 1: return launch_cfg<W, R, CB, false, 1, 1>(ctx, g);
+        case 2: return launch_cfg<W, R, CB, false, 2, 1>(ctx, g);
+        case 3: return launch_cfg<W, R, CB, false, 3, 1>(ctx, g);
+        case 4: return launch_cfg<W, R, CB, false, 4, 1>(ctx, g);
+        default: return launch_cfg<W, R, CB, false, 0, 0>(ctx, g);
+    }
+}
+
+int sl_gp_sweep_launch(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, int* nblocks) {
     if (ctx->h_gp.nheads < 1)
         return sl_fail(ctx, SL_ERR_INVALID, "GP dynamics selected but sl_gp_configure not called");
     int covered = 0;
@@ -657,86 +734,12 @@ int sl_gp_sweep_launch(sl_ctx* ctx, const SlDevModel& model, int64_t lo, int64_t
     if (covered != model.m.grid.d)
         return sl_fail(ctx, SL_ERR_INVALID, "GP heads cover %d outputs, state dimension is %d",
                        covered, model.m.grid.d);
-    const bool general = sl_model_is_general(model);
-    const int variant = sl_dim_variant_of(model);
-    // heads with a sum-of-products kernel (sl_gp_set_head_kernel): k_gp_small evaluates those
-    bool other_kernels = false;
-    for (int h = 0; h < ctx->h_gp.nheads; ++h) other_kernels = other_kernels || ctx->gp_heads[h].d_kernel;
-    // (k_gp_small and k_gp_sweep evaluate them; k_gp_sweep4 generates RBF values by recurrence)
-    if (other_kernels && sl_gp_small_supports(ctx, model))
-        return sl_gp_small_launch(ctx, model, lo, hi, d_init_bits, d_values, d_neg_bits, nblocks,
-                                  d_dbg, d_points);
-    // 225 .. 256 training points per head (capacity exactly one 256-row panel of k_gp_sweep4): the
-    // factor no longer fits LDS, k_gp_small waits for its fragments from L2 (1.9 ms at 256 points on
-    // 1024^2 cells, 0.6 ms at 128) while k_gp_sweep4 prefetches them two slab pairs ahead - fast-path
-    // models with RBF heads take it on ONE panel (SL_GP4_ONE_PANEL=0: keep k_gp_small).  k_gp_small
-    // pays for the row blocks that hold training points, the panel for its 256 rows: at 224 points
-    // the two meet, below k_gp_small wins (round 6, sixteen wavefronts and the short pass first:
-    // 1024^2 cells 1.39 / 1.54 / 1.71 / 1.91 ms at 200 / 224 / 240 / 256 points against 1.50 - 1.52 on the
-    // panel; 48^4: 6.90 / 7.78 / 9.66 against 7.95 - profiles/r06_one_panel_ab.txt; round 5 had the
-    // crossing at 200, profiles/r05_one_panel_ab.txt).
-    if (ctx->gp_cfg == 0 && !other_kernels && sl_gp4_supports(model)) {
-        bool one_panel = true;
-        for (int h = 0; h < ctx->h_gp.nheads; ++h)
-            one_panel = one_panel && ctx->gp_heads[h].n_pad == 256 && ctx->gp_heads[h].n > 224;
-        if (ctx->env.gp4_one_panel == 0) one_panel = false;
-        if (one_panel)
-            return sl_gp4_sweep_launch(ctx, model, lo, hi, d_init_bits, d_values, d_neg_bits, nblocks,
-                                       d_dbg, d_points);
+    const GpSweep g{model, a, nblocks};
+    for (auto launch : {gp_small_other_kernels, gp4_one_panel, gp_small_cfg0, gp4_cfg2, gp_sweep_xs_global}) {
+        const int rc = launch(ctx, g);
+        if (rc != SL_DECLINED) return rc;
     }
-    // small training sets (one head, capacity <= 256 points): a wavefront per 64-cell tile
-    if (ctx->gp_cfg == 0 && sl_gp_small_supports(ctx, model))
-        return sl_gp_small_launch(ctx, model, lo, hi, d_init_bits, d_values, d_neg_bits, nblocks,
-                                  d_dbg, d_points);
-    if (ctx->gp_cfg == 2 && !other_kernels && sl_gp4_supports(model))
-        return sl_gp4_sweep_launch(ctx, model, lo, hi, d_init_bits, d_values, d_neg_bits, nblocks,
-                                   d_dbg, d_points);
-    // training inputs too large to sit in LDS beside the k_x buffers: 64-cell-tile configuration
-    // with the inputs read from L2 (fast-path models with 2 or 4 state dimensions)
-    {
-        int xs_max = 0;
-        for (int h = 0; h < ctx->h_gp.nheads; ++h) {
-            const int v = model.in_dim * ctx->gp_heads[h].n_pad;
-            xs_max = v > xs_max ? v : xs_max;
-        }
-        const size_t fixed = sizeof(double) * (2 * SL_GP_SLABS_PER_CHUNK * 4 * 64 + 8 * 64 +
-                                               8 * 16 * SL_GP_DOUT_MAX + 2 * 64 * SL_D + 2 * 8);
-        if (ctx->gp_cfg >= 2 && fixed + sizeof(double) * xs_max > 160 * 1024) {
-            if (!general && variant == 4)
-                return launch_cfg<8, 4, 4, false, 4, 1, true>(ctx, model, lo, hi, d_init_bits, d_values,
-                                                              d_neg_bits, nblocks, d_dbg, d_points);
-            if (!general && variant == 2)
-                return launch_cfg<8, 4, 4, false, 2, 1, true>(ctx, model, lo, hi, d_init_bits, d_values,
-                                                              d_neg_bits, nblocks, d_dbg, d_points);
-            return launch_cfg<8, 4, 4, true, 0, 0, true>(ctx, model, lo, hi, d_init_bits, d_values,
-                                                         d_neg_bits, nblocks, d_dbg, d_points);
-        }
-    }
-#define SL_GP_LAUNCH(W_, R_, CB_, G, D_, M_)                                                      \
-    return launch_cfg<W_, R_, CB_, G, D_, M_>(ctx, model, lo, hi, d_init_bits, d_values, d_neg_bits,     \
-                                              nblocks, d_dbg, d_points)
-#define SL_GP_CASE(id, W_, R_, CB_)                                                               \
-    case id:                                                                                      \
-        if (general) {                                                                            \
-            if (variant == 2) { SL_GP_LAUNCH(W_, R_, CB_, true, 2, 1); }                          \
-            SL_GP_LAUNCH(W_, R_, CB_, true, 0, 0);                                                \
-        }                                                                                         \
-        switch (variant) {                                                                        \
-            case 1: SL_GP_LAUNCH(W_, R_, CB_, false, 1, 1);                                       \
-            case 2: SL_GP_LAUNCH(W_, R_, CB_, false, 2, 1);                                       \
-            case 3: SL_GP_LAUNCH(W_, R_, CB_, false, 3, 1);                                       \
-            case 4: SL_GP_LAUNCH(W_, R_, CB_, false, 4, 1);                                       \
-            default: SL_GP_LAUNCH(W_, R_, CB_, false, 0, 0);                                      \
-        }
-    switch (ctx->gp_cfg) {
-        SL_GP_CASE(0, 4, 1, 1)
-        SL_GP_CASE(1, 8, 8, 2)
-        SL_GP_CASE(2, 8, 4, 4)
-        SL_GP_CASE(3, 8, 4, 4)
-    }
-#undef SL_GP_CASE
-#undef SL_GP_LAUNCH
-    return sl_fail(ctx, SL_ERR_INVALID, "bad GP kernel configuration %d", ctx->gp_cfg);
+    return ctx->gp_cfg == 0 ? gp_sweep_shape<0>(ctx, g) : gp_sweep_shape<1>(ctx, g);
 }
 
 // =============================================================================================

@@ -43,8 +43,7 @@
 // Compiled out: the build's audit of the fixed-accumulator code failed on this toolchain
 // (safe_learning_amd/_build.py); every GP sweep then runs k_gp_sweep (sl_gp.hip).
 bool sl_gp4_supports(const SlDevModel&) { return false; }
-int sl_gp4_sweep_launch(sl_ctx* ctx, const SlDevModel&, int64_t, int64_t, const uint64_t*, const double*,
-                        uint64_t*, int*, double*, const double*) {
+int sl_gp4_sweep_launch(sl_ctx* ctx, const SlDevModel&, const SlSweepArgs&, int*) {
     return sl_fail(ctx, SL_ERR_UNSUPPORTED, "k_gp_sweep4 is compiled out of this build");
 }
 #else
@@ -475,7 +474,7 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
     // Tiles are drawn from a counter: a tile whose cells cross a saturation kink of the policy
     // generates its k_x chunks at twice the cost (a fifth of the headline workload's tiles), and
     // with a fixed tile list per workgroup the unlucky workgroups finish last (measured: 2 % of
-    // the sweep, profiles/r04_gp4_tickets_ab.txt).
+    // the sweep, CHANGELOG.md round 4).
     // (Few tiles per workgroup - small grids, C2's 1024 tiles on 512 workgroups: the counter hands
     // one workgroup three tiles and another one, and the sweep lasts as long as the three; a fixed
     // round-robin list is the better balance there: ticket == nullptr.)
@@ -950,8 +949,7 @@ static int launch4(sl_ctx* ctx, const SlDevModel& model, int64_t lo, int64_t hi,
     // SL_GP4_SEEDS=0: every generation from scratch (same k_x bit for bit: the test of that)
     double* seeds = ctx->env.gp4_seeds == 0 ? nullptr : ctx->d_gp4_seeds + head_bytes / sizeof(double);
     unsigned long long* ticket = reinterpret_cast<unsigned long long*>(ctx->d_gp4_seeds);
-    // SL_GP4_TICKETS=0 / 1 force the list / the counter
-    const bool counter = ctx->env.gp4_tickets >= 0 ? ctx->env.gp4_tickets != 0 : ntiles >= 4 * blocks;
+    const bool counter = ntiles >= 4 * blocks;
     if (counter) SL_HIP_CHECK(ctx, hipMemsetAsync(ticket, 0, head_bytes, ctx->stream));
     else ticket = nullptr;
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(gp4::W * 64), lds, ctx->stream, model,
@@ -991,13 +989,11 @@ SL_GP4_DIM_ENTRY(3)
 SL_GP4_DIM_ENTRY(4)
 
 // Fast-path models (closed-form or per-vertex table policy, quadratic V) with panels of 512 rows.
-int sl_gp4_sweep_launch(sl_ctx* ctx, const SlDevModel& model, int64_t lo, int64_t hi,
-                        const uint64_t* d_init_bits, const double* d_values, uint64_t* d_neg_bits,
-                        int* nblocks, double* d_dbg, const double* d_points) {
+int sl_gp4_sweep_launch(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, int* nblocks) {
     const int variant = sl_dim_variant_of(model);
 #define SL_GP4(D_)                                                                                 \
-    return sl_gp4_launch_d##D_(ctx, model, lo, hi, d_init_bits, d_values, d_neg_bits, nblocks,     \
-                               d_dbg, d_points)
+    return sl_gp4_launch_d##D_(ctx, model, a.lo, a.hi, a.init_bits, a.values, a.neg_bits, nblocks, \
+                               a.dbg, a.points)
     switch (variant) {
         case 1: SL_GP4(1);
         case 2: SL_GP4(2);

@@ -439,8 +439,7 @@ static int launch_small(sl_ctx* ctx, const SlDevModel& model, int64_t lo, int64_
         ticket = ctx->d_ticket;
         SL_HIP_CHECK(ctx, hipMemsetAsync(ticket, 0, sizeof(unsigned long long), ctx->stream));
     }
-    bool other_kernels = false;
-    for (int k = 0; k < ctx->h_gp.nheads; ++k) other_kernels = other_kernels || ctx->gp_heads[k].d_kernel;
+    const bool other_kernels = sl_has_other_kernels(ctx);
 #define SL_GPS_GO(ALDS_, W_)                                                                       \
     do {                                                                                           \
         auto kern = other_kernels ? k_gp_small<GENERAL, DT, MT, ALDS_, W_, true>                   \
@@ -469,14 +468,12 @@ static int launch_small(sl_ctx* ctx, const SlDevModel& model, int64_t lo, int64_
     return SL_OK;
 }
 
-int sl_gp_small_launch(sl_ctx* ctx, const SlDevModel& model, int64_t lo, int64_t hi,
-                       const uint64_t* d_init_bits, const double* d_values, uint64_t* d_neg_bits,
-                       int* nblocks, double* d_dbg, const double* d_points) {
+int sl_gp_small_launch(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, int* nblocks) {
     const bool general = sl_model_is_general(model);
     const int variant = sl_dim_variant_of(model);
 #define SL_GPS(G, D_, M_)                                                                          \
-    return launch_small<G, D_, M_>(ctx, model, lo, hi, d_init_bits, d_values, d_neg_bits, nblocks, \
-                                   d_dbg, d_points)
+    return launch_small<G, D_, M_>(ctx, model, a.lo, a.hi, a.init_bits, a.values, a.neg_bits, nblocks, \
+                                   a.dbg, a.points)
     if (general) {
         if (variant == 2) SL_GPS(true, 2, 1);
         SL_GPS(true, 0, 0);

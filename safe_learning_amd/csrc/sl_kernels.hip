@@ -55,14 +55,12 @@ static int env_int(const char* name) {
 
 void sl_env_read(SlEnv* e) {
     e->gp_cfg = env_int("SL_GP_CFG");
-    if (e->gp_cfg > 3) e->gp_cfg = -1;
+    if (e->gp_cfg == 1 || e->gp_cfg > 3) e->gp_cfg = -1;
     e->gp_small = env_int("SL_GP_SMALL");
     e->gp_small_waves = env_int("SL_GP_SMALL_WAVES");
-    e->gp_small_split = env_int("SL_GP_SMALL_SPLIT");
     e->det_rows = env_int("SL_DET_ROWS");
     e->gp4_one_panel = env_int("SL_GP4_ONE_PANEL");
     e->gp4_seeds = env_int("SL_GP4_SEEDS");
-    e->gp4_tickets = env_int("SL_GP4_TICKETS");
     e->bellman_mfma = env_int("SL_BELLMAN_MFMA");
     e->bellman4 = env_int("SL_BELLMAN4");
     e->bellman4_policy = env_int("SL_BELLMAN4_POLICY");
@@ -779,7 +777,6 @@ __global__ __launch_bounds__(SL_BLOCK) void k_reduce_fail(const sl_key* __restri
 }
 
 
-// shared by sl_lyap_sweep (grid cells) and sl_eval_points (explicit points)
 // the model the posterior pass of a split sweep sees: same grid, policy and GP; a zero quadratic V
 // and a scalar L_v (the fast path of the GP kernels) - its records carry mean and error only
 static SlDevModel sl_posterior_only(const SlDevModel& full) {
@@ -791,137 +788,133 @@ static SlDevModel sl_posterior_only(const SlDevModel& full) {
     return m;
 }
 
-// table flavours (V, L_v = |grad V|, interpolated policy) of a GP model whose heads are served by
-// k_gp_sweep4: action table + posterior records + check instead of k_gp_sweep's 16x16x4 structure
-static bool sl_gp_three_pass(sl_ctx* ctx) {
-    const SlDevModel& M = ctx->h_model;
-    if (M.m.value.kind == SL_V_NETWORK || !sl_model_is_general(M)) return false;
-    bool other_kernels = false;
-    for (int h = 0; h < ctx->h_gp.nheads; ++h) other_kernels = other_kernels || ctx->gp_heads[h].d_kernel;
-    SlDevModel po = sl_posterior_only(M);
-    if (po.m.policy.kind == SL_POLICY_TRI) po.m.policy.kind = SL_POLICY_TABLE;
-    if (ctx->gp_cfg == 2 && !other_kernels && sl_gp4_supports(po)) return true;
-    // small training sets (k_gp_small, the notebooks' regime): the same split
-    if (ctx->env.gp_small_split == 1 && (other_kernels || ctx->gp_cfg == 0) && sl_gp_small_supports(ctx, po))
-        return true;
-    return false;
+// the posterior pass of a split sweep over a: its records go to ctx->d_records ((2 + 2d) doubles
+// per cell, then action_doubles per cell for an action table, then the pass's own mask words)
+static int sl_posterior_pass(sl_ctx* ctx, const SlSweepArgs& a, int action_doubles, SlSweepArgs* posterior) {
+    const size_t cells = (size_t)(a.hi - a.lo), rec_doubles = cells * (2 + 2 * ctx->h_model.m.grid.d);
+    const size_t doubles = rec_doubles + cells * action_doubles;
+    SL_HIP_CHECK(ctx, sl_grow(ctx, &ctx->d_records, &ctx->records_bytes,
+                              sizeof(double) * doubles + sizeof(uint64_t) * ((cells + 63) / 64 + 1)));
+    double* rec = reinterpret_cast<double*>(ctx->d_records);
+    *posterior = {a.lo, a.hi, nullptr, nullptr, reinterpret_cast<uint64_t*>(rec + doubles), rec, a.points};
+    return SL_OK;
 }
 
-int sl_sweep_any(sl_ctx* ctx, int64_t lo, int64_t hi, const uint64_t* d_init_bits,
-                 const double* d_values, uint64_t* d_neg_bits, sl_sweep_result* d_result,
-                 double* d_dbg, const double* d_points) {
-    int rc = sl_check_ready(ctx, "sl_lyap_sweep");
-    if (rc) return rc;
-    if (lo < 0 || hi < lo || (!d_points && hi > ctx->h_model.gf.nindex) ||
-        ((lo & 63) && hi != lo))      // an empty shard may start anywhere (tail ranks of a small grid)
-        return sl_fail(ctx, SL_ERR_INVALID, "sl_lyap_sweep: bad range (lo must be a multiple of 64)");
-    // with explicit points a TABLE policy is indexed by the point number (one action per point)
-    if (!d_neg_bits || !d_result) return sl_fail(ctx, SL_ERR_INVALID, "sl_lyap_sweep: NULL output");
-    SL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    SlPolicyTableScope network_policy(ctx, lo, hi, d_points);   // (a network policy becomes a per-cell table)
-    if (network_policy.rc) return network_policy.rc;
-    int blocks = 1;
-    ctx->last_kernel[0] = 0;
-    if (hi == lo) {
-        blocks = 0;
-    } else if (ctx->h_model.m.value.kind == SL_V_NETWORK) {
-        // network V: (1) GP posterior records from the MFMA kernel, (2) cooperative network check
-        const double* records = nullptr;
-        if (ctx->h_model.m.dynamics.kind == SL_DYN_GP) {
-            const int d = ctx->h_model.m.grid.d;
-            const size_t need = sizeof(double) * (size_t)(hi - lo) * (2 + 2 * d) +
-                                sizeof(uint64_t) * (size_t)((hi - lo + 63) / 64 + 1);
-            SL_HIP_CHECK(ctx, sl_grow(ctx, &ctx->d_records, &ctx->records_bytes, need));
-            double* rec = reinterpret_cast<double*>(ctx->d_records);
-            uint64_t* tmp_bits = reinterpret_cast<uint64_t*>(rec + (size_t)(hi - lo) * (2 + 2 * d));
-            SlDevModel posterior_only = sl_posterior_only(ctx->h_model);
-            int gp_blocks = 0;
-            rc = sl_gp_sweep_launch(ctx, posterior_only, lo, hi, nullptr, nullptr, tmp_bits,
-                                    &gp_blocks, rec, d_points);
-            if (rc) return rc;
-            records = rec;
-        }
-        rc = sl_nn_check_launch(ctx, lo, hi, d_init_bits, d_values, records, d_neg_bits, &blocks,
-                                d_dbg, d_points);
-        if (rc) return rc;
-    } else if (ctx->h_model.m.dynamics.kind == SL_DYN_GP && sl_gp_three_pass(ctx)) {
-        // table V / L_v = |grad V| / interpolated policy on a large training set (see k_policy_table)
-        const SlDevModel& full = ctx->h_model;
-        const int d = full.m.grid.d, m = full.in_dim - d;
-        const size_t rec_doubles = (size_t)(hi - lo) * (2 + 2 * d), act_doubles = (size_t)(hi - lo) * m;
-        const size_t need = sizeof(double) * (rec_doubles + act_doubles) +
-                            sizeof(uint64_t) * (size_t)((hi - lo + 63) / 64 + 1);
-        SL_HIP_CHECK(ctx, sl_grow(ctx, &ctx->d_records, &ctx->records_bytes, need));
-        double* rec = reinterpret_cast<double*>(ctx->d_records);
-        double* act = rec + rec_doubles;
-        uint64_t* tmp_bits = reinterpret_cast<uint64_t*>(act + act_doubles);
-        SlAux aux{ctx->d_tri, ctx->d_net};
-        SlDevModel posterior_only = sl_posterior_only(full);
-        const int variant = sl_dim_variant(full);
-        const bool tri_policy = full.m.policy.kind == SL_POLICY_TRI;
-        blocks = sl_grid_blocks(hi - lo);
-        if (tri_policy) {
-#define SL_CALL(G, D_, M_)                                                                     \
-    hipLaunchKernelGGL((k_policy_table<true, D_, M_>), dim3(blocks), dim3(SL_BLOCK), 0, ctx->stream, \
-                       full, aux, lo, hi, d_points, act)
-            SL_DISPATCH_DIMS(variant, true, SL_CALL);
-#undef SL_CALL
-            SL_HIP_CHECK(ctx, hipGetLastError());
-            // the per-cell table is indexed by the cell (or point) number
-            posterior_only.m.policy.kind = SL_POLICY_TABLE;
-            posterior_only.m.policy.d_table = act - lo * m;
-        }
+// network V: (1) GP posterior records from the MFMA kernel, (2) cooperative network check
+static int sweep_network_value(sl_ctx* ctx, const SlSweepArgs& a, int* blocks) {
+    if (ctx->h_model.m.value.kind != SL_V_NETWORK) return SL_DECLINED;
+    SlSweepArgs posterior{};
+    if (ctx->h_model.m.dynamics.kind == SL_DYN_GP) {
         int gp_blocks = 0;
-        rc = sl_gp_sweep_launch(ctx, posterior_only, lo, hi, nullptr, nullptr, tmp_bits, &gp_blocks,
-                                rec, d_points);
+        int rc = sl_posterior_pass(ctx, a, 0, &posterior);
+        if (!rc) rc = sl_gp_sweep_launch(ctx, sl_posterior_only(ctx->h_model), posterior, &gp_blocks);
         if (rc) return rc;
+    }
+    return sl_nn_check_launch(ctx, a.lo, a.hi, a.init_bits, a.values, posterior.dbg, a.neg_bits, blocks, a.dbg,
+                              a.points);
+}
+
+// table flavours (V, L_v = |grad V|, interpolated policy) of a GP model whose heads are served by
+// k_gp_sweep4: action table + posterior records + check instead of k_gp_sweep's 16x16x4 structure
+static int sweep_gp_three_pass(sl_ctx* ctx, const SlSweepArgs& a, int* blocks) {
+    const SlDevModel& full = ctx->h_model;
+    if (full.m.dynamics.kind != SL_DYN_GP || !sl_model_is_general(full) || ctx->gp_cfg != 2 ||
+        sl_has_other_kernels(ctx))
+        return SL_DECLINED;
+    SlDevModel posterior_only = sl_posterior_only(full);
+    const bool tri_policy = full.m.policy.kind == SL_POLICY_TRI;
+    if (tri_policy) posterior_only.m.policy.kind = SL_POLICY_TABLE;
+    if (!sl_gp4_supports(posterior_only)) return SL_DECLINED;
+    const int64_t lo = a.lo, hi = a.hi;
+    const int m = full.in_dim - full.m.grid.d;
+    SlSweepArgs posterior;
+    int rc = sl_posterior_pass(ctx, a, m, &posterior);
+    if (rc) return rc;
+    const double* rec = posterior.dbg;
+    double* act = posterior.dbg + (size_t)(hi - lo) * (2 + 2 * full.m.grid.d);
+    SlAux aux{ctx->d_tri, ctx->d_net};
+    const int variant = sl_dim_variant(full);
+    *blocks = sl_grid_blocks(hi - lo);
+    if (tri_policy) {
 #define SL_CALL(G, D_, M_)                                                                     \
-    hipLaunchKernelGGL((k_check_records<true, D_, M_>), dim3(blocks), dim3(SL_BLOCK), 0, ctx->stream, \
-                       full, aux, lo, hi, d_init_bits, d_values, rec, d_neg_bits, ctx->d_partials, \
-                       d_dbg, d_points)
+    hipLaunchKernelGGL((k_policy_table<true, D_, M_>), dim3(*blocks), dim3(SL_BLOCK), 0, ctx->stream, \
+                       full, aux, lo, hi, a.points, act)
         SL_DISPATCH_DIMS(variant, true, SL_CALL);
 #undef SL_CALL
         SL_HIP_CHECK(ctx, hipGetLastError());
-        sl_note_kernel(ctx, true, tri_policy ? "k_policy_table + k_check_records" : "k_check_records");
-    } else if (ctx->h_model.m.dynamics.kind == SL_DYN_GP) {
-        rc = sl_gp_sweep_launch(ctx, ctx->h_model, lo, hi, d_init_bits, d_values, d_neg_bits,
-                                &blocks, d_dbg, d_points);
-        if (rc) return rc;
-    } else if (!d_dbg && !d_points && ctx->env.det_rows != 0 && sl_det_rows_supports(ctx->h_model, lo, hi)) {
-        // linear dynamics / linear policy / quadratic V: 8 cells of a grid row per thread
-        rc = sl_det_rows_launch(ctx, lo, hi, d_init_bits, d_values, d_neg_bits, &blocks);
-        if (rc) return rc;
-    } else {
-        blocks = sl_grid_blocks(hi - lo);
-        SlAux aux{ctx->d_tri, ctx->d_net};
-        const int dyn = ctx->h_model.m.dynamics.kind;
-        const bool pow2 = ctx->h_model.gf.all_pow2 && ctx->h_model.gf.nindex <= 0xffffffffll &&
-                          !d_dbg && !d_points;
-#define SL_LAUNCH_DET(G, D_, M_, DYN_)                                                          \
-    do {                                                                                        \
-        if (pow2 && !(G) && (D_) > 0 && (DYN_) != 0)                                            \
-            hipLaunchKernelGGL((k_det_sweep<G, D_, M_, DYN_, (!(G) && (D_) > 0 && (DYN_) != 0)>), \
-                               dim3(blocks), dim3(SL_BLOCK), 0, ctx->stream, ctx->h_model, aux, \
-                               lo, hi, d_init_bits, d_values, d_neg_bits, ctx->d_partials,      \
-                               d_dbg, d_points);                                                \
-        else                                                                                    \
-            hipLaunchKernelGGL((k_det_sweep<G, D_, M_, DYN_>), dim3(blocks), dim3(SL_BLOCK), 0, \
-                               ctx->stream, ctx->h_model, aux, lo, hi, d_init_bits, d_values,  \
-                               d_neg_bits, ctx->d_partials, d_dbg, d_points);                   \
-    } while (0)
+        // the per-cell table is indexed by the cell (or point) number
+        posterior_only.m.policy.d_table = act - lo * m;
+    }
+    int gp_blocks = 0;
+    rc = sl_gp_sweep_launch(ctx, posterior_only, posterior, &gp_blocks);
+    if (rc) return rc;
+#define SL_CALL(G, D_, M_)                                                                     \
+    hipLaunchKernelGGL((k_check_records<true, D_, M_>), dim3(*blocks), dim3(SL_BLOCK), 0, ctx->stream, \
+                       full, aux, lo, hi, a.init_bits, a.values, rec, a.neg_bits, ctx->d_partials, \
+                       a.dbg, a.points)
+    SL_DISPATCH_DIMS(variant, true, SL_CALL);
+#undef SL_CALL
+    SL_HIP_CHECK(ctx, hipGetLastError());
+    sl_note_kernel(ctx, true, tri_policy ? "k_policy_table + k_check_records" : "k_check_records");
+    return SL_OK;
+}
+
+static int sweep_gp(sl_ctx* ctx, const SlSweepArgs& a, int* blocks) {
+    if (ctx->h_model.m.dynamics.kind != SL_DYN_GP) return SL_DECLINED;
+    return sl_gp_sweep_launch(ctx, ctx->h_model, a, blocks);
+}
+
+template <bool G, int D, int M, int DYN>
+static void launch_det(sl_ctx* ctx, const SlSweepArgs& a, int blocks, bool pow2) {
+    constexpr bool POW2_OK = !G && D > 0 && DYN != 0;
+    auto kern = POW2_OK && pow2 ? k_det_sweep<G, D, M, DYN, POW2_OK> : k_det_sweep<G, D, M, DYN>;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(SL_BLOCK), 0, ctx->stream, ctx->h_model, SlAux{ctx->d_tri, ctx->d_net},
+                       a.lo, a.hi, a.init_bits, a.values, a.neg_bits, ctx->d_partials, a.dbg, a.points);
+}
+
+// deterministic dynamics, one cell per thread: takes every model
+static int sweep_det(sl_ctx* ctx, const SlSweepArgs& a, int* blocks) {
+    const SlDevModel& M = ctx->h_model;
+    *blocks = sl_grid_blocks(a.hi - a.lo);
+    const int dyn = M.m.dynamics.kind, variant = sl_dim_variant(M);
+    const bool general = sl_model_is_general(M);
+    const bool pow2 = M.gf.all_pow2 && M.gf.nindex <= 0xffffffffll && !a.dbg && !a.points;
 #define SL_CALL(G, D_, M_)                                                                     \
     do {                                                                                       \
-        if (!(G) && (D_) > 0 && dyn == SL_DYN_LINEAR) SL_LAUNCH_DET(G, D_, M_, SL_DYN_LINEAR); \
-        else if (!(G) && (D_) == 2 && dyn == SL_DYN_PENDULUM) SL_LAUNCH_DET(G, D_, M_, SL_DYN_PENDULUM); \
-        else if (!(G) && (D_) == 4 && dyn == SL_DYN_CARTPOLE) SL_LAUNCH_DET(G, D_, M_, SL_DYN_CARTPOLE); \
-        else SL_LAUNCH_DET(G, D_, M_, 0);                                                      \
+        if (!(G) && (D_) > 0 && dyn == SL_DYN_LINEAR) launch_det<G, D_, M_, SL_DYN_LINEAR>(ctx, a, *blocks, pow2); \
+        else if (!(G) && (D_) == 2 && dyn == SL_DYN_PENDULUM) launch_det<G, D_, M_, SL_DYN_PENDULUM>(ctx, a, *blocks, pow2); \
+        else if (!(G) && (D_) == 4 && dyn == SL_DYN_CARTPOLE) launch_det<G, D_, M_, SL_DYN_CARTPOLE>(ctx, a, *blocks, pow2); \
+        else launch_det<G, D_, M_, 0>(ctx, a, *blocks, pow2);                                   \
     } while (0)
-        SL_DISPATCH_DIMS(sl_dim_variant(ctx->h_model), sl_model_is_general(ctx->h_model), SL_CALL);
-        sl_note_kernel(ctx, false, "k_det_sweep<general=%d, d=%d, dynamics=%d, pow2=%d>",
-                       (int)sl_model_is_general(ctx->h_model), sl_dim_variant(ctx->h_model), dyn, (int)pow2);
+    SL_DISPATCH_DIMS(variant, general, SL_CALL);
 #undef SL_CALL
-#undef SL_LAUNCH_DET
-        SL_HIP_CHECK(ctx, hipGetLastError());
+    sl_note_kernel(ctx, false, "k_det_sweep<general=%d, d=%d, dynamics=%d, pow2=%d>", (int)general, variant,
+                   dyn, (int)pow2);
+    SL_HIP_CHECK(ctx, hipGetLastError());
+    return SL_OK;
+}
+
+// shared by sl_lyap_sweep (grid cells) and sl_eval_points (explicit points)
+int sl_sweep_any(sl_ctx* ctx, const SlSweepArgs& a, sl_sweep_result* d_result, bool timed) {
+    int rc = sl_check_ready(ctx, "sl_lyap_sweep");
+    if (rc) return rc;
+    if (a.lo < 0 || a.hi < a.lo || (!a.points && a.hi > ctx->h_model.gf.nindex) ||
+        ((a.lo & 63) && a.hi != a.lo))   // an empty shard may start anywhere (tail ranks of a small grid)
+        return sl_fail(ctx, SL_ERR_INVALID, "sl_lyap_sweep: bad range (lo must be a multiple of 64)");
+    // with explicit points a TABLE policy is indexed by the point number (one action per point)
+    if (!a.neg_bits || !d_result) return sl_fail(ctx, SL_ERR_INVALID, "sl_lyap_sweep: NULL output");
+    SlTimed timing(timed ? ctx : nullptr, 0);
+    SL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    SlPolicyTableScope network_policy(ctx, a.lo, a.hi, a.points);   // (a network policy becomes a per-cell table)
+    if (network_policy.rc) return network_policy.rc;
+    int blocks = 0;
+    ctx->last_kernel[0] = 0;
+    if (a.hi > a.lo) {
+        for (auto launch : {sweep_network_value, sweep_gp_three_pass, sweep_gp, sl_det_rows_launch, sweep_det}) {
+            rc = launch(ctx, a, &blocks);
+            if (rc != SL_DECLINED) break;
+        }
+        if (rc) return rc;
     }
     hipLaunchKernelGGL(k_reduce_fail, dim3(1), dim3(SL_BLOCK), 0, ctx->stream, ctx->d_partials,
                        blocks, d_result);
@@ -932,8 +925,7 @@ int sl_sweep_any(sl_ctx* ctx, int64_t lo, int64_t hi, const uint64_t* d_init_bit
 extern "C" int sl_lyap_sweep(sl_ctx* ctx, int64_t lo, int64_t hi, const uint64_t* d_init_bits,
                              const double* d_values, uint64_t* d_neg_bits,
                              sl_sweep_result* d_result, double* d_dbg) {
-    SlTimed timed(ctx, 0);
-    return sl_sweep_any(ctx, lo, hi, d_init_bits, d_values, d_neg_bits, d_result, d_dbg, nullptr);
+    return sl_sweep_any(ctx, {lo, hi, d_init_bits, d_values, d_neg_bits, d_dbg, nullptr}, d_result, true);
 }
 
 // =============================================================================================

@@ -19,13 +19,13 @@ GP_CASES = [
     ("pendulum", dict(num_points=40, n_gp=3, tau_scale=0.0, **TIGHT), None, 5),        # tiny n
     ("pendulum", dict(num_points=64, n_gp=128, tau_scale=0.01, **INFORMED), None, 100),  # cfg 0, 2 panels
     ("pendulum", dict(num_points=[33, 50], n_gp=200, tau_scale=0.01, **INFORMED), None, 100),
-    ("pendulum", dict(num_points=48, n_gp=600, tau_scale=0.01, **INFORMED), "1", 100),  # cfg 1, 1 panel
+    ("pendulum", dict(num_points=48, n_gp=600, tau_scale=0.01, **INFORMED), "3", 100),  # k_gp_sweep, 2 panels
     ("pendulum", dict(num_points=48, n_gp=600, tau_scale=0.01, **INFORMED), "2", 100),  # cfg 2, 2 panels
     ("pendulum", dict(num_points=40, n_gp=2600, tau_scale=0.01, **INFORMED), None, 100),   # inputs read from L2
     # ---- cart-pole (d = 4, p = 5: the headline instantiation) -------------------------
     ("cartpole", dict(num_points=12, n_gp=150, tau_scale=0.0, **TIGHT), None, 100),     # cfg 0
     ("cartpole", dict(num_points=12, n_gp=100, tau_scale=0.0, stack=True, **TIGHT), None, 100),
-    ("cartpole", dict(num_points=12, n_gp=1100, tau_scale=0.0, **INFORMED), "1", 100),  # cfg 1, 2 panels
+    ("cartpole", dict(num_points=12, n_gp=1100, tau_scale=0.0, **INFORMED), "3", 100),  # k_gp_sweep, 3 panels
     ("cartpole", dict(num_points=14, n_gp=520, tau_scale=0.0, **TIGHT), "2", 100),      # cfg 2, 2 panels
     ("cartpole", dict(num_points=14, n_gp=520, tau_scale=0.0, **INFORMED), "2", 100),
     ("cartpole", dict(num_points=12, n_gp=300, tau_scale=0.0, stack=True, **TIGHT), None, 100),  # stack on cfg 2

@@ -1087,6 +1087,15 @@ def test_last_kernel_names_what_ran(sl, monkeypatch):
     lyap = build_lyapunov(cases.make_case("pendulum", num_points=32, n_gp=100, tau_scale=0.0))
     lyap.update_safe_set()
     assert lyap._ctx.last_kernel().startswith("k_gp_sweep<")
+    # SL_GP_CFG=1 (a configuration that no longer exists) leaves the engine's choice alone
+    monkeypatch.delenv("SL_GP_SMALL")
+    monkeypatch.setenv("SL_GP_CFG", "1")
+    lyap = build_lyapunov(cases.make_case("cartpole", num_points=8, n_gp=300, tau_scale=0.0))
+    lyap.update_safe_set()
+    assert lyap._ctx.last_kernel().startswith("k_gp_sweep4<d=4")
+    lyap = build_lyapunov(cases.make_case("pendulum", num_points=32, n_gp=100, tau_scale=0.0))
+    lyap.update_safe_set()
+    assert lyap._ctx.last_kernel().startswith("k_gp_small<")
 
 
 def _neg_mask_of_update(lyap):

@@ -116,10 +116,13 @@ def _matern_stack(ns, kern_lib, case, n):
     return ns.FunctionStack(heads)
 
 
-@pytest.mark.parametrize("n,cfg", [(300, None), (130, "3"), (130, "1")], ids=["n300", "n130_cfg3", "n130_cfg1"])
-def test_large_sets_run_on_the_16x16x4_kernel(n, cfg, monkeypatch):
+@pytest.mark.parametrize("n,cfg,kernel", [(300, None, "k_gp_sweep<"), (130, "3", "k_gp_sweep<"),
+                                          (130, "0", "k_gp_sweep<W=4, R=1, CB=1")],
+                         ids=["n300", "n130_cfg3", "n130_cfg0"])
+def test_large_sets_run_on_the_16x16x4_kernel(n, cfg, kernel, monkeypatch):
     """More than 256 training points (or a forced configuration): ``k_gp_sweep`` evaluates the
-    leaves; records, masks and the safe set equal the oracle's."""
+    leaves; records, masks and the safe set equal the oracle's.  ``n130_cfg0``: the small panel
+    shape, where the engine goes when ``k_gp_small`` declines."""
     import safe_learning_amd as sl
     from safe_learning_amd.benchmarks import build_specs, initial_safe_mask
     if cfg is not None:
@@ -134,7 +137,7 @@ def test_large_sets_run_on_the_16x16x4_kernel(n, cfg, monkeypatch):
     olyap = cases.oracle_lyapunov(case, dynamics=odynamics)
     lyap.update_safe_set()
     olyap.update_safe_set()
-    assert lyap._ctx.last_kernel().startswith("k_gp_sweep<"), lyap._ctx.last_kernel()
+    assert lyap._ctx.last_kernel().startswith(kernel), lyap._ctx.last_kernel()
     np.testing.assert_array_equal(lyap.safe_set, olyap.safe_set)
     assert lyap.c_max == olyap.c_max
     nidx = lyap.discretization.nindex

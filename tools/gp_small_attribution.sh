@@ -11,9 +11,7 @@ one() { timeout 300 python bench.py --config $1 --steps 6 --warmup 2 --no-cpu-ba
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']; print('$2', d['config']['name'], round(r['kernel_ms'],3), r.get('kernel'))"; }
 for c in C2-table-large C2-notebook; do
-  for split in 0 1; do
-    for f in 0 1 2 4 6 7 8 15 31 32 63; do
-      SL_GP_SMALL_SPLIT=$split SL_GPS_FLAGS=$f one $c "split=$split flags=$f"
-    done
+  for f in 0 1 2 4 6 7 8 15 31 32 63; do
+    SL_GPS_FLAGS=$f one $c "flags=$f"
   done
 done
