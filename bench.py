@@ -1,7 +1,7 @@
 """Headline benchmark: grid-cell Lyapunov checks per second (BASELINE.json).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C4] [--num-points P] [--n-gp G]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full]
 
 Default workload (BASELINE.json configs[3] / SURVEY 8d "C4"): cart-pole state grid 128^4 (2.68e8
 cells), 1024-point shared-kernel RBF GP over [x, u] (p = 5 inputs, 4 outputs), quadratic LQR
@@ -24,6 +24,14 @@ The grid is sharded by contiguous index ranges: total work is fixed, so scaling 
 ``--dump-outputs DIR``: after the timed steps, what the last of them handed its caller is written
 as ``DIR/<name>.npy`` (float32 / float64; see ``step_outputs``), so that two builds can be compared
 output for output - the inputs are seeded and the same for the same arguments.
+
+A plain run does what its figure needs: it sets up, warms up, times the K steps, writes its outputs
+and prints the line (the figures of the timed steps themselves - kernel and collective times, the
+roofline - and what the last step left: c_max, safe and passing cells).  ``--full`` adds what takes
+work of its own: the CPU baseline (``cpu_baseline``, rank 0 of one process), two updates with c_max
+read (``config.ms_per_step_incl_c_max_read``) and one with the mask on the host (``end_to_end_ms``),
+C5's recomputing sweep (``config.uncached_sweep``) and its run to convergence
+(``config.sweeps_to_convergence``, ``time_to_convergence_s``, ...).
 """
 
 import argparse
@@ -412,24 +420,25 @@ def run_rank(args, rank, world, local_rank, backend):
         if args.successor_cache == "off":
             obj.successor_cache(0)
         else:
-            # (i) the recomputing sweep - what every sweep cost before the successor cache and what the
-            # first sweep of a loop still costs: a few sweeps with the cache switched off, HIP
-            # events around the kernels; (ii) the loop as a user runs it, from V = 0: the first
-            # sweep locates the successors and fills the cache, the timed steps below and the
-            # convergence run behind them are served from it
-            obj.successor_cache(0)
-            obj.value_iteration(actions)
-            barrier()
-            obj._ctx.timing_configure(8)
-            t0 = time.perf_counter()
-            for _ in range(3):
+            # (i) --full: the recomputing sweep - what every sweep cost before the successor cache
+            # and what the first sweep of a loop still costs: a few sweeps with the cache switched
+            # off, HIP events around the kernels; (ii) the loop as a user runs it, from V = 0: the
+            # first sweep locates the successors and fills the cache, the timed steps below (and,
+            # with --full, the convergence run behind them) are served from it
+            if args.full:
+                obj.successor_cache(0)
                 obj.value_iteration(actions)
-            barrier()
-            un_ms = 1e3 * (time.perf_counter() - t0) / 3
-            un_kernel_ms = float(np.mean(obj._ctx.timing_collect(obj._ctx.TIMING_BELLMAN)))
-            obj._ctx.timing_configure(0)
-            extra["uncached_sweep"] = {"ms_per_sweep": un_ms, "kernel_ms": un_kernel_ms,
-                                       "kernel": obj._ctx.last_kernel()}
+                barrier()
+                obj._ctx.timing_configure(8)
+                t0 = time.perf_counter()
+                for _ in range(3):
+                    obj.value_iteration(actions)
+                barrier()
+                un_ms = 1e3 * (time.perf_counter() - t0) / 3
+                un_kernel_ms = float(np.mean(obj._ctx.timing_collect(obj._ctx.TIMING_BELLMAN)))
+                obj._ctx.timing_configure(0)
+                extra["uncached_sweep"] = {"ms_per_sweep": un_ms, "kernel_ms": un_kernel_ms,
+                                           "kernel": obj._ctx.last_kernel()}
             obj.successor_cache(-1)
             obj.value_function.parameters = np.zeros((obj.discretization.nindex, 1))
             barrier()
@@ -491,10 +500,11 @@ def run_rank(args, rank, world, local_rank, backend):
         t1 = time.perf_counter()
         outputs = step_outputs(kind, obj, result)
         capture_s = time.perf_counter() - t1
+    end_to_end_ms = None
     if kind == "lyapunov":
-        from safe_learning_amd.benchmarks import initial_safe_mask
         extra["safe_cells"] = int(obj.safe_count)
-        extra["initial_cells"] = int(np.count_nonzero(initial_safe_mask(case)))
+        # (the read-only array build_lyapunov made of benchmarks.initial_safe_mask(case))
+        extra["initial_cells"] = int(np.count_nonzero(obj.initial_safe_set))
         extra["c_max"] = float(obj.c_max)
         extra["tau"] = float(case["tau"])
         if "dynamics" in case and case["dynamics"].get("kind") == "gp":
@@ -512,37 +522,36 @@ def run_rank(args, rank, world, local_rank, backend):
         if grouped:
             dist.all_reduce(cnt)
         extra["negative_cells"] = int(cnt[0])
-        # update_safe_set() returns when its kernels are enqueued; the reference's call also leaves
-        # c_max on the host (lyapunov.py:590-595).  The same loop with c_max READ after every update
-        # (the 64-byte record copy + the host code behind it - and, when nothing failed, the select
-        # passes of the no-failure quirk - inside the clock): two steps, labelled.
-        barrier()
-        t1 = time.perf_counter()
-        for _ in range(2):
-            obj.update_safe_set()
-            obj.c_max
-        barrier()
-        extra["ms_per_step_incl_c_max_read"] = 1e3 * (time.perf_counter() - t1) / 2
-        # end to end: one more update including the bool[N] mask on the host (lyapunov.py:598-606)
-        barrier()
-        t1 = time.perf_counter()
-        obj.update_safe_set()
-        mask = obj.safe_set
-        end_to_end_ms = 1e3 * (time.perf_counter() - t1)
-        assert int(mask.sum()) == extra["safe_cells"]
         if args.config in ("C2", "C4") and extra["safe_cells"] <= extra["initial_cells"] \
                 and not args.diagnostic and args.gp_variant != "survey":
             # (attribution runs skip phases; SURVEY 8d's literal hyper-parameters are known to
             # let one cell of 2.7e8 pass - that variant exists to show the cost is the same)
             raise SystemExit("bench.py: degenerate workload - the level set did not grow (%d safe "
                              "cells, %d initial)" % (extra["safe_cells"], extra["initial_cells"]))
+        if args.full:
+            # update_safe_set() returns when its kernels are enqueued; the reference's call also leaves
+            # c_max on the host (lyapunov.py:590-595).  The same loop with c_max READ after every update
+            # (the 64-byte record copy + the host code behind it - and, when nothing failed, the select
+            # passes of the no-failure quirk - inside the clock): two steps, labelled.
+            barrier()
+            t1 = time.perf_counter()
+            for _ in range(2):
+                obj.update_safe_set()
+                obj.c_max
+            barrier()
+            extra["ms_per_step_incl_c_max_read"] = 1e3 * (time.perf_counter() - t1) / 2
+            # end to end: one more update including the bool[N] mask on the host (lyapunov.py:598-606)
+            barrier()
+            t1 = time.perf_counter()
+            obj.update_safe_set()
+            mask = obj.safe_set
+            end_to_end_ms = 1e3 * (time.perf_counter() - t1)
+            assert int(mask.sum()) == extra["safe_cells"]
     elif kind == "policy":
-        end_to_end_ms = None
         table = obj.policy._host_parameters().reshape(-1, case["num_points"][-1])
         extra["distinct_actions_per_row"] = float(
             np.mean((np.diff(np.sort(table, axis=1), axis=1) != 0).sum(axis=1) + 1))
-    else:
-        end_to_end_ms = None
+    elif kind == "bellman" and args.full:
         # sweeps to convergence at max|dV| <= 1e-6 max|V| (SURVEY 8d metric iii), continuing from
         # the table the timed sweeps left
         sweeps, rel, last, monotone = args.warmup + args.steps, float("inf"), float("inf"), True
@@ -638,18 +647,19 @@ def run_rank(args, rank, world, local_rank, backend):
         forced = any(os.environ.get(k) for k in ("SL_GP_CFG", "SL_BELLMAN4", "SL_BELLMAN_MFMA"))
         forced = forced or args.num_points or args.n_gp      # other shapes may pick other kernels
         if args.config == "C5" and args.successor_cache != "off" and not forced:
-            # the timed steps come from the cache; the recomputing sweep in front of them must have
-            # run on the 4x4x4 kernels
+            # the timed steps come from the cache; the recomputing sweep in front of them (--full)
+            # must have run on the 4x4x4 kernels
+            uncached = extra.get("uncached_sweep", {}).get("kernel")
             if not (out["roofline"]["kernel"].startswith("k_bellman_cached")
-                    and extra["uncached_sweep"]["kernel"].startswith(expected)
+                    and (uncached is None or uncached.startswith(expected))
                     and "k_bellman_lookup" in extra["first_sweep_kernel"]):
                 raise SystemExit("bench.py: C5 ran on %r / %r / %r" % (
-                    out["roofline"]["kernel"], extra["uncached_sweep"]["kernel"], extra["first_sweep_kernel"]))
+                    out["roofline"]["kernel"], uncached, extra["first_sweep_kernel"]))
             expected = None
         if expected and not forced and not out["roofline"]["kernel"].startswith(expected):
             raise SystemExit("bench.py: %s ran on %r instead of %s* (library built without its "
                              "4x4x4 kernels?)" % (args.config, out["roofline"]["kernel"], expected))
-        if world == 1 and not args.no_cpu_baseline and kind != "policy":
+        if args.full and world == 1 and not args.no_cpu_baseline and kind != "policy":
             # (the policy-evaluation line has no CPU leg of its own: C5's is the same oracle sweep)
             out["cpu_baseline"] = cpu_baseline(kind, case, min_cells=args.cpu_cells)
         if outputs is not None:
@@ -844,7 +854,7 @@ def parse_args(argv=None):
     ap.add_argument("--num-points", type=int, default=None)
     ap.add_argument("--n-gp", type=int, default=None)
     ap.add_argument("--family", default="cartpole", choices=["cartpole", "pendulum"])
-    ap.add_argument("--max-sweeps", type=int, default=3000, help="C5: bound of the convergence run")
+    ap.add_argument("--max-sweeps", type=int, default=3000, help="C5: bound of the convergence run (--full)")
     ap.add_argument("--successor-cache", default="on", choices=["on", "off"],
                     help="C5 / C5-policy: serve the sweeps after the first from the successor cache "
                          "(default) or recompute every sweep (the kernels of the first sweep)")
@@ -852,7 +862,11 @@ def parse_args(argv=None):
                     help="allow SL_LIB_PATH / SL_GP4_SKIP / SL_BM_FLAGS / SL_B4P_FLAGS (development "
                          "builds, timing attribution): the line is tagged 'diagnostic' and its metric "
                          "renamed - not a benchmark result")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline, the "
+                         "updates with c_max read / with the mask on the host, C5's recomputing sweep "
+                         "and its run to convergence (see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-cells", type=int, default=0,
                     help="least number of cells of the CPU baseline sample (SURVEY 8d asks for 2^24 = "
                          "16777216 at C4: ~3.5 minutes on 4 BLAS threads; the default sample is bounded "

@@ -133,6 +133,12 @@ def test_steps_and_warmup_are_checked():
     assert bench.parse_args([]).dump_outputs is None
 
 
+def test_full_is_off_by_default():
+    assert bench.parse_args([]).full is False
+    args = bench.parse_args(["--full", "--no-cpu-baseline", "--steps", "3"])
+    assert args.full and args.no_cpu_baseline and args.steps == 3
+
+
 def test_step_outputs_are_a_fixed_sample_within_the_limit(tmp_path):
     """--dump-outputs: float32 / float64 files, a grid larger than DUMP_SAMPLE cut to the same
     seeded sample of cells in every run, the values of the sampled cells, at most DUMP_LIMIT bytes."""

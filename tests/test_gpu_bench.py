@@ -27,7 +27,7 @@ def _run(*flags, **extra_env):
 
 def test_bench_line_small_and_two_ranks():
     small = ["--num-points", "24", "--n-gp", "300", "--steps", "2", "--warmup", "1"]
-    one = _run(*small)
+    one = _run("--full", *small)
     assert one["n_gpus"] == 1 and one["value"] > 0
     for key in ("metric", "unit", "ms_per_step", "roofline", "cpu_baseline", "end_to_end_ms"):
         assert key in one
@@ -48,6 +48,27 @@ def test_bench_line_small_and_two_ranks():
     assert two["config"]["c_max"] == cfg["c_max"]
 
 
+def test_bench_plain_line_leaves_the_extra_measurements_to_full():
+    """A run without --full sets up, warms up, times its steps and prints the line: the headline
+    fields and the figures of the timed steps, none of the measurements that take work of their own
+    (CPU baseline, the updates with c_max read / the mask on the host, C5's recomputing sweep and
+    run to convergence)."""
+    small = ["--num-points", "24", "--n-gp", "300", "--steps", "2", "--warmup", "1"]
+    one = _run(*small)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert key in one
+    assert one["value"] > 0 and one["ms_per_step"] > 0 and one["higher_is_better"] is True
+    assert "cpu_baseline" not in one and "end_to_end_ms" not in one
+    assert "ms_per_step_incl_c_max_read" not in one["config"]
+    assert 0 < one["config"]["negative_cells"] < 24 ** 4
+    assert one["config"]["safe_cells"] >= one["config"]["initial_cells"] + 50
+    c5 = _run("--config", "C5", "--num-points", "10", "--n-gp", "128", "--steps", "3")
+    assert c5["value"] > 0 and "cpu_baseline" not in c5
+    assert "k_bellman_cached" in c5["roofline"]["kernel"]
+    for key in ("uncached_sweep", "sweeps_to_convergence", "time_to_convergence_s"):
+        assert key not in c5["config"]
+
+
 def test_bench_rccl_call_sequence_at_world_one():
     """The exact collective sequence of the N > 1 path on this one-GPU box: SL_FORCE_COLLECTIVES=1
     makes bench.py create an `nccl` (= RCCL) process group of one rank and the package issue
@@ -66,8 +87,8 @@ def test_bench_rccl_call_sequence_at_world_one():
         assert cfg[key] == ref[key]
     assert forced["roofline"]["kernel"].startswith("k_gp_sweep4<")
     # the Bellman path: table gather + residual reduction over RCCL
-    c5 = ["--config", "C5", "--num-points", "10", "--n-gp", "128", "--steps", "3", "--no-cpu-baseline",
-          "--max-sweeps", "40"]
+    c5 = ["--full", "--config", "C5", "--num-points", "10", "--n-gp", "128", "--steps", "3",
+          "--no-cpu-baseline", "--max-sweeps", "40"]
     plain5 = _run(*c5)
     forced5 = _run("--backend", "nccl", *c5, SL_FORCE_COLLECTIVES="1")
     assert forced5["config"]["relative_residual"] == plain5["config"]["relative_residual"]
@@ -122,13 +143,13 @@ def test_bench_c5_policy_line():
 
 
 def test_bench_c5_runs_to_convergence():
-    out = _run("--config", "C5", "--num-points", "10", "--n-gp", "128", "--steps", "3",
+    out = _run("--full", "--config", "C5", "--num-points", "10", "--n-gp", "128", "--steps", "3",
                "--no-cpu-baseline", "--max-sweeps", "2500")
     cfg = out["config"]
     assert cfg["converged"] and cfg["relative_residual"] <= 1e-6
     assert cfg["residual_monotone"]
     assert 100 < cfg["sweeps_to_convergence"] < 2500      # gamma = 0.98
-    two = _run("--config", "C5", "--num-points", "10", "--n-gp", "128", "--steps", "3",
+    two = _run("--full", "--config", "C5", "--num-points", "10", "--n-gp", "128", "--steps", "3",
                "--no-cpu-baseline", "--max-sweeps", "2500", "--gpus", "2")
     assert two["config"]["sweeps_to_convergence"] == cfg["sweeps_to_convergence"]
 

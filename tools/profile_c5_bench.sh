@@ -14,4 +14,4 @@ rocprofv3 --pmc WRITE_SIZE TCC_MISS_sum -d $OUT/pmc_c -o p -- $B > $OUT/pmc_c.lo
 python tools/pmc_dump.py k_ $(find $OUT/pmc_a $OUT/pmc_b $OUT/pmc_c -name "*_results.db") > $OUT/C5_pmc.txt 2>&1
 rm -rf $OUT/trace $OUT/pmc_a $OUT/pmc_b $OUT/pmc_c
 grep -h '^{' $OUT/trace.log | cut -c1-2500 > $OUT/C5_bench.jsonl
-python bench.py --config C5 --no-cpu-baseline 2>&1 | grep '^{' | cut -c1-2500 > $OUT/C5_bench_full.jsonl
+python bench.py --full --config C5 --no-cpu-baseline 2>&1 | grep '^{' | cut -c1-2500 > $OUT/C5_bench_full.jsonl
