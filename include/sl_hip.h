@@ -217,6 +217,13 @@ SL_API int  sl_gp_set_head_kernel(sl_ctx* ctx, int head, int n, int p, int dout,
 SL_API int  sl_gp_append_point(sl_ctx* ctx, int head, const double* h_x, const double* h_linv_row,
                         const double* h_alpha_new);
 SL_API int  sl_gp_configure(sl_ctx* ctx, int nheads, double beta);
+/* k_gp_sweep4 (one shared-kernel RBF head of more than 256 points, closed-form policy, quadratic V,
+ * no record output) computes the posterior mean of a 64-cell tile first and stops adding variance
+ * panels once bounds of the decrease - err = 0 from below, err = beta sqrt(variance - partial |a|^2)
+ * from above - settle the mask bit of every cell: the same bits, fewer flops.  enable = 0 runs every
+ * panel of every tile (the A/B baseline and the other side of the bit-identity tests); the default
+ * is 1.  Takes effect at the next sweep. */
+SL_API int  sl_gp4_early_configure(sl_ctx* ctx, int enable);
 
 /* Auxiliary grid #slot with a per-vertex table (Triangulation: functions.py:1002-1032,
  * 1064-1101): slot 0 = value function, slot 1 = policy.  h_simplices [nsimplex][d+1] are the

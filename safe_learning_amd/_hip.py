@@ -125,7 +125,7 @@ S_PREFIX, S_REMAINING, S_KEY_V, S_KEY_I, S_RANK, S_NONE = range(6)
 EXPORTS = [
     "sl_version", "sl_ctx_create", "sl_ctx_destroy", "sl_last_error", "sl_ctx_synchronize",
     "sl_last_kernel",
-    "sl_model_set", "sl_policy_touch", "sl_gp_set_head", "sl_gp_set_head_kernel", "sl_gp_append_point", "sl_gp_configure", "sl_tri_set", "sl_tri_set_table",
+    "sl_model_set", "sl_policy_touch", "sl_gp_set_head", "sl_gp_set_head_kernel", "sl_gp_append_point", "sl_gp_configure", "sl_gp4_early_configure", "sl_tri_set", "sl_tri_set_table",
     "sl_network_set", "sl_policy_network_set", "sl_values", "sl_lyap_sweep", "sl_lyap_finalize", "sl_select_pass",
     "sl_values_implicit", "sl_fold_results", "sl_lyap_finalize_dev", "sl_refinement_carry", "sl_select_begin",
     "sl_select_hist", "sl_select_digit",
@@ -176,6 +176,8 @@ def load_library():
                                           c_double_p, c_double_p, c_double_p, C.POINTER(GpKernel)]
     lib.sl_gp_append_point.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p]
     lib.sl_gp_configure.argtypes = [C.c_void_p, C.c_int, C.c_double]
+    if not dev_early or hasattr(lib, "sl_gp4_early_configure"):
+        lib.sl_gp4_early_configure.argtypes = [C.c_void_p, C.c_int]
     lib.sl_tri_set.argtypes = [C.c_void_p, C.c_int, C.POINTER(GridDesc), C.c_int,
                                C.POINTER(C.c_int32), c_double_p, c_double_p, C.c_int, C.c_int,
                                C.c_void_p]
@@ -297,6 +299,10 @@ class Context(object):
             raise HipEngineError("sl_ctx_create failed: %s" % self.lib.sl_last_error(None).decode())
         self.handle = handle
         self._keepalive = {}        # slot -> the device table the engine currently points at
+        # SL_GP4_EARLY=0 (A/B runs, the bit-identity tests): k_gp_sweep4 runs every variance panel of
+        # every tile.  Read here, once per context; `roofline.kernel` / last_kernel() name what ran.
+        if os.environ.get("SL_GP4_EARLY") == "0":
+            self.check(self.lib.sl_gp4_early_configure(self.handle, 0), "sl_gp4_early_configure")
 
     def close(self):
         if getattr(self, "handle", None):

@@ -143,8 +143,11 @@ def headline_case(num_points=128, n_gp=1024, family='cartpole', stack=False, var
     spacings / 2), because with 8d's literal values (and the full tau) no cell passes the decrease
     check, which would make mask parity vacuous: measured on the 128^4 grid, 8d's values give 1
     passing cell of 2.7e8 and a safe set equal to the initial set; this workload has 8.5e7 passing
-    cells and a level set that grows by 1.3e4 cells.  The cost of a sweep does not depend on the
-    hyper-parameters (the kernel has no early exit)."""
+    cells and a level set that grows by 1.3e4 cells.  The RESULT of a sweep does not depend on how
+    the kernel gets there, its cost does: ``k_gp_sweep4`` computes the posterior mean of a 64-cell
+    tile first and stops adding variance panels once bounds of the decrease settle every cell of the
+    tile, so the hyper-parameters decide how much of the variance work is executed
+    (``informed``: about a third; ``survey``, whose cells fail BECAUSE of the uncertainty: most of it)."""
     hyper = GP_VARIANTS[HEADLINE_GP if variant is None else variant]
     return make_case(family, num_points=num_points, n_gp=n_gp, stack=stack,
                      tau_scale=HEADLINE_TAU_SCALE, **hyper)

@@ -19,6 +19,7 @@
 struct SlGpHeadHost {
     bool set = false;
     int n = 0, n_pad = 0, p = 0, dout = 0, col0 = 0, cfg = 0;
+    double linv00 = 0.0;                          // Linv[0][0] = 1 / sqrt(k(x_0, x_0) + sigma_n^2)
     double lengthscales[SL_MAX_INPUT_DIM] = {};   // as uploaded: appended points are scaled by the
                                                   // same division as the packed ones (bit-identical)
     double* d_xs = nullptr;
@@ -95,6 +96,7 @@ struct sl_ctx {
     void* d_scratch = nullptr;         // grown on demand (sl_eval_points)
     size_t scratch_bytes = 0;
     double* d_gp4_seeds = nullptr;     // k_gp_sweep4: seeds of the k_x sequences, per workgroup
+    bool gp4_early = true;             // k_gp_sweep4 may decide tiles early (sl_gp4_early_configure)
     size_t gp4_seed_bytes = 0;
     void* d_records = nullptr;         // GP posterior records of the two-pass network check
     size_t records_bytes = 0;

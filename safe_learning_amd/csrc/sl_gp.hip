@@ -452,6 +452,7 @@ static int gp_set_head(sl_ctx* ctx, int head, int n, int p, int dout, int col0, 
     SL_HIP_CHECK(ctx, hipMemcpy(hh.d_mpack, mpack.data(), mpack.size() * sizeof(double), hipMemcpyHostToDevice));
     SL_HIP_CHECK(ctx, hipMemcpy(hh.d_alpha, alphap.data(), alphap.size() * sizeof(double), hipMemcpyHostToDevice));
     hh.set = true; hh.n = n; hh.n_pad = n_pad; hh.p = p; hh.dout = dout; hh.col0 = col0; hh.cfg = cfg;
+    hh.linv00 = h_Linv[0];
 
     SlGpHeadDev& dv = ctx->h_gp.head[head];
     memset(&dv, 0, sizeof(dv));
@@ -563,6 +564,12 @@ extern "C" int sl_debug_gp_inputs(sl_ctx* ctx, int head, double* h_xs) {
     for (int q = 0; q < hh.p; ++q)
         SL_HIP_CHECK(ctx, hipMemcpy(h_xs + (size_t)q * hh.n, hh.d_xs + (size_t)q * hh.n_pad,
                                     sizeof(double) * hh.n, hipMemcpyDeviceToHost));
+    return SL_OK;
+}
+
+extern "C" int sl_gp4_early_configure(sl_ctx* ctx, int enable) {
+    if (!ctx) return sl_fail(nullptr, SL_ERR_INVALID, "sl_gp4_early_configure: NULL context");
+    ctx->gp4_early = enable != 0;
     return SL_OK;
 }
 

@@ -407,17 +407,27 @@ __device__ __forceinline__ double uniform(double v) {
 
 }  // namespace gp4
 
+#ifdef SL_DIAG
+// development builds: tiles decided before panel 0 .. 3 ([0..3]) and tiles asked but left open ([7],
+// once per question) - printed and cleared by launch4 when SL_GP4_SKIP has bit 16 (which skips nothing)
+static __device__ unsigned long long sl_gp4_stage_count[8];
+#endif
+
 // (The scaled training inputs and alpha' are read from L2 through buffer resources: two workgroups
 // per CU leave no LDS for them beside the k_x buffers.)
-template <int DT, int MT>
+// EARLY: tiles may be decided from bounds of the decrease (see try_decide); its own instantiation,
+// so that the plain path (EARLY = false: records, several heads, switched off) stays the code it was.
+template <int DT, int MT, bool EARLY>
 __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
     const SlDevModel M, const SlGpDev gp, SlAux aux, int64_t lo, int64_t hi, int64_t ntiles,
     const uint64_t* __restrict__ init_bits, const double* __restrict__ values,
     uint64_t* __restrict__ neg_bits, sl_key* __restrict__ partials, double* __restrict__ dbg,
     const double* __restrict__ points, int skip_arg, double* __restrict__ seeds, int seed_chunks,
     unsigned long long* __restrict__ ticket) {
+    constexpr bool early = EARLY;
     // skip (SL_GP4_SKIP; development builds, -DSL_DIAG, only): 1 no k_x generation, 2 no mean pass,
-    // 4 no per-cell check, 8 no MFMA chunks - timing attribution, the results are then meaningless.
+    // 4 no per-cell check, 8 no MFMA chunks - timing attribution, the results are then meaningless;
+    // 16 skips nothing: the host prints how many tiles were decided before each panel.
     // The shipped kernel has no such switch: the tests fold to constants.
 #ifdef SL_DIAG
     const int skip = skip_arg;
@@ -438,6 +448,7 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
     uint64_t* sv = reinterpret_cast<uint64_t*>(runc + W * RUNS * RUNC);   // [W]
     int64_t* si = reinterpret_cast<int64_t*>(sv + W);                  // [W]
     int64_t* next_tile = si + W;                                       // the tile the workgroup drew
+    uint64_t* tile_decided = reinterpret_cast<uint64_t*>(next_tile + 1);   // wavefront 0 to the others
 
     const SlDims nd = sl_dims<DT, MT>(M);
     const int d = nd.d, p = nd.p;
@@ -489,6 +500,17 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
             __syncthreads();                       // everybody has read next_tile
             continue;
         }
+
+        // mask word and failing-cell key of the tile (wavefront 0, lane = cell)
+        auto finish_tile = [&](bool negative, bool valid, double v_x, int64_t idx) {
+            const uint64_t word = __ballot(negative);
+            uint64_t init = 0ull;
+            if (init_bits) init = init_bits[(tile_base - lo) >> 6];
+            if (lane == 0) neg_bits[(tile_base - lo) >> 6] = word;
+            const bool okc = negative || ((init >> lane) & 1ull);
+            if (valid && !okc) sl_key_min(best_v, best_i, sl_vbits(v_x), idx);
+        };
+        bool decided = false;                      // (early only) the bounds settled all 64 cells
 
         for (int h = 0; h < gp.nheads; ++h) {
             const SlGpHeadDev& hd = gp.head[h];
@@ -783,7 +805,80 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
             // panels that hold training points (the upload pads to the 16x16x4 fallback's 512 rows:
             // a panel of zero rows contributes nothing - 600 points are three panels, not four)
             const int npanels = (hd.n + RP - 1) / RP;
-            for (int pan = 0; pan < npanels; ++pan) {
+            constexpr int CPP = RP / 64;                         // chunks per panel (its diagonal band)
+            const int nchunks_head = npanels * CPP;
+            // Early decision (one head, no records: decided on the host, template parameter EARLY).
+            // The mask bit is decrease < threshold with decrease = (V(mu) - V(x)) + sum_j lv_j(mu) err_j,
+            // lv >= 0, err = beta sqrt(variance - |a|^2): monotone in err, and |a|^2 only grows as
+            // the panels add their rows.  With the mean mu complete, err = 0 bounds the decrease from
+            // below (a cell that fails with it fails) and err_hi = beta sqrt(variance - partial |a|^2)
+            // from above (a cell that passes with it passes); every operation between |a|^2 and the
+            // comparison rounds monotonically, so a bit both bounds agree on is the bit of the full
+            // sum.  A tile whose 64 cells are all decided needs no further panel.
+            // try_decide: every wavefront calls it (two barriers); wavefront 0 evaluates both bounds
+            // for its 64 cells, writes word and key if they agree everywhere, and tells the others.
+            auto try_decide = [&](int stage, bool have_ss) -> bool {
+                __syncthreads();                   // cell_mean (and part_ss) of every wavefront
+                if (wave == 0) {
+                    const int64_t idx = tile_base + lane;
+                    const bool valid = idx < hi;
+                    bool neg_hi = false, open = false;
+                    double v_x = 0.0;
+                    if (valid) {
+                        double x[SL_P], u[SL_M], prior[SL_D], mean[SL_D], err0[SL_D], err1[SL_D];
+                        sl_cell_state(M, d, idx, points, x);
+                        sl_policy_any<false>(M, nd, aux.tri, idx, x, u);
+                        sl_append_action(nd, u, x);
+                        sl_rows_dot<SL_D, SL_P>(M.m.dynamics.matrix, d, p, x, prior);
+                        double var = variance;
+                        if (have_ss) {
+                            double sumsq = 0.0;
+                            for (int k = 0; k < PSS; ++k) sumsq += part_ss[k * C + lane];
+                            var = variance - sumsq;
+                        }
+                        const double e = gp.beta * sqrt(var);
+#pragma unroll
+                        for (int k = 0; k < SL_D; ++k) {
+                            if (k < d) {
+                                mean[k] = cell_mean[lane * SL_D + k] + prior[k];
+                                err0[k] = 0.0;
+                                err1[k] = e;
+                            }
+                        }
+                        const SlCellCheck c0 = sl_cell_check<SL_FAST>(M, d, aux, x, mean, err0);
+                        const SlCellCheck c1 = sl_cell_check<SL_FAST>(M, d, aux, x, mean, err1);
+                        neg_hi = c1.negative;
+                        // (a non-finite mean or err_hi leaves the cell, and so the tile, undecided)
+                        open = c0.negative != c1.negative || !(fabs(c0.decrease) < INFINITY) ||
+                               !(fabs(c1.decrease) < INFINITY);
+                        v_x = values ? values[idx - lo] : c1.v_x;
+                    }
+                    const bool all = __ballot(open) == 0ull;
+                    if (all) finish_tile(neg_hi, valid, v_x, idx);
+                    if (lane == 0) {
+                        *tile_decided = all ? 1ull : 0ull;
+#ifdef SL_DIAG
+                        atomicAdd(&sl_gp4_stage_count[all ? stage : 7], 1ull);
+#endif
+                    }
+                }
+                (void)stage;
+                __syncthreads();
+                return __builtin_amdgcn_readfirstlane((int)*tile_decided) != 0;
+            };
+            if (early) {
+                // The mean first: every chunk once, without the factor (a wavefront's mean_run reads
+                // the k_x values it has just written itself - no workgroup barrier between chunks),
+                // in the order and through the accumulators of the interleaved pass: the same bits.
+                // The seeds are stored as the first generation stores them; every generation of
+                // the panels below is then a re-generation (no chunk is new to them).
+                for (int ch = 0; ch < nchunks_head; ++ch) produce(ch, ch & 1, 0, true);
+                if (lk < dout)
+                    cell_mean[(16 * wave + 4 * blk + low) * SL_D + hd.col0 + lk] =
+                        (macc[0] + macc[1]) + (macc[2] + macc[3]);
+                decided = try_decide(0, false);
+            }
+            for (int pan = decided ? npanels : 0; pan < npanels; ++pan) {
                 acc_zero_all();
                 int rowoff[R];                     // byte offset of each owned row block's fragments
                 int nzd[R];                        // slab pairs of its diagonal chunk that are not zero
@@ -793,9 +888,8 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
                     rowoff[r] = (pan * RB + r * W + wsel) * hd.nslab2 * 1024;
                     nzd[r] = 2 * wsel + 2;
                 }
-                constexpr int CPP = RP / 64;                     // chunks per panel (its diagonal band)
                 const int nchunks = (pan + 1) * CPP;
-                const int first_new_chunk = pan * (RP / 64);     // chunks not generated before
+                const int first_new_chunk = early ? INT_MAX : pan * CPP;   // chunks not generated before (EARLY: none)
                 const bool keep = pan + 1 < npanels;
                 produce(0, 0, first_new_chunk, keep);
                 __syncthreads();
@@ -843,8 +937,14 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
                         __builtin_amdgcn_wave_barrier();
                     }
                 }
+                // the rows so far may already decide the tile (the last panel ends in the epilogue)
+                if (early && pan + 1 < npanels) {
+                    decided = try_decide(pan + 1, true);
+                    if (decided) break;
+                }
             }
-            if (lk < dout)
+            if (decided) break;
+            if (!early && lk < dout)
                 cell_mean[(16 * wave + 4 * blk + low) * SL_D + hd.col0 + lk] =
                     (macc[0] + macc[1]) + (macc[2] + macc[3]);
             __syncthreads();
@@ -858,6 +958,7 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
             __syncthreads();
         }
 
+        if (decided) continue;                     // wavefront 0 wrote the word and folded the key
         // ---- per-cell decrease check, mask word, failing-cell key (as k_gp_sweep) -------------------
         const int64_t idx = tile_base + tid;
         const bool valid = (tid < C) && (idx < hi);
@@ -886,14 +987,7 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
                 for (int k = 0; k < SL_D; ++k) if (k < d) { o[2 + k] = mean[k]; o[2 + d + k] = err[k]; }
             }
         }
-        if (wave == 0) {
-            const uint64_t word = __ballot(negative);
-            uint64_t init = 0ull;
-            if (init_bits) init = init_bits[(tile_base - lo) >> 6];
-            if (lane == 0) neg_bits[(tile_base - lo) >> 6] = word;
-            const bool okc = negative || ((init >> lane) & 1ull);
-            if (valid && !okc) sl_key_min(best_v, best_i, sl_vbits(v_x), idx);
-        }
+        if (wave == 0) finish_tile(negative, valid, v_x, idx);
         // (cell_mean / cell_err / cin are rewritten only after the next tile's barriers)
     }
     __syncthreads();
@@ -907,7 +1001,34 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
 static size_t gp4_fixed_lds() {
     return sizeof(double) * (2 * gp4::KXBUF + gp4::W * gp4::C +
                              2 * gp4::C * SL_D + gp4::C * SL_P + gp4::W * gp4::RUNS * gp4::RUNC) +
-           (2 * gp4::W + 2) * sizeof(uint64_t);
+           (2 * gp4::W + 4) * sizeof(uint64_t);
+}
+
+// May tiles be decided from bounds of the decrease (the kernel's try_decide)?  Conditions, not
+// measurements:
+//  * one GP head that fills every output column, no record output, no forced configuration
+//    (SL_GP_CFG), not switched off (sl_gp4_early_configure);
+//  * decrease is monotone in err: beta >= 0 and L_v >= 0.  The |.| kinds of L_v are; SL_LIP_CONST
+//    takes the caller's constant as it is, so a negative or non-finite one switches this off;
+//  * variance - |a|^2 of the FULL sum stays positive (a negative one makes err NaN and the cell
+//    "not negative" in the full sweep, which an early "passes" would contradict).  The posterior
+//    variance of n points with noise sigma_n^2 is at least v_min = 1 / (1 / s^2 + n / sigma_n^2)
+//    (all n points on the cell itself), the rounding of |a|^2 is of the order n 2^-53 s^2:
+//    required v_min >= 64 n 2^-53 s^2.  sigma_n^2 = 1 / Linv[0][0]^2 - s^2 (the first pivot of
+//    the Cholesky factor of K + sigma_n^2 I with k(x, x) = s^2).
+static bool gp4_early_ok(const sl_ctx* ctx, const SlDevModel& model, const double* d_dbg) {
+    if (!ctx->gp4_early || ctx->env.gp_cfg >= 0 || d_dbg || ctx->h_gp.nheads != 1) return false;
+    const SlGpHeadHost& hh = ctx->gp_heads[0];
+    if (hh.col0 != 0 || hh.dout != model.m.grid.d || !model.uncertain) return false;
+    const double beta = ctx->h_gp.beta;
+    if (!(beta >= 0.0) || !(beta < INFINITY)) return false;
+    const sl_lipschitz_desc& l = model.m.lipschitz;
+    if (l.lv_kind == SL_LIP_CONST && (!(l.lv_const >= 0.0) || !(l.lv_const < INFINITY))) return false;
+    const double s2 = ctx->h_gp.head[0].variance;
+    const double noise = 1.0 / (hh.linv00 * hh.linv00) - s2;
+    if (!(noise > 0.0) || !(noise < INFINITY)) return false;
+    const double v_min = 1.0 / (1.0 / s2 + (double)hh.n / noise);
+    return v_min >= 64.0 * (double)hh.n * 0x1p-53 * s2;
 }
 
 template <int DT, int MT>
@@ -926,9 +1047,10 @@ static int launch4(sl_ctx* ctx, const SlDevModel& model, int64_t lo, int64_t hi,
     }
     const size_t lds = gp4_fixed_lds();                       // two workgroups per CU: < 80 KB each
     static_assert(sizeof(double) * (2 * gp4::KXBUF + gp4::W * gp4::C + 2 * gp4::C * SL_D + gp4::C * SL_P +
-                                    gp4::W * gp4::RUNS * gp4::RUNC) + (2 * gp4::W + 2) * sizeof(uint64_t)
+                                    gp4::W * gp4::RUNS * gp4::RUNC) + (2 * gp4::W + 4) * sizeof(uint64_t)
                       <= 80 * 1024, "two workgroups of k_gp_sweep4 per CU");
-    auto kern = k_gp_sweep4<DT, MT>;
+    const bool early = gp4_early_ok(ctx, model, d_dbg);
+    auto kern = early ? k_gp_sweep4<DT, MT, true> : k_gp_sweep4<DT, MT, false>;
     SL_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const int64_t resident = (int64_t)ctx->num_cu * 2;
@@ -956,8 +1078,19 @@ static int launch4(sl_ctx* ctx, const SlDevModel& model, int64_t lo, int64_t hi,
                        ctx->h_gp, aux, lo, hi, ntiles, d_init_bits, d_values, d_neg_bits,
                        ctx->d_partials, d_dbg, d_points, skip, seeds, seed_chunks, ticket);
     SL_HIP_CHECK(ctx, hipGetLastError());
-    sl_note_kernel(ctx, false, "k_gp_sweep4<d=%d, m=%d> (%d-row panels, %d workgroup(s) per CU)",
-                   DT, MT, gp4::RP, 2);
+#ifdef SL_DIAG
+    if (skip & 16) {
+        unsigned long long c[8];
+        SL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        SL_HIP_CHECK(ctx, hipMemcpyFromSymbol(c, HIP_SYMBOL(sl_gp4_stage_count), sizeof(c)));
+        fprintf(stderr, "k_gp_sweep4 stages: tiles %lld decided before panel 0/1/2/3: %llu %llu %llu %llu "
+                        "(questions left open: %llu)\n", (long long)ntiles, c[0], c[1], c[2], c[3], c[7]);
+        memset(c, 0, sizeof(c));
+        SL_HIP_CHECK(ctx, hipMemcpyToSymbol(HIP_SYMBOL(sl_gp4_stage_count), c, sizeof(c)));
+    }
+#endif
+    sl_note_kernel(ctx, false, "k_gp_sweep4<d=%d, m=%d> (%d-row panels, %d workgroup(s) per CU%s)",
+                   DT, MT, gp4::RP, 2, early ? ", early decision" : "");
     return SL_OK;
 }
 

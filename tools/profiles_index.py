@@ -1,7 +1,8 @@
 """Regenerate profiles/README.md: one row per shipped kernel (source file, the configuration that
 measures it, ms, fraction of its roof, the counter / A-B files behind the number) and a list of what
 else is in profiles/.  Reads profiles/r06_configs.jsonl (tools/bench_configs.sh), the headline line
-profiles/r06_bench_driver_command.log, profiles/pmc_traffic.json and profiles/pmc_valu.json.
+profiles/r06_bench_driver_command.log and profiles/early_bench_headline.jsonl, profiles/pmc_traffic.json and
+profiles/pmc_valu.json.
 
     python tools/profiles_index.py"""
 import json
@@ -12,7 +13,8 @@ P = os.path.join(ROOT, "profiles")
 
 # kernel -> (source, configuration that measures it, files with the evidence)
 KERNELS = [
-    ("k_gp_sweep4", "csrc/sl_gp4.hip", "C4", "r06_kernel_stats.md, r06_pmc_48.txt, r06_pmc_128.txt, r05_pmc_l2_64.txt, pmc_traffic.json; "
+    ("k_gp_sweep4", "csrc/sl_gp4.hip", "C4", "early_ab_headline.jsonl (parent / early / plain, interleaved on one box), early_kernel_stats.md, early_pmc_48.txt, early_pmc_128.txt, "
+     "early_stage_counts.txt, early_ab_other_lines.jsonl, early_dump_outputs.txt, early_little_skipped.txt; the plain instantiation (every panel of every tile): r06_kernel_stats.md, r06_pmc_48.txt, r06_pmc_128.txt, r05_pmc_l2_64.txt, pmc_traffic.json; "
      "A/B: dropped/r06_gp4_alias_ab.txt (phases; every factor read an L2 hit: -1 %), dropped/r06_gp4_seeds_nontemporal_ab.txt, dropped/r06_gp4_seed_latency_ab.txt, r05_gp4_diag_ab.txt"),
     ("k_gp_sweep4 (n = 512, 1024 tiles)", "csrc/sl_gp4.hip", "C2", "r06_C2_kernel_stats.md, r05_C2_ab.txt; dropped/r06_gp4_stagger_ab.txt (tile-count series at 512 points)"),
     ("k_gp_sweep4 + k_nn_check_mfma", "csrc/sl_gp4.hip, csrc/sl_nn.hip", "C3", "r06_C3_kernel_stats.md, r04_C3_kernel_stats.md; r06_box_variance_ab.txt (270.5 ms on another box, "
@@ -48,6 +50,7 @@ def load_lines(name):
 def main():
     lines = load_lines("r06_configs.jsonl")
     lines.update(load_lines("r06_bench_driver_command.log"))
+    lines.update(load_lines("early_bench_headline.jsonl"))      # the headline with the early tile decision
     try:
         valu = json.load(open(os.path.join(P, "pmc_valu.json")))
     except (OSError, ValueError):
@@ -75,11 +78,13 @@ def main():
         by_round.setdefault(key, []).append(name)
     text = ["# profiles/ — index", "",
             "Generated by `tools/profiles_index.py` from `r06_configs.jsonl` (one `bench.py` line per configuration,",
-            "`tools/bench_configs.sh`), `r06_bench_driver_command.log` (the headline command), `pmc_traffic.json` and",
+            "`tools/bench_configs.sh`), `r06_bench_driver_command.log` / `early_bench_headline.jsonl` (the headline command), `pmc_traffic.json` and",
             "`pmc_valu.json` (counter passes of `tools/profile_r06.sh`, tied to the kernel sources by sha256).",
             "One MI355X.  `roof`: `mfma` = 78.6 TFLOP/s FP64 matrix pipe (algorithmic flops, SURVEY 8d), `hbm` = 8 TB/s,",
             "`valu` = share of the SIMDs' cycles that issue a vector-ALU instruction (in brackets: the byte or",
-            "matrix-pipe fraction bench.py printed before round 5).", ""] + rows + [""]
+            "matrix-pipe fraction bench.py printed before round 5).  The headline's `mfma` fraction counts the algorithmic",
+            "flops of ALL cells while `k_gp_sweep4` skips the variance panels its bounds decide: an effective rate",
+            "(matrix pipe busy 0.687 of the SIMD-cycles, `early_pmc_128.txt`; DESIGN.md 5).", ""] + rows + [""]
     if valu:
         text += ["## Vector-ALU issue utilisation (`pmc_valu.json`)", "",
                  "| entry | kernel | issue utilisation | FP64 share of the vector instructions | matrix pipe busy | wave-cycles waiting |",
@@ -98,6 +103,8 @@ def main():
              "* `rNN_pytest_gpu*.log`, `rNN_smoke.log`: GPU test logs; `rNN_parity_exclusions.json`: what the table-lookup parity tests "
              "left out / membership-checked (`tests/exclusions.py`).",
              "* `r05_rocprofv3_memory_counters.txt`: every memory-side counter this rocprofv3 offers (there is none behind the fabric).",
+             "* `early_*`: the early tile decision of `k_gp_sweep4` against its parent commit, everything from one visit of one box "
+             "(DESIGN.md 4.1 \"Early tile decision\").",
              "* `r06_shard_balance.md`: the N = 2 / 4 / 8 shards of C4 and C5 timed one by one on one GPU (`tools/shard_balance.py`).",
              "* `r06_parity_report.md`: what the parity claims rest on, what is a definition, what is unpinned.",
              "* `r06_box_variance_ab.txt`: the round-5 library and the tree alternating on ONE box (C3, C4-lin, C4-det): boxes of the pool "
