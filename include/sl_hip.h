@@ -278,22 +278,7 @@ SL_API int  sl_lyap_sweep(sl_ctx* ctx, int64_t lo, int64_t hi, const uint64_t* d
                    const double* d_values, uint64_t* d_neg_bits, sl_sweep_result* d_result,
                    double* d_dbg);
 
-/* safe_i = init_i | (key_i < key_star) | (prev_i & key_i >= key_keep), the parallel form of
- * lyapunov.py:513-606.  d_prev_bits may be NULL.  Fills last_safe, max_key,
- * count_below, count_safe of d_result. */
-SL_API int  sl_lyap_finalize(sl_ctx* ctx, int64_t lo, int64_t hi, const double* d_values,
-                      const uint64_t* d_init_bits, const uint64_t* d_prev_bits,
-                      sl_key key_star, sl_key key_keep, uint64_t* d_safe_bits,
-                      sl_sweep_result* d_result);
-
-/* One radix-select pass over the (V, index) keys of [lo,hi): 256-bin histogram of byte
- * `byte` (7 = most significant) of the vbits (which = 0) or of the index (which = 1, only cells
- * with vbits == prefix) among keys whose higher bytes equal `prefix`'s.  d_hist[256] is ADDED to
- * (zero it first).  Gives the k-th order statistic that lyapunov.py:590-595 reads through argsort. */
-SL_API int  sl_select_pass(sl_ctx* ctx, int64_t lo, int64_t hi, const double* d_values, int which,
-                    int byte, uint64_t prefix, uint64_t vbits_equal, uint64_t* d_hist);
-
-/* ---- the same rule with every decision read from DEVICE memory (no host round trip between the
+/* ---- the level set: every decision is read from DEVICE memory (no host round trip between the
  * passes of one update_safe_set; the multi-GPU path of SURVEY.md 8e) ------------------------------ */
 
 /* *out = 1 when d_values may be NULL in sl_lyap_sweep AND in the three passes below: V is a
@@ -311,9 +296,11 @@ SL_API int  sl_values_implicit(sl_ctx* ctx, int* out);
 SL_API int  sl_fold_results(sl_ctx* ctx, const sl_sweep_result* d_records, int count,
                      sl_sweep_result* d_out);
 
-/* sl_lyap_finalize with key_star = d_folded->fail and key_keep = *d_keep (NULL: none) read by the
- * kernel.  d_values may be NULL (sl_values_implicit).  d_result: ->fail is copied from d_folded,
- * the other fields are this range's statistics (fold them across ranks with sl_fold_results). */
+/* safe_i = init_i | (key_i < key_star) | (prev_i & key_i >= key_keep), the parallel form of
+ * lyapunov.py:513-606, with key_star = d_folded->fail and key_keep = *d_keep (NULL:
+ * none) read by the kernel.  d_init_bits and d_prev_bits may be NULL, d_values too
+ * (sl_values_implicit).  d_result: ->fail is copied from d_folded; last_safe, max_key, count_below
+ * and count_safe are this range's statistics (fold them across ranks with sl_fold_results). */
 SL_API int  sl_lyap_finalize_dev(sl_ctx* ctx, int64_t lo, int64_t hi, const double* d_values,
                           const uint64_t* d_init_bits, const uint64_t* d_prev_bits,
                           const sl_sweep_result* d_folded, const sl_key* d_keep,
@@ -344,9 +331,13 @@ typedef struct sl_select_state {
  * their previous state).  n_total = cells of the whole grid. */
 SL_API int  sl_select_begin(sl_ctx* ctx, sl_select_state* d_state, int64_t k, int64_t batch,
                      const sl_sweep_result* d_folded, int64_t n_total);
-/* Histogram of one byte (7 = most significant first) of the keys of [lo,hi) that match the state's
- * prefix: which = 0 the vbits, which = 1 the index among cells with vbits == state->key.vbits.
- * d_hist[256] is zeroed and filled; SUM it over the ranks, then call sl_select_digit. */
+/* One radix-select pass over the (V, index) keys of [lo,hi): the 256-bin histogram of byte `byte`
+ * (7 = most significant, taken first) of the vbits (which = 0) or of the index (which = 1, only cells
+ * with vbits == state->key.vbits), among the keys whose higher bytes equal the state's prefix.
+ * d_values may be NULL (sl_values_implicit).  d_hist[256] is zeroed and filled, not added to: SUM it
+ * over the ranks, then call sl_select_digit, which takes the digit that holds the rank into the
+ * prefix.  Eight passes of which = 0, then eight of which = 1, give the k-th order statistic that
+ * lyapunov.py:590-595 reads through argsort. */
 SL_API int  sl_select_hist(sl_ctx* ctx, int64_t lo, int64_t hi, const double* d_values, int which,
                     int byte, const sl_select_state* d_state, uint64_t* d_hist);
 SL_API int  sl_select_digit(sl_ctx* ctx, int which, int byte, const uint64_t* d_hist,
@@ -549,12 +540,12 @@ SL_API int  sl_eval_points(sl_ctx* ctx, int what, int64_t n, const double* d_poi
  * call is asynchronous on the context's stream.  RCCL is bound at run time: on a system without
  * librccl.so the calls return SL_ERR_UNSUPPORTED.
  *   sl_comm_unique_id: rank 0 creates the 128-byte id and hands it to the other ranks out of band.
- *   sl_allreduce_result: the per-shard record of sl_lyap_sweep / sl_lyap_finalize becomes the record
+ *   sl_allreduce_result: the per-shard record of sl_lyap_sweep / sl_lyap_finalize_dev becomes the record
  *     of the whole grid IN PLACE: lexicographic min of `fail`, lexicographic max of `last_safe`
  *     and `max_key`, sums of the counters (the reductions of lyapunov.py:512-606 over shards).
  *   sl_allgather: value-table shards of equal size after a Bellman sweep
  *     (reinforcement_learning.py:135-140); sl_allreduce_max_f64: its residual;
- *   sl_allreduce_sum_u64: the radix-select histograms of sl_select_pass.                        */
+ *   sl_allreduce_sum_u64: the radix-select histograms of sl_select_hist.                        */
 #define SL_COMM_ID_BYTES 128
 SL_API int  sl_comm_unique_id(unsigned char* id_out /* [SL_COMM_ID_BYTES] */);
 SL_API int  sl_comm_init(sl_ctx* ctx, const unsigned char* id /* [SL_COMM_ID_BYTES] */, int rank, int world);

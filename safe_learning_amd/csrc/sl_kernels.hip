@@ -1,7 +1,7 @@
 // sl_kernels.hip - context, model upload and the streaming (HBM-bound) passes of the Lyapunov
-// sweep for gfx950: values, deterministic-dynamics decrease check, safe-set finalisation,
-// radix-select histogram, bit/byte mask conversion.  The GP (MFMA) sweep lives in sl_gp.hip,
-// the dynamic-programming sweep in sl_bellman.hip.
+// sweep for gfx950: values, deterministic-dynamics decrease check, bit/byte mask conversion.
+// The GP (MFMA) sweep lives in sl_gp.hip, safe-set finalisation and the radix-select histogram in
+// sl_level.hip, the dynamic-programming sweep in sl_bellman.hip.
 //
 // Launch geometry: 256-thread workgroups (4 wavefronts of 64), a grid capped at 2048 blocks
 // (= 8 per CU) that walks the cell range in 256-cell strides, so consecutive lanes own
@@ -926,156 +926,6 @@ extern "C" int sl_lyap_sweep(sl_ctx* ctx, int64_t lo, int64_t hi, const uint64_t
                              const double* d_values, uint64_t* d_neg_bits,
                              sl_sweep_result* d_result, double* d_dbg) {
     return sl_sweep_any(ctx, {lo, hi, d_init_bits, d_values, d_neg_bits, d_dbg, nullptr}, d_result, true);
-}
-
-// =============================================================================================
-// finalisation: the prefix rule of lyapunov.py:513-606 in parallel form
-// =============================================================================================
-__global__ __launch_bounds__(SL_BLOCK) void k_finalize(
-    int64_t lo, int64_t hi, const double* __restrict__ values,
-    const uint64_t* __restrict__ init_bits, const uint64_t* __restrict__ prev_bits, sl_key star,
-    sl_key keep, uint64_t* __restrict__ safe_bits, sl_key* __restrict__ partials,
-    int64_t* __restrict__ counts) {
-    __shared__ uint64_t sv[SL_BLOCK / 64];
-    __shared__ int64_t si[SL_BLOCK / 64];
-    __shared__ int64_t sc[2][SL_BLOCK / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint64_t ls_v = 0ull, mx_v = 0ull;
-    int64_t ls_i = -1, mx_i = -1;
-    int64_t n_below = 0, n_safe = 0;
-    for (int64_t base = lo + (int64_t)blockIdx.x * SL_BLOCK; base < hi;
-         base += (int64_t)gridDim.x * SL_BLOCK) {
-        const int64_t idx = base + threadIdx.x;
-        const bool valid = idx < hi;
-        const int64_t wbase = base + (threadIdx.x & ~63);
-        bool safe = false;
-        if (wbase < hi) {
-            const int64_t widx = (wbase - lo) >> 6;
-            const uint64_t init = init_bits ? init_bits[widx] : 0ull;
-            const uint64_t prev = prev_bits ? prev_bits[widx] : 0ull;
-            if (valid) {
-                const uint64_t vb = sl_vbits(values[idx - lo]);
-                const bool below = sl_key_less(vb, idx, star.vbits, star.index);
-                const bool kept = ((prev >> lane) & 1ull) && !sl_key_less(vb, idx, keep.vbits, keep.index);
-                safe = below || kept || ((init >> lane) & 1ull);
-                if (below) { ++n_below; sl_key_max(ls_v, ls_i, vb, idx); }
-                sl_key_max(mx_v, mx_i, vb, idx);
-            }
-            const uint64_t word = __ballot(safe);
-            if (lane == 0) { safe_bits[widx] = word; n_safe += __popcll(word); }
-        }
-    }
-    // block reductions
-    for (int off = 32; off >= 1; off >>= 1) {
-        n_below += __shfl_xor((long long)n_below, off, 64);
-        n_safe += __shfl_xor((long long)n_safe, off, 64);
-    }
-    if (lane == 0) { sc[0][wave] = n_below; sc[1][wave] = n_safe; }
-    sl_block_reduce_key<false>(ls_v, ls_i, sv, si);
-    __syncthreads();
-    sl_block_reduce_key<false>(mx_v, mx_i, sv, si);
-    if (threadIdx.x == 0) {
-        partials[2 * blockIdx.x].vbits = ls_v; partials[2 * blockIdx.x].index = ls_i;
-        partials[2 * blockIdx.x + 1].vbits = mx_v; partials[2 * blockIdx.x + 1].index = mx_i;
-        int64_t a = 0, b = 0;
-        for (int w = 0; w < SL_BLOCK / 64; ++w) { a += sc[0][w]; b += sc[1][w]; }
-        counts[2 * blockIdx.x] = a; counts[2 * blockIdx.x + 1] = b;
-    }
-}
-
-__global__ __launch_bounds__(SL_BLOCK) void k_reduce_finalize(const sl_key* __restrict__ partials,
-                                                              const int64_t* __restrict__ counts,
-                                                              int n, sl_sweep_result* result) {
-    __shared__ uint64_t sv[SL_BLOCK / 64];
-    __shared__ int64_t si[SL_BLOCK / 64];
-    __shared__ int64_t sc[2][SL_BLOCK / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint64_t ls_v = 0ull, mx_v = 0ull;
-    int64_t ls_i = -1, mx_i = -1, a = 0, b = 0;
-    for (int k = threadIdx.x; k < n; k += SL_BLOCK) {
-        sl_key_max(ls_v, ls_i, partials[2 * k].vbits, partials[2 * k].index);
-        sl_key_max(mx_v, mx_i, partials[2 * k + 1].vbits, partials[2 * k + 1].index);
-        a += counts[2 * k]; b += counts[2 * k + 1];
-    }
-    for (int off = 32; off >= 1; off >>= 1) {
-        a += __shfl_xor((long long)a, off, 64);
-        b += __shfl_xor((long long)b, off, 64);
-    }
-    if (lane == 0) { sc[0][wave] = a; sc[1][wave] = b; }
-    sl_block_reduce_key<false>(ls_v, ls_i, sv, si);
-    __syncthreads();
-    sl_block_reduce_key<false>(mx_v, mx_i, sv, si);
-    if (threadIdx.x == 0) {
-        result->last_safe.vbits = ls_v; result->last_safe.index = ls_i;
-        result->max_key.vbits = mx_v; result->max_key.index = mx_i;
-        int64_t ta = 0, tb = 0;
-        for (int w = 0; w < SL_BLOCK / 64; ++w) { ta += sc[0][w]; tb += sc[1][w]; }
-        result->count_below = ta; result->count_safe = tb;
-    }
-}
-
-extern "C" int sl_lyap_finalize(sl_ctx* ctx, int64_t lo, int64_t hi, const double* d_values,
-                                const uint64_t* d_init_bits, const uint64_t* d_prev_bits,
-                                sl_key key_star, sl_key key_keep, uint64_t* d_safe_bits,
-                                sl_sweep_result* d_result) {
-    if (!ctx) return sl_fail(nullptr, SL_ERR_INVALID, "sl_lyap_finalize: NULL context");
-    if (lo < 0 || hi < lo || ((lo & 63) && hi != lo) || !d_values || !d_safe_bits || !d_result)
-        return sl_fail(ctx, SL_ERR_INVALID, "sl_lyap_finalize: bad argument");
-    SL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    int blocks = (hi == lo) ? 0 : sl_grid_blocks(hi - lo);
-    if (blocks) {
-        hipLaunchKernelGGL(k_finalize, dim3(blocks), dim3(SL_BLOCK), 0, ctx->stream, lo, hi,
-                           d_values, d_init_bits, d_prev_bits, key_star, key_keep, d_safe_bits,
-                           ctx->d_partials, ctx->d_partial_counts);
-        SL_HIP_CHECK(ctx, hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_reduce_finalize, dim3(1), dim3(SL_BLOCK), 0, ctx->stream, ctx->d_partials,
-                       ctx->d_partial_counts, blocks, d_result);
-    SL_HIP_CHECK(ctx, hipGetLastError());
-    return SL_OK;
-}
-
-// =============================================================================================
-// radix-select histogram pass over (V, index) keys
-// =============================================================================================
-__global__ __launch_bounds__(SL_BLOCK) void k_select_pass(int64_t lo, int64_t hi,
-                                                          const double* __restrict__ values,
-                                                          int which, int byte, uint64_t prefix,
-                                                          uint64_t vbits_equal,
-                                                          uint64_t* __restrict__ hist) {
-    __shared__ unsigned int lh[256];
-    lh[threadIdx.x] = 0;
-    __syncthreads();
-    const int shift = byte * 8;
-    const uint64_t himask = (byte == 7) ? 0ull : (~0ull << (shift + 8));
-    for (int64_t idx = lo + (int64_t)blockIdx.x * SL_BLOCK + threadIdx.x; idx < hi;
-         idx += (int64_t)gridDim.x * SL_BLOCK) {
-        const uint64_t vb = sl_vbits(values[idx - lo]);
-        uint64_t key;
-        bool take;
-        if (which == 0) { key = vb; take = true; }
-        else { key = (uint64_t)idx; take = (vb == vbits_equal); }
-        take = take && ((key & himask) == (prefix & himask));
-        if (take) atomicAdd(&lh[(key >> shift) & 0xff], 1u);
-    }
-    __syncthreads();
-    const unsigned int c = lh[threadIdx.x];
-    if (c) atomicAdd((unsigned long long*)&hist[threadIdx.x], (unsigned long long)c);
-}
-
-extern "C" int sl_select_pass(sl_ctx* ctx, int64_t lo, int64_t hi, const double* d_values,
-                              int which, int byte, uint64_t prefix, uint64_t vbits_equal,
-                              uint64_t* d_hist) {
-    if (!ctx) return sl_fail(nullptr, SL_ERR_INVALID, "sl_select_pass: NULL context");
-    if (lo < 0 || hi < lo || !d_values || !d_hist || byte < 0 || byte > 7 || which < 0 || which > 1)
-        return sl_fail(ctx, SL_ERR_INVALID, "sl_select_pass: bad argument");
-    if (hi == lo) return SL_OK;
-    SL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    // a block must not overflow its 32-bit local counters: <= 2^31 cells per block
-    hipLaunchKernelGGL(k_select_pass, dim3(sl_grid_blocks(hi - lo)), dim3(SL_BLOCK), 0,
-                       ctx->stream, lo, hi, d_values, which, byte, prefix, vbits_equal, d_hist);
-    SL_HIP_CHECK(ctx, hipGetLastError());
-    return SL_OK;
 }
 
 // =============================================================================================

@@ -45,30 +45,138 @@ def test_library_exports_nothing_else():
     assert defined == _declared_symbols(), sorted(set(defined) ^ set(_declared_symbols()))
 
 
+# every ctypes.Structure of _hip.py and the C type it mirrors
+STRUCTS = {"GridDesc": "sl_grid_desc", "PolicyDesc": "sl_policy_desc", "DynamicsDesc": "sl_dynamics_desc",
+           "ValueDesc": "sl_value_desc", "LipschitzDesc": "sl_lipschitz_desc", "ModelDesc": "sl_model_desc",
+           "Key": "sl_key", "GpKernelFactor": "sl_gp_kernel_factor", "GpKernel": "sl_gp_kernel",
+           "SuccessorCacheStats": "sl_successor_cache_stats", "ValueSolveStats": "sl_value_solve_stats"}
+
+
 def test_struct_layout_matches_header():
-    """ctypes mirrors must have the C sizes (compiled check with the host compiler)."""
+    """ctypes mirrors must have the C sizes and field offsets (compiled check with the host compiler)."""
     import subprocess
     import tempfile
-    src = r'''
-    #include <stdio.h>
-    #include "sl_hip.h"
-    int main(void) {
-        printf("%zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(sl_grid_desc), sizeof(sl_policy_desc),
-               sizeof(sl_dynamics_desc), sizeof(sl_value_desc), sizeof(sl_lipschitz_desc),
-               sizeof(sl_model_desc), sizeof(sl_key), sizeof(sl_sweep_result));
-        return 0;
-    }'''
+    mirrors = sorted(name for name, obj in vars(_hip).items()
+                     if isinstance(obj, type) and issubclass(obj, C.Structure) and obj is not C.Structure)
+    assert mirrors == sorted(STRUCTS), "a Structure of _hip.py without its C name in STRUCTS"
+    labels, expected, lines = [], [], []
+    for name, cname in STRUCTS.items():
+        mirror = getattr(_hip, name)
+        labels.append("sizeof(%s)" % cname)
+        expected.append(C.sizeof(mirror))
+        lines.append('printf("%%zu\\n", sizeof(%s));' % cname)
+        for field, _ in mirror._fields_:
+            labels.append("%s.%s" % (cname, field))
+            expected.append(getattr(mirror, field).offset)
+            lines.append('printf("%%zu\\n", offsetof(%s, %s));' % (cname, field))
+    lines.append('printf("%zu\\n", sizeof(sl_sweep_result));')
+    src = ('#include <stddef.h>\n#include <stdio.h>\n#include "sl_hip.h"\nint main(void) {\n%s\nreturn 0;\n}\n'
+           % "\n".join(lines))
     with tempfile.TemporaryDirectory() as tmp:
-        c = os.path.join(tmp, "sizes.c")
+        c = os.path.join(tmp, "layout.c")
         with open(c, "w") as f:
             f.write(src)
-        exe = os.path.join(tmp, "sizes")
+        exe = os.path.join(tmp, "layout")
         subprocess.check_call(["gcc", "-I" + os.path.join(ROOT, "include"), c, "-o", exe])
-        sizes = [int(v) for v in subprocess.check_output([exe]).split()]
-    mirrors = [_hip.GridDesc, _hip.PolicyDesc, _hip.DynamicsDesc, _hip.ValueDesc,
-               _hip.LipschitzDesc, _hip.ModelDesc, _hip.Key]
-    assert sizes[:7] == [C.sizeof(m) for m in mirrors]
-    assert sizes[7] == 8 * _hip.RESULT_WORDS
+        numbers = [int(v) for v in subprocess.check_output([exe]).split()]
+    assert len(numbers) == len(expected) + 1
+    for label, got, want in zip(labels, numbers, expected):
+        assert got == want, "%s: C %d, ctypes %d" % (label, got, want)
+    assert numbers[-1] == 8 * _hip.RESULT_WORDS
+
+
+def _header_prototypes():
+    """{name: (return type, [argument types])} of every ``SL_API`` prototype, as C text without the
+    argument names."""
+    with open(os.path.join(ROOT, "include", "sl_hip.h")) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    out = {}
+    for ret, name, args in re.findall(r"SL_API\s+([\w\s\*]+?)\b(sl_\w+)\s*\(([^)]*)\)\s*;", text):
+        args = [" ".join(a.split()) for a in args.split(",")]
+        if args == ["void"]:
+            args = []
+        out[name] = (" ".join(ret.split()), [re.sub(r"\s*\w+$", "", a) for a in args])   # (without its name)
+    return out
+
+
+def _same_class(ctype, cdecl):
+    """One argument: does the ctypes type pass what the C declaration expects?"""
+    if "*" in cdecl:
+        return ctype in (C.c_void_p, C.c_char_p) or issubclass(ctype, C._Pointer)
+    base = cdecl.replace("const ", "").strip()
+    if base in ("int", "int32_t"):
+        return ctype is C.c_int and C.sizeof(ctype) == 4
+    if base in ("int64_t", "uint64_t"):
+        return ctype in (C.c_int64, C.c_uint64)
+    if base == "double":
+        return ctype is C.c_double
+    if base == "sl_key":
+        return ctype is _hip.Key
+    raise AssertionError("argument type %r of sl_hip.h is not in the test's table" % cdecl)
+
+
+def test_signatures_match_header():
+    """Every prototype of the header against ``_hip.SIGNATURES``: the names, the number of arguments
+    and the class of every argument and of the return value."""
+    protos = _header_prototypes()
+    assert sorted(protos) == sorted(_hip.SIGNATURES) == _declared_symbols()
+    for name, (ret, args) in protos.items():
+        restype, argtypes = _hip.SIGNATURES[name]
+        assert {"int": C.c_int, "const char*": C.c_char_p}[ret] is restype, name
+        assert len(args) == len(argtypes), "%s: %d arguments in the header, %d bound" % (name, len(args), len(argtypes))
+        for k, (cdecl, ctype) in enumerate(zip(args, argtypes)):
+            assert _same_class(ctype, cdecl), "%s, argument %d: %s bound as %s" % (name, k, cdecl, ctype.__name__)
+
+
+class _StandIn(object):
+    """A library object with a settable function per name, like ``ctypes.CDLL`` gives."""
+
+    def __init__(self, names):
+        for name in names:
+            fn = type("fn", (), {"__call__": lambda self, ctx: b"what went wrong"})()
+            fn.__name__ = name
+            setattr(self, name, fn)
+
+
+def _bound_as_declared(lib, name):
+    restype, argtypes = _hip.SIGNATURES[name]
+    return getattr(lib, name).restype is restype and getattr(lib, name).argtypes == list(argtypes)
+
+
+def test_loader_binds_every_symbol_or_names_the_missing_one(monkeypatch):
+    monkeypatch.delenv("SL_LIB_PATH", raising=False)
+    lib = _hip._bind(_StandIn(_hip.SIGNATURES))
+    for name in _hip.SIGNATURES:
+        assert _bound_as_declared(lib, name), name
+    with pytest.raises(_hip.HipEngineError, match=r"\bsl_value_solve\b"):
+        _hip._bind(_StandIn(n for n in _hip.SIGNATURES if n != "sl_value_solve"))
+
+
+def test_loader_skips_symbols_a_development_library_lacks(monkeypatch):
+    monkeypatch.setenv("SL_LIB_PATH", "/somewhere/libslhip_dev.so")
+    lacking = ("sl_value_solve", "sl_values")
+    lib = _hip._bind(_StandIn(n for n in _hip.SIGNATURES if n not in lacking))
+    for name in _hip.SIGNATURES:
+        assert not hasattr(lib, name) if name in lacking else _bound_as_declared(lib, name), name
+
+
+def test_loader_makes_a_failed_call_raise(monkeypatch):
+    """Every entry point that takes a context and returns a status raises on a status other than 0,
+    with the text ``Context.check`` gives; the two whose caller reads the status do not."""
+    monkeypatch.delenv("SL_LIB_PATH", raising=False)
+    lib = _hip._bind(_StandIn(_hip.SIGNATURES))
+    for name, (restype, argtypes) in _hip.SIGNATURES.items():
+        fn = getattr(lib, name)
+        if restype is C.c_int and argtypes[:1] == (C.c_void_p,) and name not in _hip.UNCHECKED:
+            assert fn.errcheck(0, fn, (None,)) == 0
+            with pytest.raises(_hip.HipEngineError) as err:
+                fn.errcheck(-1, fn, (None,))
+            assert str(err.value) == "%s failed (-1): what went wrong" % name
+        else:
+            assert not hasattr(fn, "errcheck"), name
+    assert sorted(n for n in _hip.SIGNATURES if not hasattr(getattr(lib, n), "errcheck")) == [
+        "sl_comm_unique_id", "sl_ctx_create", "sl_ctx_destroy", "sl_gp_append_point", "sl_last_error",
+        "sl_last_kernel", "sl_version"]
 
 
 @pytest.mark.skipif(_have_gpu(), reason="only meaningful on a GPU-less host")
