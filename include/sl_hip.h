@@ -534,6 +534,32 @@ enum sl_eval_what {
 SL_API int  sl_eval_points(sl_ctx* ctx, int what, int64_t n, const double* d_points /* [n][d] */,
                     double* d_out);
 
+/* ---- closed-loop rollouts (utilities.py:519-583 compute_trajectory, examples/utilities.py:654-686
+ * compute_roa) ----------------------------------------------------------------------------- *
+ * sl_rollout advances the trajectories [lo, hi) by `steps` steps of x <- f(x, policy(x)) under the
+ *   model of sl_model_set, the state held in registers between steps (one thread per trajectory).
+ *   d_start NULL: trajectory i starts at grid point i (GridWorld.all_points: np.linspace, the last
+ *     point of an axis is its upper limit), hi <= the number of grid cells;
+ *   d_start [hi - lo][d]: explicit start states (the grid of the model is not used);
+ *   d_state [hi - lo][d]: the end states; may be d_start itself (continue a rollout in place);
+ *   d_traj NULL or [steps][hi - lo][d]: the state after every step, step-major;
+ *   d_actions NULL or [steps][hi - lo][m]: the action of every step (policy of the state before it).
+ *   The horizon is cut into launches of steps_per_launch steps with the state carried in d_state
+ *   (0: the library chooses from hi - lo so that a launch stays near a second); the results do not
+ *   depend on it.  steps = 0 copies the start states.
+ *   Policies: LINEAR, CONST, TRI (table slot 1); NETWORK runs step by step (its actions of a step
+ *   become a per-trajectory table, as in the sweeps); a per-vertex TABLE is defined for one step
+ *   only (steps > 1: SL_ERR_INVALID).  SL_DYN_GP: SL_ERR_UNSUPPORTED (step the mean through
+ *   sl_eval_points instead).
+ * sl_rollout_mask: bit i of d_bits (ceil(n / 64) words, bits past n zero) = ||x_i - e||_2 <= tol
+ *   for the states d_state [n][d] (any d up to SL_MAX_STATE_DIM; no model needed) - the rooted sum
+ *   of squares as np.linalg.norm adds it, NaN is outside; *d_count (may be NULL) = number of set
+ *   bits.  h_equilibrium NULL: the origin.                                                       */
+SL_API int  sl_rollout(sl_ctx* ctx, int64_t lo, int64_t hi, const double* d_start, int steps,
+                    int steps_per_launch, double* d_state, double* d_traj, double* d_actions);
+SL_API int  sl_rollout_mask(sl_ctx* ctx, int64_t n, int d, const double* d_state,
+                    const double* h_equilibrium /* [d] */, double tol, uint64_t* d_bits, int64_t* d_count);
+
 /* ---- multi-GPU collectives directly on RCCL ----------------------------- *
  * For callers without torch.distributed (the Python package issues the same exchanges through
  * torch.distributed, backend "nccl" = RCCL).  One communicator per context, one rank per GPU; every

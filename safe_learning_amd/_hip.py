@@ -197,6 +197,9 @@ SIGNATURES = {
     "sl_successor_cache_info": (_int, (_vp, C.POINTER(SuccessorCacheStats))),
     # evaluation at arbitrary points
     "sl_eval_points": (_int, (_vp, _int, _i64, _vp, _vp)),
+    # closed-loop rollouts
+    "sl_rollout": (_int, (_vp, _i64, _i64, _vp, _int, _int, _vp, _vp, _vp)),
+    "sl_rollout_mask": (_int, (_vp, _i64, _int, _vp, c_double_p, _dbl, _vp, _vp)),
     # RCCL collectives
     "sl_comm_unique_id": (_int, (C.c_char_p,)),
     "sl_comm_init": (_int, (_vp, C.c_char_p, _int, _int)),
@@ -584,6 +587,22 @@ class Context(object):
 
     def eval_points(self, what, n, d_points, d_out):
         self.lib.sl_eval_points(self.handle, what, n, _ptr(d_points), _ptr(d_out))
+
+    def rollout(self, lo, hi, d_start, steps, d_state, d_traj=None, d_actions=None, steps_per_launch=0):
+        """``sl_rollout``: ``steps`` closed-loop steps of the trajectories ``[lo, hi)`` under the model
+        (``d_start=None``: from the grid points)."""
+        self.lib.sl_rollout(self.handle, lo, hi, _ptr(d_start), int(steps), int(steps_per_launch),
+                            _ptr(d_state), _ptr(d_traj), _ptr(d_actions))
+
+    def rollout_mask(self, n, d, d_state, equilibrium, tol, d_bits, d_count):
+        """``sl_rollout_mask``: bit i = ``||state_i - equilibrium||_2 <= tol`` (``None``: the origin)."""
+        pe = None
+        if equilibrium is not None:
+            equilibrium, pe = _as_c(np.ravel(equilibrium))
+            if equilibrium.size != d:
+                raise ValueError("equilibrium has %d entries, the states %d" % (equilibrium.size, d))
+        self.lib.sl_rollout_mask(self.handle, int(n), int(d), _ptr(d_state), pe, float(tol), _ptr(d_bits),
+                                 _ptr(d_count))
 
     def synchronize(self):
         self.lib.sl_ctx_synchronize(self.handle)

@@ -1,9 +1,11 @@
-"""Host-side helpers kept from the reference's utilities (``safe_learning/utilities.py``)."""
+"""Helpers kept from the reference's utilities (``safe_learning/utilities.py``) and closed-loop
+simulation on the GPU: ``compute_trajectory`` (``utilities.py:519-583``) and the ``compute_roa`` of
+the notebooks (``examples/utilities.py:654-686``)."""
 
 import numpy as np
 import scipy.linalg
 
-__all__ = ['dlqr', 'batchify']
+__all__ = ['dlqr', 'batchify', 'compute_trajectory', 'compute_roa']
 
 
 def dlqr(a, b, q, r):
@@ -22,3 +24,185 @@ def batchify(arrays, batch_size):
     while arrays[0][start:start + batch_size].size:
         yield start, [a[start:start + batch_size] for a in arrays]
         start += batch_size
+
+
+# ---- closed-loop rollouts (csrc/sl_rollout.hip) ---------------------------------------------------
+
+def _engine(d):
+    """(context, model builder) of the rollouts: the point-evaluation context, which keeps tables
+    and network parameters between calls (``_evaluate._builder``)."""
+    from . import _evaluate
+    return _evaluate._builder(d)
+
+
+def _check_single_process():
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise NotImplementedError('closed-loop rollouts run on one GPU; under torch.distributed call them '
+                                  'on one rank (the C entry point sl_rollout takes a range [lo, hi) for '
+                                  'callers that shard by hand)')
+
+
+def _check_pair(dynamics, policy):
+    """The (dynamics, policy) specs the fused kernel takes."""
+    from .functions import (CartPole, ConstantFunction, InvertedPendulum, LinearSystem, NeuralNetwork,
+                            Saturation, Triangulation, UncertainFunction)
+    if isinstance(dynamics, UncertainFunction):
+        raise ValueError('the fused rollout needs deterministic dynamics; %s returns (mean, error): pass '
+                         'a callable instead of the pair, e.g. `lambda x: dynamics(x, policy(x))[0]`'
+                         % type(dynamics).__name__)
+    if not isinstance(dynamics, (LinearSystem, InvertedPendulum, CartPole)):
+        raise TypeError('unsupported dynamics spec %r: use LinearSystem, InvertedPendulum, CartPole, or '
+                        'pass a callable on states' % (dynamics,))
+    inner = policy.fun if isinstance(policy, Saturation) else policy
+    if not isinstance(inner, (LinearSystem, ConstantFunction, Triangulation, NeuralNetwork)):
+        raise TypeError('unsupported policy spec %r: use LinearSystem, ConstantFunction, a Saturation of '
+                        'either, a Triangulation or a NeuralNetwork, or pass a callable on states'
+                        % (policy,))
+
+
+def _start_points(ctx, grid):
+    """-> (GridWorld or None, device start points or None, n, d): a GridWorld starts the kernel at
+    its cells, anything else is an explicit ``[n, d]`` point list."""
+    from . import _evaluate
+    from .functions import GridWorld
+    if isinstance(grid, GridWorld):
+        return grid, None, int(grid.nindex), int(grid.ndim)
+    import torch
+    if not isinstance(grid, torch.Tensor):
+        grid = np.asarray(grid, dtype=np.float64)
+    if grid.ndim != 2:
+        raise ValueError('start states must be an [n, d] array, got shape %s' % (tuple(grid.shape),))
+    points = _evaluate._to_device(ctx, grid)
+    return None, points, int(points.shape[0]), int(points.shape[1])
+
+
+def _rollout(dynamics, policy, grid, steps, trajectory=False, actions=False, steps_per_launch=0):
+    """``steps`` closed-loop steps from every cell of a GridWorld or every row of ``[n, d]`` start
+    states -> device tensors ``(end states [n, d], states [steps + 1, n, d] or None, actions
+    [steps, n, m] or None)``; the state buffer is step-major, row 0 the start states."""
+    import copy
+    import torch
+    from . import _evaluate
+    from .functions import GridWorld, QuadraticFunction
+    _check_pair(dynamics, policy)
+    _check_single_process()
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError('the number of steps must not be negative')
+    d = int(grid.ndim) if isinstance(grid, GridWorld) else int(grid.shape[-1])
+    ctx, builder = _engine(d)
+    world, start, n, d = _start_points(ctx, grid)
+    if world is not None:
+        builder.grid = copy.copy(world)
+    desc = builder.upload(policy, dynamics, QuadraticFunction(np.eye(d)))
+    m = int(desc.policy.m)
+    dev = ctx.torch_device
+    end = torch.empty((n, d), dtype=torch.float64, device=dev)
+    states = acts = None
+    if trajectory:
+        states = torch.empty((steps + 1, n, d), dtype=torch.float64, device=dev)
+        ctx.rollout(0, n, start, 0, states[0])                     # row 0: the start states
+        start = states[0]
+    if actions:
+        acts = torch.empty((steps, n, m), dtype=torch.float64, device=dev)
+    ctx.rollout(0, n, start, steps, end, states[1:] if trajectory and steps else None,
+                acts if actions and steps else None, steps_per_launch)
+    return end, states, acts
+
+
+def _membership(ctx, end, equilibrium, tol):
+    """``||end - equilibrium||_2 <= tol`` per row as a device bool tensor (``sl_rollout_mask``)."""
+    import torch
+    n, d = end.shape
+    dev = ctx.torch_device
+    bits = torch.zeros(((n + 63) // 64,), dtype=torch.int64, device=dev)
+    count = torch.zeros((1,), dtype=torch.int64, device=dev)
+    ctx.rollout_mask(n, d, end, equilibrium, tol, bits, count)
+    as_bytes = torch.empty((8 * ((n + 7) // 8),), dtype=torch.uint8, device=dev)
+    ctx.bits_to_bytes(n, bits, as_bytes)
+    return as_bytes[:n].to(torch.bool)
+
+
+def compute_trajectory(dynamics, policy, initial_state, num_steps, steps_per_launch=0):
+    """Simulate ``x <- dynamics(x, policy(x))`` from ``initial_state`` (``utilities.py:519-583``).
+
+    Returns ``states [num_steps, d]`` (row 0 the initial state) and ``actions [num_steps - 1, m]``;
+    for ``[n, d]`` initial states with n > 1 ``[n, num_steps, d]`` and ``[n, num_steps - 1, m]``,
+    every row simulated on its own.  ``dynamics`` and ``policy`` are specs (``LinearSystem``,
+    ``InvertedPendulum``, ``CartPole``; ``LinearSystem``, ``ConstantFunction``, ``Saturation``,
+    ``Triangulation``, ``NeuralNetwork``): the whole simulation is one kernel per chunk of steps
+    (``steps_per_launch``, 0 = chosen by the library; the result does not depend on it) with the
+    state in registers.  A device tensor as ``initial_state`` keeps the results on the device."""
+    import torch
+    num_steps = int(num_steps)
+    if num_steps < 1:
+        raise ValueError('num_steps counts the initial state: it must be at least 1')
+    keep = isinstance(initial_state, torch.Tensor)
+    if not keep:
+        initial_state = np.atleast_2d(np.asarray(initial_state, dtype=np.float64))
+    elif initial_state.dim() == 1:
+        initial_state = initial_state.reshape(1, -1)
+    _, states, acts = _rollout(dynamics, policy, initial_state, num_steps - 1, trajectory=True,
+                               actions=True, steps_per_launch=steps_per_launch)
+    states, acts = states.permute(1, 0, 2), acts.permute(1, 0, 2)
+    if states.shape[0] == 1:
+        states, acts = states[0], acts[0]
+    return (states, acts) if keep else (states.cpu().numpy(), acts.cpu().numpy())
+
+
+def compute_roa(grid, closed_loop_dynamics, horizon=100, tol=1e-3, equilibrium=None, no_traj=True,
+                steps_per_launch=0):
+    """The states of ``grid`` that end within ``tol`` of ``equilibrium`` after ``horizon - 1`` steps
+    of the closed loop (``examples/utilities.py:654-686``).
+
+    ``grid``: a ``GridWorld`` (all its points) or an ``[n, d]`` array of start states.
+    ``closed_loop_dynamics``: a ``(dynamics, policy)`` pair of specs - the fused kernel, see
+    ``compute_trajectory`` - or any callable on ``[n, d]`` states as in the reference (a GP's mean, a
+    composition of specs on device tensors ...), which is stepped ``horizon - 1`` times on the
+    device.  Returns the boolean mask ``roa [n]``; with ``no_traj=False`` also ``trajectories`` of
+    shape ``(n, d, horizon)`` - a permuted view of the step-major buffer the kernel writes, not a
+    copy.  Device-tensor start states keep the results on the device."""
+    import torch
+    from . import _evaluate
+    from .functions import GridWorld
+    horizon = int(horizon)
+    if horizon < 1:
+        raise ValueError('horizon counts the start states: it must be at least 1')
+    keep = isinstance(grid, torch.Tensor)
+    d = int(grid.ndim) if isinstance(grid, GridWorld) else int(np.shape(grid)[-1])
+    if equilibrium is not None and np.size(equilibrium) != d:
+        raise ValueError('equilibrium has %d entries, the states %d' % (np.size(equilibrium), d))
+    if isinstance(closed_loop_dynamics, (tuple, list)):
+        if len(closed_loop_dynamics) != 2:
+            raise ValueError('closed_loop_dynamics must be a (dynamics, policy) pair or a callable')
+        dynamics, policy = closed_loop_dynamics
+        end, states, _ = _rollout(dynamics, policy, grid, horizon - 1, trajectory=not no_traj,
+                                  steps_per_launch=steps_per_launch)
+        ctx = _evaluate._ctx()
+    elif callable(closed_loop_dynamics):
+        _check_single_process()
+        ctx = _evaluate._ctx()
+        points = grid.all_points if isinstance(grid, GridWorld) else grid
+        if np.ndim(points) != 2:
+            raise ValueError('start states must be an [n, d] array')
+        end = _evaluate._to_device(ctx, points)
+        states = None
+        if not no_traj:
+            states = torch.empty((horizon,) + tuple(end.shape), dtype=torch.float64, device=ctx.torch_device)
+            states[0] = end
+        for t in range(1, horizon):
+            nxt = closed_loop_dynamics(end)
+            nxt = nxt[0] if isinstance(nxt, tuple) else nxt
+            end = _evaluate._to_device(ctx, nxt)
+            if states is not None:
+                states[t] = end
+    else:
+        raise TypeError('closed_loop_dynamics must be a (dynamics, policy) pair of specs or a callable')
+    roa = _membership(ctx, end, equilibrium, tol)
+    if not keep:
+        roa = roa.cpu().numpy()
+    if no_traj:
+        return roa
+    trajectories = states.permute(1, 2, 0)                           # (n, d, horizon), a view
+    return roa, (trajectories if keep else trajectories.cpu().numpy())

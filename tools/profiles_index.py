@@ -108,7 +108,9 @@ def main():
              "* `r06_shard_balance.md`: the N = 2 / 4 / 8 shards of C4 and C5 timed one by one on one GPU (`tools/shard_balance.py`).",
              "* `r06_parity_report.md`: what the parity claims rest on, what is a definition, what is unpinned.",
              "* `r06_box_variance_ab.txt`: the round-5 library and the tree alternating on ONE box (C3, C4-lin, C4-det): boxes of the pool "
-             "differ by 1-4 %, the libraries by < 0.3 %.", ""]
+             "differ by 1-4 %, the libraries by < 0.3 %.",
+             "* `rollout_roa.md`, `rollout_kernel_stats.md`: closed-loop rollouts (`k_rollout`, csrc/sl_rollout.hip) against the stepwise "
+             "composition of the point evaluations and against the sweep of the same cells (`tools/rollout_probe.py`; DESIGN.md 4.2b).", ""]
     for key in sorted(by_round):
         text.append("* %s: %s" % (key, ", ".join("`%s`" % n for n in by_round[key])))
     with open(os.path.join(P, "README.md"), "w") as f:
