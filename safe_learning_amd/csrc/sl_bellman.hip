@@ -722,18 +722,13 @@ static int bellman_mfma(sl_ctx* ctx, const SlBellmanArgs& b) {
     const int blocks = (int)(ntiles < ctx->num_cu ? ntiles : ctx->num_cu);
     SlAux aux{ctx->d_tri, ctx->d_net};
     if (policy_mode) {
-#define SL_BP_LAUNCH(D_)                                                                          \
-        do {                                                                                      \
-            auto kern = k_bellman_policy_mfma<D_>;                                                \
-            SL_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),            \
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                                                  (int)lds));                                     \
-            hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * SL_BM_WAVES), lds, ctx->stream,      \
-                               ctx->h_model, ctx->h_gp, aux, pk, lo, hi, pack, b.v_new, b.stats); \
-        } while (0)
-        if (variant == 4) SL_BP_LAUNCH(4); else SL_BP_LAUNCH(2);
-#undef SL_BP_LAUNCH
-        SL_HIP_CHECK(ctx, hipGetLastError());
+        const int rc = sl_with_dim<4, 2>(variant, [&](auto dt) {
+            SL_HIP_CHECK(ctx, sl_launch_lds(k_bellman_policy_mfma<dt>, dim3(blocks), dim3(64 * SL_BM_WAVES), lds,
+                                            ctx->stream, ctx->h_model, ctx->h_gp, aux, pk, lo, hi, pack, b.v_new,
+                                            b.stats));
+            return SL_OK;
+        });
+        if (rc) return rc;
         sl_note_kernel(ctx, false, "k_bellman_policy_mfma<d=%d>", variant == 4 ? 4 : 2);
         return SL_OK;
     }
@@ -744,30 +739,18 @@ static int bellman_mfma(sl_ctx* ctx, const SlBellmanArgs& b) {
         fill = sl_succ_view(ctx);
         ctx->succ.filled = true;
     }
-#define SL_BM_LAUNCH(D_, N_, H_)                                                                  \
-    do {                                                                                          \
-        auto kern = k_bellman_mfma<D_, N_, H_>;                                                   \
-        SL_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize,         \
-                                              (int)lds));                                         \
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * SL_BM_WAVES), lds, ctx->stream,          \
-                           ctx->h_model, ctx->h_gp, aux, pk, lo, hi, n_actions, ctx->d_actions,   \
-                           pack, b.v_new, b.argmax, b.q, b.stats, bm_flags, fill);                \
-    } while (0)
-#define SL_BM_DIMS(N_)                                  \
-    do {                                                \
-        if (variant == 4) SL_BM_LAUNCH(4, N_, 1);       \
-        else SL_BM_LAUNCH(2, N_, 1);                    \
-    } while (0)
-    if (nheads > 1) {
-        if (variant == 4) SL_BM_LAUNCH(4, 1, 4);
-        else SL_BM_LAUNCH(2, 1, 2);
-    } else if (ncb_t == 1) SL_BM_DIMS(1);
-    else if (ncb_t == 3) SL_BM_DIMS(3);
-    else SL_BM_DIMS(6);
-#undef SL_BM_DIMS
-#undef SL_BM_LAUNCH
-    SL_HIP_CHECK(ctx, hipGetLastError());
+    // one head with 1, 3 or 6 column blocks, or (0 here) a FunctionStack of D single-output heads with one each
+    const int rc = sl_with_dim<4, 2>(variant, [&](auto dt) {
+        constexpr int DT = dt;
+        return sl_with_dim<0, 1, 3, 6>(nheads > 1 ? 0 : ncb_t, [&](auto n) {
+            constexpr int NCB = n != 0 ? n : 1, HEADS = n != 0 ? 1 : DT;
+            SL_HIP_CHECK(ctx, sl_launch_lds(k_bellman_mfma<DT, NCB, HEADS>, dim3(blocks), dim3(64 * SL_BM_WAVES), lds,
+                                            ctx->stream, ctx->h_model, ctx->h_gp, aux, pk, lo, hi, n_actions,
+                                            ctx->d_actions, pack, b.v_new, b.argmax, b.q, b.stats, bm_flags, fill));
+            return SL_OK;
+        });
+    });
+    if (rc) return rc;
     sl_note_kernel(ctx, false, "k_bellman_mfma<d=%d, column blocks=%d, heads=%d>", variant == 4 ? 4 : 2,
                    nheads > 1 ? 1 : ncb_t, nheads);
     return SL_OK;
@@ -791,40 +774,31 @@ static int bellman_valu(sl_ctx* ctx, const SlBellmanArgs& b) {
     const int blocks = (int)(blocks64 < cap ? blocks64 : cap);
     SlAux aux{ctx->d_tri, ctx->d_net};
     const int variant = sl_dim_variant_of(M);
-#define SL_BELLMAN(ACT, D_, M_)                                                                  \
-    do {                                                                                         \
-        auto kern = k_bellman<ACT, D_, M_>;                                                      \
-        if (lds > 48 * 1024)                                                                     \
-            SL_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),           \
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize,    \
-                                                  (int)lds));                                    \
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(SL_BLOCK), lds, ctx->stream, ctx->h_model,   \
-                           ctx->h_gp, aux, lo, hi, n_actions, ctx->d_actions, b.v_new, b.argmax, \
-                           b.q, b.stats, fill);                                                  \
-    } while (0)
-#define SL_BELLMAN_DIMS(AM_)                                     \
-    do {                                                        \
-        if (variant == 4) SL_BELLMAN(AM_, 4, 1);                \
-        else if (variant == 2) SL_BELLMAN(AM_, 2, 1);           \
-        else if (variant == 1) SL_BELLMAN(AM_, 1, 1);           \
-        else SL_BELLMAN(AM_, 0, 0);                             \
-    } while (0)
-    // (DT = 0, the runtime-dimension flavour, locates through sl_tri_eval: nothing to cache)
-    SlSuccDev fill;
-    memset(&fill, 0, sizeof(fill));
-    if (ctx->succ.filling && variant != 0) {
-        fill = sl_succ_view(ctx);
-        ctx->succ.filled = true;
-    }
     sl_note_kernel(ctx, false, "k_bellman<actions<=%d, d=%d>", amax, variant);
-    if (amax == 3) SL_BELLMAN_DIMS(3);
-    else if (amax == 9) SL_BELLMAN_DIMS(9);
-    else if (amax == SL_MAX_ACTIONS) SL_BELLMAN_DIMS(SL_MAX_ACTIONS);
-    else SL_BELLMAN_DIMS(0);
-#undef SL_BELLMAN_DIMS
-#undef SL_BELLMAN
-    SL_HIP_CHECK(ctx, hipGetLastError());
-    return SL_OK;
+    return sl_with_dim<4, 2, 1, 0>(variant, [&](auto dt) {
+        constexpr int DT = dt;
+        // The kernel leaves the points it locates in the successor cache.  DT = 0, the runtime-dimension
+        // flavour (a 3-D grid among others), locates through sl_tri_eval and has none to leave: the cache
+        // is handed over, and reported as filled, only where the instantiation launched here can fill it.
+        SlSuccDev fill;
+        memset(&fill, 0, sizeof(fill));
+        if constexpr (DT != 0) {
+            if (ctx->succ.filling) {
+                fill = sl_succ_view(ctx);
+                ctx->succ.filled = true;
+            }
+        }
+        return sl_with_dim<3, 9, SL_MAX_ACTIONS, 0>(amax, [&](auto am) {
+            auto kern = k_bellman<am, DT, DT != 0 ? 1 : 0>;
+            if (lds > 48 * 1024)
+                SL_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(kern, dim3(blocks), dim3(SL_BLOCK), lds, ctx->stream, ctx->h_model, ctx->h_gp, aux, lo,
+                               hi, n_actions, ctx->d_actions, b.v_new, b.argmax, b.q, b.stats, fill);
+            SL_HIP_CHECK(ctx, hipGetLastError());
+            return SL_OK;
+        });
+    });
 }
 
 extern "C" int sl_bellman_sweep(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actions,

@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "sl_hip.h"
@@ -262,9 +263,7 @@ int sl_gp_small_launch(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& 
 int sl_bellman4_launch(sl_ctx* ctx, const SlBellmanArgs& b);
 int sl_bellman4_policy_launch(sl_ctx* ctx, const SlBellmanArgs& b);
 int sl_nn_values_launch(sl_ctx* ctx, int64_t lo, int64_t hi, double* d_values);
-int sl_nn_check_launch(sl_ctx* ctx, int64_t lo, int64_t hi, const uint64_t* d_init_bits,
-                       const double* d_values, const double* d_records, uint64_t* d_neg_bits,
-                       int* nblocks, double* d_dbg, const double* d_points);
+int sl_nn_check_launch(sl_ctx* ctx, const SlSweepArgs& a, const double* d_records, int* nblocks);
 
 #define SL_HIP_CHECK(ctx, call)                                                             \
     do {                                                                                    \
@@ -657,10 +656,42 @@ static inline int sl_grid_blocks(int64_t ncells) {
     return (int)b;
 }
 
-// kernel-variant id of a model: 0 = generic, 1..4 = (d, 1)
+// ---- which template instantiation a launcher starts -----------------------------------------
+// kernel-variant id of a model: 0 = generic (dimensions read from the model), 1..4 = (d, 1)
 static inline int sl_dim_variant_of(const SlDevModel& M) {
     if (M.m.policy.m == 1 && M.m.grid.d >= 1 && M.m.grid.d <= 4) return M.m.grid.d;
     return 0;
+}
+
+// f(std::integral_constant<int, D>()) for the first listed D that equals `variant`, else for the
+// LAST one listed (a site's fallback).  The list is the set of instantiations the site compiles;
+// inside f the dimension is a compile-time value (`if constexpr (d != 0)`), so what the host does
+// around a launch cannot disagree with the kernel it starts.  Returns f's status.
+template <int D, int... Ds, typename F>
+static inline int sl_with_dim(int variant, F&& f) {
+    if constexpr (sizeof...(Ds) == 0) return f(std::integral_constant<int, D>());
+    else return variant == D ? f(std::integral_constant<int, D>()) : sl_with_dim<Ds...>(variant, f);
+}
+
+// The (GENERAL, D, M) flavours of the per-cell sweeps: fixed (state, action) dimensions fold every
+// per-dimension predicate; the table flavours are compiled for (2, 1) and the generic (0, 0) only.
+// f(std::bool_constant<GENERAL>(), d, m) with d, m integral constants.
+template <typename F>
+static inline int sl_with_flavour(bool general, int variant, F&& f) {
+    auto with_m = [&](auto g, auto d) { return f(g, d, std::integral_constant<int, d != 0 ? 1 : 0>()); };
+    if (general) return sl_with_dim<2, 0>(variant, [&](auto d) { return with_m(std::true_type(), d); });
+    return sl_with_dim<1, 2, 3, 4, 0>(variant, [&](auto d) { return with_m(std::false_type(), d); });
+}
+
+// One launch of a kernel with `lds` bytes of dynamic LDS: opt in to that size, launch, and report.
+template <typename... P, typename... A>
+static inline hipError_t sl_launch_lds(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream,
+                                       const A&... args) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, grid, block, lds, stream, args...);
+    return hipGetLastError();
 }
 
 // true when the model needs the table / network code paths

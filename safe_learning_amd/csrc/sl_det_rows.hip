@@ -221,17 +221,13 @@ int sl_det_rows_launch(sl_ctx* ctx, const SlSweepArgs& a, int* nblocks) {
         SL_HIP_CHECK(ctx, hipMemsetAsync(a.neg_bits + ((hi - lo) >> 6), 0, sizeof(uint64_t), ctx->stream));
     const uint8_t* init_bytes = reinterpret_cast<const uint8_t*>(a.init_bits);
     uint8_t* neg_bytes = reinterpret_cast<uint8_t*>(a.neg_bits);
-#define SL_ROWS(D_)                                                                                \
-    hipLaunchKernelGGL(k_det_rows<D_>, dim3((unsigned)blocks), dim3(SL_BLOCK), 0, ctx->stream, M,  \
-                       lo, hi, init_bytes, a.values, neg_bytes, ctx->d_partials)
-    switch (M.m.grid.d) {
-        case 1: SL_ROWS(1); break;
-        case 2: SL_ROWS(2); break;
-        case 3: SL_ROWS(3); break;
-        default: SL_ROWS(4); break;
-    }
-#undef SL_ROWS
-    SL_HIP_CHECK(ctx, hipGetLastError());
+    int rc = sl_with_dim<1, 2, 3, 4>(M.m.grid.d, [&](auto d) {
+        hipLaunchKernelGGL(k_det_rows<d>, dim3((unsigned)blocks), dim3(SL_BLOCK), 0, ctx->stream, M, lo, hi,
+                           init_bytes, a.values, neg_bytes, ctx->d_partials);
+        SL_HIP_CHECK(ctx, hipGetLastError());
+        return SL_OK;
+    });
+    if (rc) return rc;
     sl_note_kernel(ctx, false, "k_det_rows<d=%d> (8 cells of a row per thread)", M.m.grid.d);
     return SL_OK;
 }

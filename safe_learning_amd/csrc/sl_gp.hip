@@ -647,17 +647,13 @@ static int launch_cfg(sl_ctx* ctx, const GpSweep& g) {
     if (lds > LDS_CAP)
         return sl_fail(ctx, SL_ERR_UNSUPPORTED, "GP training set too large for LDS staging "
                                                 "(%zu bytes needed)", lds);
-    auto kern = k_gp_sweep<W, R, CB, GENERAL, DT, MT, XSG>;
-    SL_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int64_t blocks = ntiles < ctx->num_cu ? ntiles : ctx->num_cu;
     if (blocks > SL_MAX_GRID) blocks = SL_MAX_GRID;
     *g.nblocks = (int)blocks;
     SlAux aux{ctx->d_tri, ctx->d_net};
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(W * 64), lds, ctx->stream, model,
-                       ctx->h_gp, aux, lo, hi, ntiles, a.init_bits, a.values, a.neg_bits, ctx->d_partials, a.dbg,
-                       xs_doubles, alpha_doubles, a.points, nb);
-    SL_HIP_CHECK(ctx, hipGetLastError());
+    SL_HIP_CHECK(ctx, sl_launch_lds(k_gp_sweep<W, R, CB, GENERAL, DT, MT, XSG>, dim3((unsigned)blocks), dim3(W * 64),
+                                    lds, ctx->stream, model, ctx->h_gp, aux, lo, hi, ntiles, a.init_bits, a.values,
+                                    a.neg_bits, ctx->d_partials, a.dbg, xs_doubles, alpha_doubles, a.points, nb));
     sl_note_kernel(ctx, false, "k_gp_sweep<W=%d, R=%d, CB=%d, general=%d, d=%d, m=%d, xs_global=%d>", W, R,
                    CB, (int)GENERAL, DT, MT, (int)XSG);
     return SL_OK;
@@ -710,27 +706,20 @@ static int gp_sweep_xs_global(sl_ctx* ctx, const GpSweep& g) {
     const size_t fixed = sizeof(double) * (2 * SL_GP_SLABS_PER_CHUNK * 4 * 64 + 8 * 64 +
                                            8 * 16 * SL_GP_DOUT_MAX + 2 * 64 * SL_D + 2 * 8);
     if (fixed + sizeof(double) * xs_max <= 160 * 1024) return SL_DECLINED;
-    const bool general = sl_model_is_general(g.model);
-    const int variant = sl_dim_variant_of(g.model);
-    if (!general && variant == 4) return launch_cfg<8, 4, 4, false, 4, 1, true>(ctx, g);
-    if (!general && variant == 2) return launch_cfg<8, 4, 4, false, 2, 1, true>(ctx, g);
-    return launch_cfg<8, 4, 4, true, 0, 0, true>(ctx, g);
+    // (compiled for the fast flavours of 4 and 2 dimensions; every other model takes the generic table flavour)
+    const int variant = sl_model_is_general(g.model) ? 0 : sl_dim_variant_of(g.model);
+    return sl_with_dim<4, 2, 0>(variant, [&](auto d) {
+        return launch_cfg<8, 4, 4, d == 0, d, d != 0 ? 1 : 0, true>(ctx, g);
+    });
 }
 
 // k_gp_sweep on the configuration's panel shape: takes every model
 template <int S>
 static int gp_sweep_shape(sl_ctx* ctx, const GpSweep& g) {
     constexpr int W = kCfgW[S], R = kCfgR[S], CB = kCfgCB[S];
-    const int variant = sl_dim_variant_of(g.model);
-    if (sl_model_is_general(g.model))
-        return variant == 2 ? launch_cfg<W, R, CB, true, 2, 1>(ctx, g) : launch_cfg<W, R, CB, true, 0, 0>(ctx, g);
-    switch (variant) {
-        case 1: return launch_cfg<W, R, CB, false, 1, 1>(ctx, g);
-        case 2: return launch_cfg<W, R, CB, false, 2, 1>(ctx, g);
-        case 3: return launch_cfg<W, R, CB, false, 3, 1>(ctx, g);
-        case 4: return launch_cfg<W, R, CB, false, 4, 1>(ctx, g);
-        default: return launch_cfg<W, R, CB, false, 0, 0>(ctx, g);
-    }
+    return sl_with_flavour(sl_model_is_general(g.model), sl_dim_variant_of(g.model), [&](auto general, auto d, auto m) {
+        return launch_cfg<W, R, CB, general, d, m>(ctx, g);
+    });
 }
 
 int sl_gp_sweep_launch(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, int* nblocks) {
@@ -905,15 +894,10 @@ extern "C" int sl_debug_fp64_rate(sl_ctx* ctx, int which, int iters, double* h_o
     const int blocks = ctx->num_cu * per_cu;     // per_cu blocks of 4 wavefronts per CU
     for (int rep = 0; rep < 2; ++rep) {
         SL_HIP_CHECK(ctx, hipEventRecord(e0, ctx->stream));
-        if (which == 0) hipLaunchKernelGGL(k_fp64_rate<0>, dim3(blocks), dim3(256), 0, ctx->stream, iters, sink, clocks);
-        else if (which == 1) hipLaunchKernelGGL(k_fp64_rate<1>, dim3(blocks), dim3(256), 0, ctx->stream, iters, sink, clocks);
-        else if (which == 2) hipLaunchKernelGGL(k_fp64_rate<2>, dim3(blocks), dim3(256), 0, ctx->stream, iters, sink, clocks);
-        else if (which == 3) hipLaunchKernelGGL(k_fp64_rate<3>, dim3(blocks), dim3(256), 0, ctx->stream, iters, sink, clocks);
-        else if (which == 4) hipLaunchKernelGGL(k_fp64_rate<4>, dim3(blocks), dim3(256), 0, ctx->stream, iters, sink, clocks);
-        else if (which == 5) hipLaunchKernelGGL(k_fp64_rate<5>, dim3(blocks), dim3(256), 0, ctx->stream, iters, sink, clocks);
-        else if (which == 6) hipLaunchKernelGGL(k_fp64_rate<6>, dim3(blocks), dim3(256), 0, ctx->stream, iters, sink, clocks);
-        else if (which == 7) hipLaunchKernelGGL(k_fp64_rate<7>, dim3(blocks), dim3(256), 0, ctx->stream, iters, sink, clocks);
-        else hipLaunchKernelGGL(k_fp64_rate<8>, dim3(blocks), dim3(256), 0, ctx->stream, iters, sink, clocks);
+        sl_with_dim<0, 1, 2, 3, 4, 5, 6, 7, 8>(which, [&](auto w) {
+            hipLaunchKernelGGL(k_fp64_rate<w>, dim3(blocks), dim3(256), 0, ctx->stream, iters, sink, clocks);
+            return SL_OK;
+        });
         SL_HIP_CHECK(ctx, hipEventRecord(e1, ctx->stream));
         SL_HIP_CHECK(ctx, hipEventSynchronize(e1));
     }

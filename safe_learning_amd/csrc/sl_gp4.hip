@@ -1032,9 +1032,8 @@ static bool gp4_early_ok(const sl_ctx* ctx, const SlDevModel& model, const doubl
 }
 
 template <int DT, int MT>
-static int launch4(sl_ctx* ctx, const SlDevModel& model, int64_t lo, int64_t hi,
-                   const uint64_t* d_init_bits, const double* d_values, uint64_t* d_neg_bits,
-                   int* nblocks, double* d_dbg, const double* d_points) {
+static int launch4(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, int* nblocks) {
+    const int64_t lo = a.lo, hi = a.hi;
     const int64_t ntiles = (hi - lo + 63) / 64;
     const int p = model.in_dim;
     for (int h = 0; h < ctx->h_gp.nheads; ++h) {
@@ -1049,10 +1048,7 @@ static int launch4(sl_ctx* ctx, const SlDevModel& model, int64_t lo, int64_t hi,
     static_assert(sizeof(double) * (2 * gp4::KXBUF + gp4::W * gp4::C + 2 * gp4::C * SL_D + gp4::C * SL_P +
                                     gp4::W * gp4::RUNS * gp4::RUNC) + (2 * gp4::W + 4) * sizeof(uint64_t)
                       <= 80 * 1024, "two workgroups of k_gp_sweep4 per CU");
-    const bool early = gp4_early_ok(ctx, model, d_dbg);
-    auto kern = early ? k_gp_sweep4<DT, MT, true> : k_gp_sweep4<DT, MT, false>;
-    SL_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const bool early = gp4_early_ok(ctx, model, a.dbg);
     const int64_t resident = (int64_t)ctx->num_cu * 2;
     int64_t blocks = ntiles < resident ? ntiles : resident;
     if (blocks > SL_MAX_GRID) blocks = SL_MAX_GRID;
@@ -1074,10 +1070,14 @@ static int launch4(sl_ctx* ctx, const SlDevModel& model, int64_t lo, int64_t hi,
     const bool counter = ntiles >= 4 * blocks;
     if (counter) SL_HIP_CHECK(ctx, hipMemsetAsync(ticket, 0, head_bytes, ctx->stream));
     else ticket = nullptr;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(gp4::W * 64), lds, ctx->stream, model,
-                       ctx->h_gp, aux, lo, hi, ntiles, d_init_bits, d_values, d_neg_bits,
-                       ctx->d_partials, d_dbg, d_points, skip, seeds, seed_chunks, ticket);
-    SL_HIP_CHECK(ctx, hipGetLastError());
+    const int rc = sl_with_dim<1, 0>(early, [&](auto e) {
+        SL_HIP_CHECK(ctx, sl_launch_lds(k_gp_sweep4<DT, MT, e != 0>, dim3((unsigned)blocks), dim3(gp4::W * 64), lds,
+                                        ctx->stream, model, ctx->h_gp, aux, lo, hi, ntiles, a.init_bits, a.values,
+                                        a.neg_bits, ctx->d_partials, a.dbg, a.points, skip, seeds, seed_chunks,
+                                        ticket));
+        return SL_OK;
+    });
+    if (rc) return rc;
 #ifdef SL_DIAG
     if (skip & 16) {
         unsigned long long c[8];
@@ -1097,17 +1097,15 @@ static int launch4(sl_ctx* ctx, const SlDevModel& model, int64_t lo, int64_t hi,
 // One entry per state dimension.  The build compiles this file once per dimension
 // (-DSL_GP4_DIM=1..4, four hipcc jobs side by side: the unrolled chunks make one instantiation a
 // minute of compile time); without the macro everything lives in one translation unit.
-#define SL_GP4_DIM_ENTRY(D_)                                                                       \
-    int sl_gp4_launch_d##D_(sl_ctx* ctx, const SlDevModel& model, int64_t lo, int64_t hi,          \
-                            const uint64_t* d_init_bits, const double* d_values,                   \
-                            uint64_t* d_neg_bits, int* nblocks, double* d_dbg,                     \
-                            const double* d_points) {                                              \
-        return launch4<D_, 1>(ctx, model, lo, hi, d_init_bits, d_values, d_neg_bits, nblocks,      \
-                              d_dbg, d_points);                                                    \
+template <int D>
+int sl_gp4_launch_dim(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, int* nblocks);
+#define SL_GP4_DIM_DECL(D_)                                                                                  \
+    template <> int sl_gp4_launch_dim<D_>(sl_ctx*, const SlDevModel&, const SlSweepArgs&, int*);
+#define SL_GP4_DIM_ENTRY(D_)                                                                                 \
+    template <>                                                                                              \
+    int sl_gp4_launch_dim<D_>(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, int* nblocks) {    \
+        return launch4<D_, 1>(ctx, model, a, nblocks);                                                       \
     }
-#define SL_GP4_DIM_DECL(D_)                                                                        \
-    int sl_gp4_launch_d##D_(sl_ctx*, const SlDevModel&, int64_t, int64_t, const uint64_t*,         \
-                            const double*, uint64_t*, int*, double*, const double*);
 SL_GP4_DIM_DECL(1) SL_GP4_DIM_DECL(2) SL_GP4_DIM_DECL(3) SL_GP4_DIM_DECL(4)
 #if !defined(SL_GP4_DIM) || SL_GP4_DIM == 1
 SL_GP4_DIM_ENTRY(1)
@@ -1123,20 +1121,13 @@ SL_GP4_DIM_ENTRY(4)
 
 // Fast-path models (closed-form or per-vertex table policy, quadratic V) with panels of 512 rows.
 int sl_gp4_sweep_launch(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, int* nblocks) {
-    const int variant = sl_dim_variant_of(model);
-#define SL_GP4(D_)                                                                                 \
-    return sl_gp4_launch_d##D_(ctx, model, a.lo, a.hi, a.init_bits, a.values, a.neg_bits, nblocks, \
-                               a.dbg, a.points)
-    switch (variant) {
-        case 1: SL_GP4(1);
-        case 2: SL_GP4(2);
-        case 3: SL_GP4(3);
-        case 4: SL_GP4(4);
-        default: break;
-    }
-#undef SL_GP4
-    return sl_fail(ctx, SL_ERR_UNSUPPORTED, "k_gp_sweep4 is compiled for 1..4 state dimensions and "
-                                            "one action dimension");
+    return sl_with_dim<1, 2, 3, 4, 0>(sl_dim_variant_of(model), [&](auto d) {
+        if constexpr (d == 0)
+            return sl_fail(ctx, SL_ERR_UNSUPPORTED, "k_gp_sweep4 is compiled for 1..4 state dimensions and "
+                                                    "one action dimension");
+        else
+            return sl_gp4_launch_dim<d>(ctx, model, a, nblocks);
+    });
 }
 
 // models this kernel is instantiated for (the others stay on k_gp_sweep)

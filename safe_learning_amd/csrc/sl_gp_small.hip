@@ -352,10 +352,9 @@ bool sl_gp_small_supports(sl_ctx* ctx, const SlDevModel& model) {
 }
 
 template <bool GENERAL, int DT, int MT>
-static int launch_small(sl_ctx* ctx, const SlDevModel& model, int64_t lo, int64_t hi,
-                        const uint64_t* d_init_bits, const double* d_values, uint64_t* d_neg_bits,
-                        int* nblocks, double* d_dbg, const double* d_points) {
+static int launch_small(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, int* nblocks) {
     using namespace gps;
+    const int64_t lo = a.lo, hi = a.hi;
     const int p = model.in_dim, d = model.m.grid.d;
     const int64_t ntiles = (hi - lo + 63) / 64;
     // per head: scaled inputs, alpha' and (when everything fits) the factor's lower triangle
@@ -439,51 +438,30 @@ static int launch_small(sl_ctx* ctx, const SlDevModel& model, int64_t lo, int64_
         ticket = ctx->d_ticket;
         SL_HIP_CHECK(ctx, hipMemsetAsync(ticket, 0, sizeof(unsigned long long), ctx->stream));
     }
-    const bool other_kernels = sl_has_other_kernels(ctx);
-#define SL_GPS_GO(ALDS_, W_)                                                                       \
-    do {                                                                                           \
-        auto kern = other_kernels ? k_gp_small<GENERAL, DT, MT, ALDS_, W_, true>                   \
-                                  : k_gp_small<GENERAL, DT, MT, ALDS_, W_, false>;                 \
-        SL_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                 \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * W_), lds, ctx->stream, model,   \
-                           ctx->h_gp, aux, lo, hi, ntiles, d_init_bits, d_values, d_neg_bits,      \
-                           ctx->d_partials, d_dbg, head_doubles, d_points, ticket,              \
-                           sl_diag_flags("SL_GPS_FLAGS"));                                      \
-    } while (0)
-    if constexpr (DT > 0) {
-        if (waves == WAVES_MAX) { if (alds) SL_GPS_GO(true, WAVES_MAX); else SL_GPS_GO(false, WAVES_MAX); }
-    }
-    if constexpr (DT > 0) {
-        if (waves == WAVES_TOP) { if (alds) SL_GPS_GO(true, WAVES_TOP); else SL_GPS_GO(false, WAVES_TOP); }
-    }
-    if constexpr (DT > 0) {
-        if (waves == WAVES_TINY) { if (alds) SL_GPS_GO(true, WAVES_TINY); else SL_GPS_GO(false, WAVES_TINY); }
-    }
-    if (waves == WAVES_MIN) { if (alds) SL_GPS_GO(true, WAVES_MIN); else SL_GPS_GO(false, WAVES_MIN); }
-#undef SL_GPS_GO
-    SL_HIP_CHECK(ctx, hipGetLastError());
+    // the factor in LDS (bit 1) and sum-of-products heads (bit 0) are compile-time flavours of every size
+    const int flags = (alds ? 2 : 0) | (sl_has_other_kernels(ctx) ? 1 : 0);
+    auto launch = [&](auto w) {
+        constexpr int W = w;
+        return sl_with_dim<3, 2, 1, 0>(flags, [&](auto f) {
+            SL_HIP_CHECK(ctx, sl_launch_lds(k_gp_small<GENERAL, DT, MT, (f & 2) != 0, W, (f & 1) != 0>,
+                                            dim3((unsigned)blocks), dim3(64 * W), lds, ctx->stream, model, ctx->h_gp,
+                                            aux, lo, hi, ntiles, a.init_bits, a.values, a.neg_bits, ctx->d_partials,
+                                            a.dbg, head_doubles, a.points, ticket, sl_diag_flags("SL_GPS_FLAGS")));
+            return SL_OK;
+        });
+    };
+    // (the runtime-dimension instantiations are compiled for eight wavefronts only)
+    int rc;
+    if constexpr (DT > 0) rc = sl_with_dim<WAVES_MAX, WAVES_TOP, WAVES_TINY, WAVES_MIN>(waves, launch);
+    else rc = sl_with_dim<WAVES_MIN>(waves, launch);
+    if (rc) return rc;
     sl_note_kernel(ctx, false, "k_gp_small<general=%d, d=%d, m=%d, Linv in %s, %d wavefronts> (%d head(s))",
                    (int)GENERAL, DT, MT, alds ? "LDS" : "L2", waves, ctx->h_gp.nheads);
     return SL_OK;
 }
 
 int sl_gp_small_launch(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, int* nblocks) {
-    const bool general = sl_model_is_general(model);
-    const int variant = sl_dim_variant_of(model);
-#define SL_GPS(G, D_, M_)                                                                          \
-    return launch_small<G, D_, M_>(ctx, model, a.lo, a.hi, a.init_bits, a.values, a.neg_bits, nblocks, \
-                                   a.dbg, a.points)
-    if (general) {
-        if (variant == 2) SL_GPS(true, 2, 1);
-        SL_GPS(true, 0, 0);
-    }
-    switch (variant) {
-        case 1: SL_GPS(false, 1, 1);
-        case 2: SL_GPS(false, 2, 1);
-        case 3: SL_GPS(false, 3, 1);
-        case 4: SL_GPS(false, 4, 1);
-        default: SL_GPS(false, 0, 0);
-    }
-#undef SL_GPS
+    return sl_with_flavour(sl_model_is_general(model), sl_dim_variant_of(model), [&](auto general, auto d, auto m) {
+        return launch_small<general, d, m>(ctx, model, a, nblocks);
+    });
 }

@@ -418,29 +418,6 @@ static int sl_check_ready(sl_ctx* ctx, const char* who) {
     return SL_OK;
 }
 
-// =============================================================================================
-// kernel-variant dispatch: fixed (state, action) dimensions fold every per-dimension predicate
-// =============================================================================================
-// variant ids: 0 = generic (dimensions read from the model), 1..4 = (d, 1) with d = 1..4
-static inline int sl_dim_variant(const SlDevModel& M) {
-    if (M.m.policy.m == 1 && M.m.grid.d >= 1 && M.m.grid.d <= 4) return M.m.grid.d;
-    return 0;
-}
-#define SL_DISPATCH_DIMS(variant, general, CALL)                                     \
-    do {                                                                             \
-        if (general) {                                                               \
-            if ((variant) == 2) { CALL(true, 2, 1); } else { CALL(true, 0, 0); }     \
-        } else {                                                                     \
-            switch (variant) {                                                       \
-                case 1: CALL(false, 1, 1); break;                                    \
-                case 2: CALL(false, 2, 1); break;                                    \
-                case 3: CALL(false, 3, 1); break;                                    \
-                case 4: CALL(false, 4, 1); break;                                    \
-                default: CALL(false, 0, 0); break;                                   \
-            }                                                                        \
-        }                                                                            \
-    } while (0)
-
 // Wavefronts per SIMD the compiler has to leave room for (second argument of __launch_bounds__) in the
 // GENERAL flavours - table V, interpolated policy - of the per-cell kernels below: left alone they
 // take 256 + 126 ... 240 registers, one wavefront per SIMD (profiles/r06_gen_waves_ab.txt).
@@ -490,13 +467,12 @@ extern "C" int sl_values(sl_ctx* ctx, int64_t lo, int64_t hi, double* d_values) 
     if (ctx->h_model.m.value.kind == SL_V_NETWORK) return sl_nn_values_launch(ctx, lo, hi, d_values);
     SlAux aux{ctx->d_tri, ctx->d_net};
     const int blocks = sl_grid_blocks(hi - lo);
-#define SL_CALL(G, D_, M_)                                                                    \
-    hipLaunchKernelGGL((k_values<G, D_, M_>), dim3(blocks), dim3(SL_BLOCK), 0, ctx->stream,   \
-                       ctx->h_model, aux, lo, hi, d_values)
-    SL_DISPATCH_DIMS(sl_dim_variant(ctx->h_model), sl_model_is_general(ctx->h_model), SL_CALL);
-#undef SL_CALL
-    SL_HIP_CHECK(ctx, hipGetLastError());
-    return SL_OK;
+    return sl_with_flavour(sl_model_is_general(ctx->h_model), sl_dim_variant_of(ctx->h_model), [&](auto g, auto d, auto m) {
+        hipLaunchKernelGGL((k_values<g, d, m>), dim3(blocks), dim3(SL_BLOCK), 0, ctx->stream, ctx->h_model, aux,
+                           lo, hi, d_values);
+        SL_HIP_CHECK(ctx, hipGetLastError());
+        return SL_OK;
+    });
 }
 
 // =============================================================================================
@@ -810,8 +786,7 @@ static int sweep_network_value(sl_ctx* ctx, const SlSweepArgs& a, int* blocks) {
         if (!rc) rc = sl_gp_sweep_launch(ctx, sl_posterior_only(ctx->h_model), posterior, &gp_blocks);
         if (rc) return rc;
     }
-    return sl_nn_check_launch(ctx, a.lo, a.hi, a.init_bits, a.values, posterior.dbg, a.neg_bits, blocks, a.dbg,
-                              a.points);
+    return sl_nn_check_launch(ctx, a, posterior.dbg, blocks);
 }
 
 // table flavours (V, L_v = |grad V|, interpolated policy) of a GP model whose heads are served by
@@ -833,28 +808,29 @@ static int sweep_gp_three_pass(sl_ctx* ctx, const SlSweepArgs& a, int* blocks) {
     const double* rec = posterior.dbg;
     double* act = posterior.dbg + (size_t)(hi - lo) * (2 + 2 * full.m.grid.d);
     SlAux aux{ctx->d_tri, ctx->d_net};
-    const int variant = sl_dim_variant(full);
+    const int variant = sl_dim_variant_of(full);
     *blocks = sl_grid_blocks(hi - lo);
     if (tri_policy) {
-#define SL_CALL(G, D_, M_)                                                                     \
-    hipLaunchKernelGGL((k_policy_table<true, D_, M_>), dim3(*blocks), dim3(SL_BLOCK), 0, ctx->stream, \
-                       full, aux, lo, hi, a.points, act)
-        SL_DISPATCH_DIMS(variant, true, SL_CALL);
-#undef SL_CALL
-        SL_HIP_CHECK(ctx, hipGetLastError());
+        rc = sl_with_flavour(true, variant, [&](auto, auto d, auto m) {
+            hipLaunchKernelGGL((k_policy_table<true, d, m>), dim3(*blocks), dim3(SL_BLOCK), 0, ctx->stream, full,
+                               aux, lo, hi, a.points, act);
+            SL_HIP_CHECK(ctx, hipGetLastError());
+            return SL_OK;
+        });
+        if (rc) return rc;
         // the per-cell table is indexed by the cell (or point) number
         posterior_only.m.policy.d_table = act - lo * m;
     }
     int gp_blocks = 0;
     rc = sl_gp_sweep_launch(ctx, posterior_only, posterior, &gp_blocks);
     if (rc) return rc;
-#define SL_CALL(G, D_, M_)                                                                     \
-    hipLaunchKernelGGL((k_check_records<true, D_, M_>), dim3(*blocks), dim3(SL_BLOCK), 0, ctx->stream, \
-                       full, aux, lo, hi, a.init_bits, a.values, rec, a.neg_bits, ctx->d_partials, \
-                       a.dbg, a.points)
-    SL_DISPATCH_DIMS(variant, true, SL_CALL);
-#undef SL_CALL
-    SL_HIP_CHECK(ctx, hipGetLastError());
+    rc = sl_with_flavour(true, variant, [&](auto, auto d, auto m) {
+        hipLaunchKernelGGL((k_check_records<true, d, m>), dim3(*blocks), dim3(SL_BLOCK), 0, ctx->stream, full, aux,
+                           lo, hi, a.init_bits, a.values, rec, a.neg_bits, ctx->d_partials, a.dbg, a.points);
+        SL_HIP_CHECK(ctx, hipGetLastError());
+        return SL_OK;
+    });
+    if (rc) return rc;
     sl_note_kernel(ctx, true, tri_policy ? "k_policy_table + k_check_records" : "k_check_records");
     return SL_OK;
 }
@@ -864,34 +840,32 @@ static int sweep_gp(sl_ctx* ctx, const SlSweepArgs& a, int* blocks) {
     return sl_gp_sweep_launch(ctx, ctx->h_model, a, blocks);
 }
 
-template <bool G, int D, int M, int DYN>
-static void launch_det(sl_ctx* ctx, const SlSweepArgs& a, int blocks, bool pow2) {
-    constexpr bool POW2_OK = !G && D > 0 && DYN != 0;
-    auto kern = POW2_OK && pow2 ? k_det_sweep<G, D, M, DYN, POW2_OK> : k_det_sweep<G, D, M, DYN>;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(SL_BLOCK), 0, ctx->stream, ctx->h_model, SlAux{ctx->d_tri, ctx->d_net},
-                       a.lo, a.hi, a.init_bits, a.values, a.neg_bits, ctx->d_partials, a.dbg, a.points);
-}
-
 // deterministic dynamics, one cell per thread: takes every model
 static int sweep_det(sl_ctx* ctx, const SlSweepArgs& a, int* blocks) {
     const SlDevModel& M = ctx->h_model;
     *blocks = sl_grid_blocks(a.hi - a.lo);
-    const int dyn = M.m.dynamics.kind, variant = sl_dim_variant(M);
+    const int dyn = M.m.dynamics.kind, variant = sl_dim_variant_of(M);
     const bool general = sl_model_is_general(M);
     const bool pow2 = M.gf.all_pow2 && M.gf.nindex <= 0xffffffffll && !a.dbg && !a.points;
-#define SL_CALL(G, D_, M_)                                                                     \
-    do {                                                                                       \
-        if (!(G) && (D_) > 0 && dyn == SL_DYN_LINEAR) launch_det<G, D_, M_, SL_DYN_LINEAR>(ctx, a, *blocks, pow2); \
-        else if (!(G) && (D_) == 2 && dyn == SL_DYN_PENDULUM) launch_det<G, D_, M_, SL_DYN_PENDULUM>(ctx, a, *blocks, pow2); \
-        else if (!(G) && (D_) == 4 && dyn == SL_DYN_CARTPOLE) launch_det<G, D_, M_, SL_DYN_CARTPOLE>(ctx, a, *blocks, pow2); \
-        else launch_det<G, D_, M_, 0>(ctx, a, *blocks, pow2);                                   \
-    } while (0)
-    SL_DISPATCH_DIMS(variant, general, SL_CALL);
-#undef SL_CALL
     sl_note_kernel(ctx, false, "k_det_sweep<general=%d, d=%d, dynamics=%d, pow2=%d>", (int)general, variant,
                    dyn, (int)pow2);
-    SL_HIP_CHECK(ctx, hipGetLastError());
-    return SL_OK;
+    return sl_with_flavour(general, variant, [&](auto g, auto d, auto m) {
+        // the closed-form dynamics a fast flavour of this dimension is compiled for (0: read from the model)
+        constexpr bool G = g;
+        constexpr int D = d, MT = m;
+        auto launch = [&](auto dk) {
+            constexpr bool POW2_OK = !G && D > 0 && dk != 0;
+            auto kern = POW2_OK && pow2 ? k_det_sweep<G, D, MT, dk, POW2_OK> : k_det_sweep<G, D, MT, dk>;
+            hipLaunchKernelGGL(kern, dim3(*blocks), dim3(SL_BLOCK), 0, ctx->stream, M, SlAux{ctx->d_tri, ctx->d_net},
+                               a.lo, a.hi, a.init_bits, a.values, a.neg_bits, ctx->d_partials, a.dbg, a.points);
+            SL_HIP_CHECK(ctx, hipGetLastError());
+            return SL_OK;
+        };
+        if (!G && D > 0 && dyn == SL_DYN_LINEAR) return launch(std::integral_constant<int, SL_DYN_LINEAR>());
+        if (!G && D == 2 && dyn == SL_DYN_PENDULUM) return launch(std::integral_constant<int, SL_DYN_PENDULUM>());
+        if (!G && D == 4 && dyn == SL_DYN_CARTPOLE) return launch(std::integral_constant<int, SL_DYN_CARTPOLE>());
+        return launch(std::integral_constant<int, 0>());
+    });
 }
 
 // shared by sl_lyap_sweep (grid cells) and sl_eval_points (explicit points)

@@ -460,20 +460,15 @@ extern "C" int sl_lyap_finalize_dev(sl_ctx* ctx, int64_t lo, int64_t hi, const d
         const uint8_t* init_bytes = reinterpret_cast<const uint8_t*>(d_init_bits);
         const uint8_t* prev_bytes = reinterpret_cast<const uint8_t*>(d_prev_bits);
         uint8_t* safe_bytes = reinterpret_cast<uint8_t*>(d_safe_bits);
-#define SL_FIN(D_)                                                                                  \
-    hipLaunchKernelGGL(k_finalize_dev<D_>, dim3(blocks), dim3(SL_BLOCK), 0, ctx->stream,            \
-                       ctx->h_model, lo, hi, d_values, init_bytes, prev_bytes, d_folded, d_keep,    \
-                       safe_bytes, ctx->d_partials, ctx->d_partial_counts, span_groups, vector_ok, \
-                       fold_tail ? reinterpret_cast<unsigned int*>(ctx->d_ticket + 1) : nullptr, d_result)
-        switch (dt) {
-            case 1: SL_FIN(1); break;
-            case 2: SL_FIN(2); break;
-            case 3: SL_FIN(3); break;
-            case 4: SL_FIN(4); break;
-            default: SL_FIN(0); break;
-        }
-#undef SL_FIN
-        SL_HIP_CHECK(ctx, hipGetLastError());
+        rc = sl_with_dim<1, 2, 3, 4, 0>(dt, [&](auto d) {
+            hipLaunchKernelGGL(k_finalize_dev<d>, dim3(blocks), dim3(SL_BLOCK), 0, ctx->stream, ctx->h_model, lo, hi,
+                               d_values, init_bytes, prev_bytes, d_folded, d_keep, safe_bytes, ctx->d_partials,
+                               ctx->d_partial_counts, span_groups, vector_ok,
+                               fold_tail ? reinterpret_cast<unsigned int*>(ctx->d_ticket + 1) : nullptr, d_result);
+            SL_HIP_CHECK(ctx, hipGetLastError());
+            return SL_OK;
+        });
+        if (rc) return rc;
     }
     if (!blocks || !fold_tail) {                        // (an empty range: the record of no cells)
         hipLaunchKernelGGL(k_reduce_finalize_dev, dim3(1), dim3(SL_BLOCK), 0, ctx->stream,
@@ -498,20 +493,12 @@ extern "C" int sl_refinement_carry(sl_ctx* ctx, int64_t lo, int64_t hi, const do
     const int blocks = blocks_for(ctx, hi - lo);
     const uint8_t* init_bytes = reinterpret_cast<const uint8_t*>(d_init_bits);
     const uint8_t* neg_bytes = reinterpret_cast<const uint8_t*>(d_neg_bits);
-#define SL_CARRY(D_)                                                                                \
-    hipLaunchKernelGGL(k_refinement_carry<D_>, dim3(blocks), dim3(SL_BLOCK), 0, ctx->stream,        \
-                       ctx->h_model, lo, hi, d_values, init_bytes, neg_bytes, d_folded, d_keep,     \
-                       d_refinement)
-    switch (dt) {
-        case 1: SL_CARRY(1); break;
-        case 2: SL_CARRY(2); break;
-        case 3: SL_CARRY(3); break;
-        case 4: SL_CARRY(4); break;
-        default: SL_CARRY(0); break;
-    }
-#undef SL_CARRY
-    SL_HIP_CHECK(ctx, hipGetLastError());
-    return SL_OK;
+    return sl_with_dim<1, 2, 3, 4, 0>(dt, [&](auto d) {
+        hipLaunchKernelGGL(k_refinement_carry<d>, dim3(blocks), dim3(SL_BLOCK), 0, ctx->stream, ctx->h_model, lo, hi,
+                           d_values, init_bytes, neg_bytes, d_folded, d_keep, d_refinement);
+        SL_HIP_CHECK(ctx, hipGetLastError());
+        return SL_OK;
+    });
 }
 
 extern "C" int sl_select_begin(sl_ctx* ctx, sl_select_state* d_state, int64_t k, int64_t batch,
@@ -537,19 +524,12 @@ extern "C" int sl_select_hist(sl_ctx* ctx, int64_t lo, int64_t hi, const double*
     SL_HIP_CHECK(ctx, hipMemsetAsync(d_hist, 0, 256 * sizeof(uint64_t), ctx->stream));
     if (hi == lo) return SL_OK;
     const int blocks = blocks_for(ctx, hi - lo);
-#define SL_HIST(D_)                                                                                 \
-    hipLaunchKernelGGL(k_select_hist<D_>, dim3(blocks), dim3(SL_BLOCK), 0, ctx->stream,             \
-                       ctx->h_model, lo, hi, d_values, which, byte, d_state, d_hist)
-    switch (dt) {
-        case 1: SL_HIST(1); break;
-        case 2: SL_HIST(2); break;
-        case 3: SL_HIST(3); break;
-        case 4: SL_HIST(4); break;
-        default: SL_HIST(0); break;
-    }
-#undef SL_HIST
-    SL_HIP_CHECK(ctx, hipGetLastError());
-    return SL_OK;
+    return sl_with_dim<1, 2, 3, 4, 0>(dt, [&](auto d) {
+        hipLaunchKernelGGL(k_select_hist<d>, dim3(blocks), dim3(SL_BLOCK), 0, ctx->stream, ctx->h_model, lo, hi,
+                           d_values, which, byte, d_state, d_hist);
+        SL_HIP_CHECK(ctx, hipGetLastError());
+        return SL_OK;
+    });
 }
 
 extern "C" int sl_select_digit(sl_ctx* ctx, int which, int byte, const uint64_t* d_hist,

@@ -238,49 +238,42 @@ __global__ __launch_bounds__(64 * SL_NNM_WAVES) void k_nn_check_mfma(
     if (threadIdx.x == 0) { partials[blockIdx.x].vbits = best_v; partials[blockIdx.x].index = best_i; }
 }
 
-#define SL_NN_DISPATCH(KERNEL, ...)                                                               \
-    do {                                                                                          \
-        const size_t wl = sizeof(double) * (size_t)ctx->h_net.wtotal;                             \
-        const int nl = ctx->h_net.nlayers;                                                        \
-        auto k1 = KERNEL(1); auto k2 = KERNEL(2); auto k3 = KERNEL(3); auto k4 = KERNEL(4);       \
-        auto kern = nl == 1 ? k1 : (nl == 2 ? k2 : (nl == 3 ? k3 : k4));                          \
-        SL_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize,         \
-                                              (int)wl));                                          \
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * SL_NNM_WAVES), wl, ctx->stream, \
-                           __VA_ARGS__);                                                          \
-    } while (0)
+// The kernels are compiled per layer count (1 .. 4: sl_with_dim over h_net.nlayers).
+// (the weights of every layer sit in dynamic LDS)
+static size_t nn_weight_bytes(const sl_ctx* ctx) { return sizeof(double) * (size_t)ctx->h_net.wtotal; }
 
 int sl_nn_values_launch(sl_ctx* ctx, int64_t lo, int64_t hi, double* d_values) {
     int64_t blocks = (hi - lo + 16 * SL_NNM_WAVES - 1) / (16 * SL_NNM_WAVES);
     const int64_t cap = (int64_t)ctx->num_cu * (ctx->h_net.wtotal * 8 > 75 * 1024 ? 1 : 2);
     if (blocks > cap) blocks = cap;
     SlAux aux{ctx->d_tri, ctx->d_net};
-#define SL_NN_VALUES(NL_) k_nn_values_mfma<NL_>
-    SL_NN_DISPATCH(SL_NN_VALUES, ctx->h_model, aux, lo, hi, d_values);
-    SL_HIP_CHECK(ctx, hipGetLastError());
-    return SL_OK;
+    return sl_with_dim<1, 2, 3, 4>(ctx->h_net.nlayers, [&](auto nl) {
+        SL_HIP_CHECK(ctx, sl_launch_lds(k_nn_values_mfma<nl>, dim3((unsigned)blocks), dim3(64 * SL_NNM_WAVES),
+                                        nn_weight_bytes(ctx), ctx->stream, ctx->h_model, aux, lo, hi, d_values));
+        return SL_OK;
+    });
 }
 
-int sl_nn_check_launch(sl_ctx* ctx, int64_t lo, int64_t hi, const uint64_t* d_init_bits,
-                   const double* d_values, const double* d_records, uint64_t* d_neg_bits,
-                   int* nblocks, double* d_dbg, const double* d_points) {
-    int64_t blocks = (hi - lo + 64 * SL_NNM_WAVES - 1) / (64 * SL_NNM_WAVES);
+// d_records: the GP posterior records of the sweep's first pass, or null (deterministic dynamics)
+int sl_nn_check_launch(sl_ctx* ctx, const SlSweepArgs& a, const double* d_records, int* nblocks) {
+    int64_t blocks = (a.hi - a.lo + 64 * SL_NNM_WAVES - 1) / (64 * SL_NNM_WAVES);
     int64_t cap = (int64_t)ctx->num_cu * (ctx->h_net.wtotal * 8 > 75 * 1024 ? 1 : 2);
     if (cap > SL_MAX_GRID) cap = SL_MAX_GRID;
     if (blocks > cap) blocks = cap;
     *nblocks = (int)blocks;
     SlAux aux{ctx->d_tri, ctx->d_net};
     const int variant = sl_dim_variant_of(ctx->h_model);
-#define SL_NN_CHECK_D2(NL_) k_nn_check_mfma<NL_, 2, 1>
-#define SL_NN_CHECK_D4(NL_) k_nn_check_mfma<NL_, 4, 1>
-#define SL_NN_CHECK_D0(NL_) k_nn_check_mfma<NL_, 0, 0>
-#define SL_NN_CHECK_ARGS ctx->h_model, aux, lo, hi, d_init_bits, d_values, d_records, d_neg_bits, \
-                     ctx->d_partials, d_dbg, d_points
-    if (variant == 2) SL_NN_DISPATCH(SL_NN_CHECK_D2, SL_NN_CHECK_ARGS);
-    else if (variant == 4) SL_NN_DISPATCH(SL_NN_CHECK_D4, SL_NN_CHECK_ARGS);
-    else SL_NN_DISPATCH(SL_NN_CHECK_D0, SL_NN_CHECK_ARGS);
-    SL_HIP_CHECK(ctx, hipGetLastError());
+    const int rc = sl_with_dim<2, 4, 0>(variant, [&](auto d) {
+        constexpr int D = d;
+        return sl_with_dim<1, 2, 3, 4>(ctx->h_net.nlayers, [&](auto nl) {
+            SL_HIP_CHECK(ctx, sl_launch_lds(k_nn_check_mfma<nl, D, D != 0 ? 1 : 0>, dim3((unsigned)blocks),
+                                            dim3(64 * SL_NNM_WAVES), nn_weight_bytes(ctx), ctx->stream, ctx->h_model,
+                                            aux, a.lo, a.hi, a.init_bits, a.values, d_records, a.neg_bits,
+                                            ctx->d_partials, a.dbg, a.points));
+            return SL_OK;
+        });
+    });
+    if (rc) return rc;
     sl_note_kernel(ctx, d_records != nullptr, "k_nn_check_mfma<layers=%d, d=%d>", ctx->h_net.nlayers,
                    variant);
     return SL_OK;

@@ -145,15 +145,13 @@ extern "C" int sl_policy_operator(sl_ctx* ctx, int64_t lo, int64_t hi, int32_t* 
     SL_HIP_CHECK(ctx, sl_grow(ctx, &ctx->d_scratch, &ctx->scratch_bytes, sizeof(double) * 2 * (size_t)nblk));
     double* part = reinterpret_cast<double*>(ctx->d_scratch);
     SlAux aux{ctx->d_tri, ctx->d_net};
-#define SL_ROWS(D_)                                                                                 \
-    hipLaunchKernelGGL(k_policy_operator_rows<D_>, dim3(nblk), dim3(SL_BLOCK), 0, ctx->stream,      \
-                       ctx->h_model, ctx->h_gp, aux, lo, hi, d_cols, d_w, d_r, part)
-    if (d == 1) SL_ROWS(1);
-    else if (d == 2) SL_ROWS(2);
-    else if (d == 3) SL_ROWS(3);
-    else SL_ROWS(4);
-#undef SL_ROWS
-    SL_HIP_CHECK(ctx, hipGetLastError());
+    const int rc = sl_with_dim<1, 2, 3, 4>(d, [&](auto dt) {
+        hipLaunchKernelGGL(k_policy_operator_rows<dt>, dim3(nblk), dim3(SL_BLOCK), 0, ctx->stream, ctx->h_model,
+                           ctx->h_gp, aux, lo, hi, d_cols, d_w, d_r, part);
+        SL_HIP_CHECK(ctx, hipGetLastError());
+        return SL_OK;
+    });
+    if (rc) return rc;
     hipLaunchKernelGGL(k_policy_operator_stats, dim3(1), dim3(SL_BLOCK), 0, ctx->stream, part, nblk,
                        M.m.gamma, d_stats);
     SL_HIP_CHECK(ctx, hipGetLastError());
@@ -495,16 +493,13 @@ struct Solver {
 
     template <int MODE>
     void matvec(const double* x, double* y, double* p, const SlSolveState* gate) {
-#define SL_MV(K_)                                                                                     \
-    hipLaunchKernelGGL((k_value_matvec<MODE, K_>), dim3(nblk), dim3(SL_BLOCK), 0, ctx->stream, n, k,  \
-                       cols, w, r, gamma, x, y, p, gate)
-        if (k <= 2) SL_MV(2);
-        else if (k <= 3) SL_MV(3);
-        else if (k <= 4) SL_MV(4);
-        else if (k <= 5) SL_MV(5);
-        else if (k <= 8) SL_MV(8);
-        else SL_MV(SL_ROW_MAX_K);
-#undef SL_MV
+        // compiled for rows of at most 2, 3, 4, 5, 8 and SL_ROW_MAX_K entries: the smallest that holds k
+        const int bucket = k <= 2 ? 2 : (k <= 5 ? k : (k <= 8 ? 8 : SL_ROW_MAX_K));
+        sl_with_dim<2, 3, 4, 5, 8, SL_ROW_MAX_K>(bucket, [&](auto kmax) {
+            hipLaunchKernelGGL((k_value_matvec<MODE, kmax>), dim3(nblk), dim3(SL_BLOCK), 0, ctx->stream, n, k, cols,
+                               w, r, gamma, x, y, p, gate);
+            return SL_OK;
+        });
     }
     // residual of x into V_0 and the status record (start: a GMRES cycle begins from it)
     int residual(const double* x, bool start, double tol_abs) {

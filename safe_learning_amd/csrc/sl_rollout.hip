@@ -167,12 +167,10 @@ int launch(sl_ctx* ctx, const RolloutArgs& a) {
     } else if (dyn == SL_DYN_CARTPOLE) {              // (d = 4, m = 1)
         launch_variant<false, 4, 1, SL_DYN_CARTPOLE>(ctx, a);
     } else if (dyn == SL_DYN_LINEAR && m == 1 && d >= 1 && d <= 4) {
-        switch (d) {
-            case 1: launch_variant<false, 1, 1, SL_DYN_LINEAR>(ctx, a); break;
-            case 2: launch_variant<false, 2, 1, SL_DYN_LINEAR>(ctx, a); break;
-            case 3: launch_variant<false, 3, 1, SL_DYN_LINEAR>(ctx, a); break;
-            default: launch_variant<false, 4, 1, SL_DYN_LINEAR>(ctx, a); break;
-        }
+        sl_with_dim<1, 2, 3, 4>(d, [&](auto dt) {
+            launch_variant<false, dt, 1, SL_DYN_LINEAR>(ctx, a);
+            return SL_OK;
+        });
     } else {
         launch_variant<false, 0, 0, 0>(ctx, a);
     }

@@ -448,13 +448,13 @@ int sl_succ_sweep(sl_ctx* ctx, const SlBellmanArgs& b) {
               S.select_lo == lo && S.select_hi == hi)) {
             S.select_valid = false;
             SL_HIP_CHECK(ctx, hipMemsetAsync(misses, 0, 8, ctx->stream));
-#define SL_SELECT(D_)                                                                              \
-    hipLaunchKernelGGL(k_succ_select<D_>, dim3(blocks), dim3(256), 0, ctx->stream, ctx->h_model,  \
-                       aux, sc, lo, hi, S.n_actions, usel, asel, misses, miss_list, cap)
-            if (variant == 4) SL_SELECT(4); else if (variant == 3) SL_SELECT(3);
-            else if (variant == 2) SL_SELECT(2); else SL_SELECT(1);
-#undef SL_SELECT
-            SL_HIP_CHECK(ctx, hipGetLastError());
+            const int rc = sl_with_dim<4, 3, 2, 1>(variant, [&](auto dt) {
+                hipLaunchKernelGGL(k_succ_select<dt>, dim3(blocks), dim3(256), 0, ctx->stream, ctx->h_model, aux, sc,
+                                   lo, hi, S.n_actions, usel, asel, misses, miss_list, cap);
+                SL_HIP_CHECK(ctx, hipGetLastError());
+                return SL_OK;
+            });
+            if (rc) return rc;
             unsigned long long h_miss = 0;
             SL_HIP_CHECK(ctx, hipMemcpyAsync(&h_miss, misses, 8, hipMemcpyDeviceToHost, ctx->stream));
             SL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -469,29 +469,26 @@ int sl_succ_sweep(sl_ctx* ctx, const SlBellmanArgs& b) {
         if (!S.select_usable) return SL_DECLINED;
         nmiss = S.select_misses;
     }
-#define SL_CACHED(D_, P_)                                                                          \
-    hipLaunchKernelGGL((k_bellman_cached<D_, P_>), dim3(blocks), dim3(256), 0, ctx->stream,        \
-                       ctx->h_model, aux, sc, lo, hi, S.n_actions, usel, asel, b.v_new, b.argmax,  \
-                       b.q, b.stats)
-#define SL_CACHED_D(P_)                                                                            \
-    do {                                                                                           \
-        if (variant == 4) SL_CACHED(4, P_); else if (variant == 3) SL_CACHED(3, P_);               \
-        else if (variant == 2) SL_CACHED(2, P_); else SL_CACHED(1, P_);                            \
-    } while (0)
-    if (policy) SL_CACHED_D(true); else SL_CACHED_D(false);
-#undef SL_CACHED_D
-#undef SL_CACHED
-    SL_HIP_CHECK(ctx, hipGetLastError());
+    int rc = sl_with_dim<4, 3, 2, 1>(variant, [&](auto dt) {
+        constexpr int DT = dt;
+        return sl_with_dim<1, 0>(policy, [&](auto p) {
+            hipLaunchKernelGGL((k_bellman_cached<DT, p != 0>), dim3(blocks), dim3(256), 0, ctx->stream, ctx->h_model,
+                               aux, sc, lo, hi, S.n_actions, usel, asel, b.v_new, b.argmax, b.q, b.stats);
+            SL_HIP_CHECK(ctx, hipGetLastError());
+            return SL_OK;
+        });
+    });
+    if (rc) return rc;
     if (policy && nmiss > 0) {
         const int64_t mblk = (nmiss + 3) / 4;                  // a wavefront per vertex
         const int mblocks = (int)(mblk < 8 * (int64_t)ctx->num_cu ? mblk : 8 * (int64_t)ctx->num_cu);
-#define SL_MISS(D_)                                                                                \
-    hipLaunchKernelGGL(k_succ_policy_miss<D_>, dim3(mblocks), dim3(256), 0, ctx->stream,           \
-                       ctx->h_model, ctx->h_gp, aux, sc, lo, nmiss, miss_list, usel, b.v_new, b.stats)
-        if (variant == 4) SL_MISS(4); else if (variant == 3) SL_MISS(3);
-        else if (variant == 2) SL_MISS(2); else SL_MISS(1);
-#undef SL_MISS
-        SL_HIP_CHECK(ctx, hipGetLastError());
+        rc = sl_with_dim<4, 3, 2, 1>(variant, [&](auto dt) {
+            hipLaunchKernelGGL(k_succ_policy_miss<dt>, dim3(mblocks), dim3(256), 0, ctx->stream, ctx->h_model,
+                               ctx->h_gp, aux, sc, lo, nmiss, miss_list, usel, b.v_new, b.stats);
+            SL_HIP_CHECK(ctx, hipGetLastError());
+            return SL_OK;
+        });
+        if (rc) return rc;
     }
     if (policy) ++S.policy_hits; else ++S.hits;
     if (policy && nmiss > 0)

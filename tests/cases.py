@@ -76,6 +76,40 @@ def oracle_specs(case):
     return policy, dynamics, value, lv
 
 
+def make_case_3d(num_points=(9, 10, 16), dynamics='linear', n_gp=300, seed=0, tau_scale=0.0,
+                 signal_std=0.03, noise_std=0.0005, lengthscale=1.5, initial_radius=0.3):
+    """A three-state case in ``make_case``'s format (test-only: the benchmark families are 1-D, 2-D
+    and 4-D, the kernels are also compiled for d = 3).  A discrete chain of integrators with a
+    little damping, x1' = x1 + h x2, x2' = x2 + h x3, x3' = x3 + h (u - 0.5 x3), under its saturated
+    LQR law; V = x^T P x with P normalised, L_v = |2 P x|.  ``dynamics``: 'linear' or 'gp' (one RBF
+    head over [x, u] trained on noisy samples of the chain, prior: the chain without damping)."""
+    from safe_learning_amd.utilities import dlqr
+    h = 0.1
+    A = np.array([[1., h, 0.], [0., 1., h], [0., 0., 1. - 0.5 * h]])
+    B = np.array([[0.], [0.], [h]])
+    K, P = dlqr(A, B, np.eye(3), np.eye(1))
+    P = P / np.abs(P).max()
+    num_points = [int(n) for n in np.broadcast_to(num_points, (3,))]
+    unit = 2.0 / (np.array(num_points) - 1)
+    case = dict(name='chain3', stack=False, d=3, m=1, limits=[[-1., 1.]] * 3, num_points=num_points,
+                K=-K, saturate=(-1., 1.), P=P, lv=('abs_linear', 2 * P),
+                lf=float(np.linalg.norm(A, 1) + np.linalg.norm(B, 1) * np.linalg.norm(-K, 1)),
+                tau=float(np.sum(unit) / 2) * tau_scale, initial_radius=initial_radius, A_true=A, B_true=B)
+    if dynamics == 'linear':
+        case['dynamics'] = {'kind': 'linear', 'matrix': np.hstack((A, B))}
+    elif dynamics == 'gp':
+        X = np.random.default_rng(seed).uniform(-1, 1, (n_gp, 4))
+        Y = X @ np.hstack((A, B)).T + np.random.default_rng(seed + 1).normal(0, noise_std, (n_gp, 3))
+        A_prior = A.copy()
+        A_prior[2, 2] = 1.0
+        case['dynamics'] = {'kind': 'gp', 'X': X, 'Y': Y, 'variance': signal_std ** 2,
+                            'lengthscales': np.full(4, lengthscale), 'noise_variance': noise_std ** 2,
+                            'prior': np.hstack((A_prior, B)), 'beta': 2.0}
+    else:
+        raise ValueError(dynamics)
+    return case
+
+
 class _LyapunovWithoutValues(oracle.Lyapunov):
     """For timing samples of huge grids: skip the all_points value table (8.6 GB at 128^4)."""
 

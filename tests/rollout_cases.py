@@ -19,6 +19,7 @@ LINEAR_CASES = {
     "1d": ("1d", dict(num_points=41)),
     "pendulum": ("pendulum", dict(num_points=[9, 11], dynamics="linear")),
     "cartpole": ("cartpole", dict(num_points=[3, 4, 5, 3], dynamics="linear")),
+    "chain3": ("chain3", dict(num_points=[3, 4, 5], dynamics="linear")),          # cases.make_case_3d
 }
 
 # ---- Euler dynamics, first steps of every cell ---------------------------------------------------
@@ -45,7 +46,7 @@ ROA_END_STATE_ATOL = 1e-10      # in-ROA end states: two orders above what a 1e-
 
 
 def make(name, kw):
-    return cases.make_case(name, **kw)
+    return cases.make_case_3d(**kw) if name == "chain3" else cases.make_case(name, **kw)
 
 
 def roa_case(key):

@@ -1334,3 +1334,134 @@ def test_bounded_streaming_pass_equals_the_plain_one(sl):
                     if below.any():
                         last = idx[below][np.lexsort((idx[below], keys[lo:hi][below]))[-1]]
                         assert rec[_hip.R_LAST_I] == last
+
+
+# ---------------------------------------------------------------------------------------------
+# three state dimensions: the d = 3 instantiations (the benchmark families are 1-D, 2-D and 4-D)
+# ---------------------------------------------------------------------------------------------
+# cases.make_case_3d on a 9 x 10 x 16 grid (1440 cells, rows of whole bytes).  On the oracle: linear
+# dynamics, tau-scale 0: 1052 cells pass, the level set grows by 770; tau-scale 0.01: 874 pass, it
+# grows by 12; 300-point GP: 1006 pass, it grows by 730; 40-point GP: 870 pass, it grows by 481.
+@pytest.mark.parametrize("tau_scale,min_growth", [(0.0, 500), (0.01, 10)])
+def test_three_dimensions_deterministic_bit_exact(sl, tau_scale, min_growth, monkeypatch):
+    """test_deterministic_bit_exact on a 3-D grid: records from k_det_sweep<d=3>, the update's mask
+    from k_det_rows<3> and (SL_DET_ROWS=0) from k_det_sweep<false, 3, 1, linear>."""
+    from safe_learning_amd.benchmarks import build_lyapunov
+    monkeypatch.delenv("SL_DET_ROWS", raising=False)
+    case = cases.make_case_3d(dynamics="linear", tau_scale=tau_scale)
+    lyap, olyap = build_lyapunov(case), cases.oracle_lyapunov(case)
+    assert_array_equal(lyap.values, olyap.values)
+    values, neg, rec = _engine_records(lyap)
+    assert lyap._ctx.last_kernel().startswith("k_det_sweep<general=0, d=3,"), lyap._ctx.last_kernel()
+    ref_rec, ref_neg = _oracle_all(olyap)
+    assert_array_equal(values, olyap.values)
+    assert_array_equal(rec, ref_rec)
+    assert_array_equal(neg, ref_neg)
+    _compare_safe_sets(lyap, olyap, 0)
+    assert lyap._ctx.last_kernel().startswith("k_det_rows<d=3>"), lyap._ctx.last_kernel()
+    _assert_non_degenerate(case, ref_neg, olyap, min_growth)
+    monkeypatch.setenv("SL_DET_ROWS", "0")
+    cells = build_lyapunov(case)
+    assert_array_equal(_neg_mask_of_update(cells), ref_neg)
+    assert cells._ctx.last_kernel().startswith("k_det_sweep<general=0, d=3,"), cells._ctx.last_kernel()
+    assert_array_equal(cells.safe_set, olyap.safe_set)
+    assert cells.c_max == olyap.c_max
+
+
+def test_three_dimensions_can_shrink_false_and_batches(sl, small_batches):
+    """test_can_shrink_false_and_batches on the 3-D grid: quadratic V on rows of whole bytes, so the
+    streaming passes (k_select_hist<3>, k_finalize_dev<3>) recompute the keys from the cell index."""
+    from safe_learning_amd.benchmarks import build_lyapunov
+    case = cases.make_case_3d(dynamics="linear", tau_scale=0.01)
+    lyap, olyap = build_lyapunov(case), cases.oracle_lyapunov(case)
+    assert lyap._values_implicit
+    rng = np.random.default_rng(3)
+    sizes = []
+    for step in range(4):
+        if step == 1:        # pretend earlier verification marked scattered far-away cells safe
+            extra = rng.choice(lyap.discretization.nindex, 300, replace=False)
+            lyap.safe_set[extra] = True
+            olyap.safe_set[extra] = True
+        if step == 2:        # a stricter threshold: the safe set may not shrink
+            lyap.tau = olyap.tau = case["tau"] * 4
+        if step == 3:
+            lyap.tau = olyap.tau = 0.0
+        lyap.update_safe_set(can_shrink=(step == 0))
+        olyap.update_safe_set(can_shrink=(step == 0))
+        assert_array_equal(lyap.safe_set, olyap.safe_set)
+        assert lyap.c_max == olyap.c_max
+        sizes.append(int(olyap.safe_set.sum()))
+    # (oracle: 28, 310, 310, 933 safe cells)
+    assert sizes[0] > 16 and sizes[1] >= sizes[0] + 200 and sizes[2] == sizes[1] and sizes[3] >= sizes[2] + 500
+
+
+def test_three_dimensions_refinement_survives_a_plain_update(sl, small_batches):
+    """test_refinement_survives_a_plain_update_that_must_not_shrink on the 3-D grid
+    (k_refinement_carry<3>)."""
+    from safe_learning_amd.benchmarks import build_specs
+    case = cases.make_case_3d(dynamics="linear", tau_scale=0.01)
+    init = np.zeros(int(np.prod(case["num_points"])), dtype=bool)
+    init[cases.initial_safe_mask(case)] = True
+    policy, dynamics, value, lv = build_specs(case)
+    lyap = sl.Lyapunov(sl.GridWorld(case["limits"], case["num_points"]), value, dynamics, case["lf"],
+                       lv, case["tau"], policy, initial_set=init, adaptive=True)
+    opolicy, odynamics, ovalue, olv = cases.oracle_specs(case)
+    olyap = oracle.Lyapunov(oracle.GridWorld(case["limits"], case["num_points"]), ovalue, odynamics,
+                            case["lf"], olv, case["tau"], opolicy, initial_set=init, adaptive=True)
+    steps = [dict(can_shrink=True, max_refinement=16, safety_factor=1.5),     # adaptive: some N(x) > 1
+             dict(can_shrink=False),                                          # plain, stricter tau
+             dict(can_shrink=False),                                          # plain, looser tau
+             dict(can_shrink=False, max_refinement=16, safety_factor=1.5),    # adaptive on top of it
+             dict(can_shrink=True)]                                           # plain reset: N = safe
+    t0 = 0.4 * case["tau"]
+    taus = [t0, 1.5 * t0, 0.5 * t0, 0.5 * t0, t0]
+    seen_large = False
+    for step, tau in zip(steps, taus):
+        lyap.tau = olyap.tau = tau
+        lyap.update_safe_set(**step)
+        olyap.update_safe_set(**step)
+        assert_array_equal(lyap.safe_set, olyap.safe_set)
+        assert_array_equal(lyap._refinement, olyap._refinement)
+        assert lyap.c_max == olyap.c_max
+        if "max_refinement" not in step and not step["can_shrink"]:
+            seen_large = seen_large or bool((olyap._refinement > 1).any())
+    assert seen_large, "no N(x) > 1 was carried through a plain update: the scenario tests nothing"
+
+
+@pytest.mark.parametrize("n_gp,cfg,kernel", [
+    (40, None, "k_gp_small<"),
+    (300, None, "k_gp_sweep4<"),
+    (300, "3", "k_gp_sweep<"),
+])
+def test_three_dimensions_gp_dynamics(sl, n_gp, cfg, kernel, monkeypatch):
+    """test_gp_dynamics (same comparisons, tolerances and flip allowance) on the 3-D grid, one case
+    per GP kernel family."""
+    from safe_learning_amd.benchmarks import build_lyapunov
+    min_growth = 100
+    if cfg is None:
+        monkeypatch.delenv("SL_GP_CFG", raising=False)
+    else:
+        monkeypatch.setenv("SL_GP_CFG", cfg)
+    case = cases.make_case_3d(dynamics="gp", n_gp=n_gp, tau_scale=0.0005)
+    lyap, olyap = build_lyapunov(case), cases.oracle_lyapunov(case)
+    values, neg, rec = _engine_records(lyap)
+    ran = lyap._ctx.last_kernel()
+    assert ran.startswith(kernel) and "d=3, m=1" in ran and "general=1" not in ran, ran
+    ref_rec, ref_neg = _oracle_all(olyap)
+    d = case["d"]
+    assert_array_equal(values, olyap.values)
+    assert_allclose(rec[:, 2:2 + d], ref_rec[:, 2:2 + d], rtol=RTOL_GP, atol=1e-12)   # mean
+    assert_allclose(rec[:, 2 + d:], ref_rec[:, 2 + d:], rtol=1e-7, atol=1e-12)        # beta*sigma
+    var, ref_var = (rec[:, 2 + d:] / 2.0) ** 2, (ref_rec[:, 2 + d:] / 2.0) ** 2
+    assert_allclose(var, ref_var, rtol=1e-6, atol=1e-16)                              # variance
+    assert_allclose(rec[:, :2], ref_rec[:, :2], rtol=1e-7, atol=1e-12)
+    flips, _ = _check_masks(neg, ref_neg, rec, ref_rec)
+    _compare_safe_sets(lyap, olyap, flips, neg)
+    ran = lyap._ctx.last_kernel()
+    assert ran.startswith(kernel) and "d=3, m=1" in ran and "general=1" not in ran, ran
+    _assert_non_degenerate(case, ref_neg, olyap, min_growth)
+    if flips == 0:
+        init = np.zeros(len(neg), dtype=bool)
+        init[cases.initial_safe_mask(case)] = True
+        assert int((lyap.safe_set & ~init).sum()) >= min_growth
+        assert neg[lyap.safe_set & ~init].all()

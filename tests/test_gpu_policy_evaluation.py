@@ -30,7 +30,8 @@ def sl():
 def _pair(sl, name, nv, gamma=0.95, project=True, **kw):
     """Engine and oracle PolicyIteration on the same case (value table: random, non-positive)."""
     from safe_learning_amd.benchmarks import build_specs
-    case = cases.make_case(name, num_points=nv, **kw)
+    make = cases.make_case_3d if name == "chain3" else (lambda **k: cases.make_case(name, **k))
+    case = make(num_points=nv, **kw)
     d, limits = case["d"], case["limits"]
     qmat = -scipy.linalg.block_diag(np.eye(d), 0.1 * np.eye(1))
     vgrid, ovgrid = sl.GridWorld(limits, nv), oracle.GridWorld(limits, nv)
@@ -122,6 +123,7 @@ def test_lp_equivalence(sl, name, nv, kw):
     ("cartpole", [5, 6, 5, 6], dict(dynamics="analytic")),
     ("pendulum", [13, 13], dict(n_gp=70)),
     ("cartpole", [4, 5, 4, 5], dict(n_gp=90)),
+    ("chain3", [5, 6, 7], dict(dynamics="linear")),           # k_policy_operator_rows<3>, rows of 4 entries
 ])
 def test_rows_versus_sweep_and_oracle(sl, name, nv, kw):
     from test_policy_rows_host import load_shim, _Rows
@@ -136,7 +138,13 @@ def test_rows_versus_sweep_and_oracle(sl, name, nv, kw):
     got = shim.combine(cols, w, r, rl.gamma, table)
     print("compared sweep: %s" % kernel)
     assert kernel
-    if "n_gp" in kw:
+    # The rows take their weights from sl_tri_locate_fast<D>, as the sweeps with compile-time dimensions
+    # do: bit for bit.  A 3-D grid is swept by the runtime-dimension k_bellman<A, 0, 0>, whose
+    # sl_tri_eval sums the same barycentric weights in another order: agreement to rounding (the
+    # bound of the GP cases), and the kernel name says that this is the sweep compared.
+    runtime_dims = name == "chain3"
+    assert ("d=3" in kernel) == runtime_dims, kernel
+    if "n_gp" in kw or runtime_dims:
         assert_allclose(got, expected, rtol=1e-12, atol=1e-12 * np.abs(expected).max(), err_msg=kernel)
     else:
         assert_array_equal(got, expected, err_msg=kernel)

@@ -257,3 +257,41 @@ def test_policy_evaluation_selects_cached_entries(sl, name, kw, nv, na):
     assert "k_bellman_cached" not in rl._ctx.last_kernel()
     rl_u.value_iteration()
     assert_array_equal(vf._host_parameters(), vf_u._host_parameters())
+
+
+def test_three_dimensional_max_sweeps_recompute_and_commit_no_cache(sl):
+    """A 3-D grid has no k_bellman instantiation that locates with compile-time dimensions: its max
+    sweeps run the runtime-dimension flavour, which writes nothing into the successor cache.  Every
+    sweep therefore recomputes, no cache is committed (a cache nobody filled must never serve a
+    sweep), and the tables equal a context without a cache bit for bit; one sweep against the
+    oracle as in test_cached_sweeps_against_the_oracle."""
+    nv, na = [5, 6, 9], 3
+    case = cases.make_case_3d(num_points=nv, dynamics="gp", n_gp=60)
+    actions = np.linspace(-1, 1, na)[:, None]
+    rl, orl, vf, ovf = _rl_pair(sl, case, nv)
+    rl_u, _, vf_u, _ = _rl_pair(sl, case, nv, cache=False)
+    v0 = ovf.parameters.copy()
+    cached = _loop(rl, vf, actions, 4, v0)
+    plain = _loop(rl_u, vf_u, actions, 4, v0)
+    for sweep, (c, u) in enumerate(zip(cached, plain)):
+        assert_array_equal(c[0], u[0], err_msg="value table, sweep %d" % sweep)
+        assert_array_equal(c[1], u[1], err_msg="greedy policy, sweep %d" % sweep)
+        assert c[2] == u[2], (sweep, c[2], u[2])
+        assert c[3].startswith("k_bellman<") and "d=3" in c[3], c[3]
+        assert "k_bellman_cached" not in c[3] and "k_bellman_cached" not in u[3]
+    info = rl.successor_cache_info
+    assert info["fills"] == 0 and info["valid"] == 0 and info["hits"] == 0, info
+    # the tables move from sweep to sweep (the comparison above is not one of constants)
+    assert not np.array_equal(cached[0][0], cached[3][0])
+    # one sweep against the oracle
+    orl.policy = oracle.Triangulation(ovf.discretization, np.zeros((ovf.discretization.nindex, 1)))
+    x = orl.state_space
+    ok = np.ones(len(x), dtype=bool)
+    for action in actions:
+        ok &= ~ambiguous_points(ovf, orl.dynamics(x, np.broadcast_to(action, (len(x), 1)))[0])
+    exclusions.report("test_three_dimensional_max_sweeps_recompute_and_commit_no_cache", ok, "successor")
+    vf.parameters = ovf.parameters.copy()
+    oq, _ = orl.discrete_policy_optimization(actions)
+    rl.value_iteration(actions)
+    assert "k_bellman_cached" not in rl._ctx.last_kernel()
+    assert_allclose(vf.parameters[ok, 0], oq.max(axis=1)[ok], rtol=1e-9, atol=1e-12)
