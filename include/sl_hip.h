@@ -560,6 +560,27 @@ SL_API int  sl_rollout(sl_ctx* ctx, int64_t lo, int64_t hi, const double* d_star
 SL_API int  sl_rollout_mask(sl_ctx* ctx, int64_t n, int d, const double* d_state,
                     const double* h_equilibrium /* [d] */, double tol, uint64_t* d_bits, int64_t* d_count);
 
+/* ---- discounted returns of the closed loop (examples/utilities.py:522-545 reward_rollout) ------ *
+ * sl_reward_rollout sums, for the trajectories [lo, hi) under the model of sl_model_set,
+ *     d_sum[i] = sum_t d_weights[t] * reward([x_t, policy(x_t)]),   x_{t+1} = f(x_t, policy(x_t))
+ *   sequentially from 0.0 (product rounded, then added: no contraction), with the model's `reward`
+ *   (kind SL_V_QUADRATIC on [x, u]), and stops as the reference does: after the FIRST step t at
+ *   which max over all trajectories of |d_weights[t] * reward| < tol (that term is included), for
+ *   every trajectory at once, else after `horizon` terms.  A NaN term never satisfies the test.
+ *   d_weights [horizon] on the device: the caller's discount ** t.
+ *   d_start as for sl_rollout (NULL: the grid points); d_sum [hi - lo] out; d_state [hi - lo][d]
+ *   scratch and out: the state after the dynamics step that follows the last summed term (may be
+ *   d_start).  *h_steps (host, may be NULL) = number of terms summed, *h_converged = 1 when the
+ *   test stopped the loop.
+ *   One thread keeps a trajectory's state and sum in registers for the steps of a launch; the
+ *   per-step maxima are read once per launch, and the launch that contains the stopping step is
+ *   run once more from its inputs, cut there, so the sums are those of the sequential loop
+ *   whatever steps_per_launch is (0: the library chooses, 32 at most; never more than 128).
+ *   Policies, SL_DYN_GP and the per-vertex TABLE: as for sl_rollout (NETWORK: step by step).    */
+SL_API int  sl_reward_rollout(sl_ctx* ctx, int64_t lo, int64_t hi, const double* d_start, int horizon,
+                    const double* d_weights, double tol, int steps_per_launch, double* d_sum,
+                    double* d_state, int64_t* h_steps, int* h_converged);
+
 /* ---- multi-GPU collectives directly on RCCL ----------------------------- *
  * For callers without torch.distributed (the Python package issues the same exchanges through
  * torch.distributed, backend "nccl" = RCCL).  One communicator per context, one rank per GPU; every

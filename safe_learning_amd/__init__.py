@@ -10,5 +10,5 @@ from .functions import *          # noqa: F401,F403
 from .lyapunov import *           # noqa: F401,F403
 from .reinforcement_learning import *   # noqa: F401,F403
 from . import utilities, distributed, kernels
-from .utilities import compute_roa, compute_trajectory
+from .utilities import compute_roa, compute_trajectory, reward_rollout
 from ._hip import HipEngineError

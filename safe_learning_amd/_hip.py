@@ -200,6 +200,8 @@ SIGNATURES = {
     # closed-loop rollouts
     "sl_rollout": (_int, (_vp, _i64, _i64, _vp, _int, _int, _vp, _vp, _vp)),
     "sl_rollout_mask": (_int, (_vp, _i64, _int, _vp, c_double_p, _dbl, _vp, _vp)),
+    "sl_reward_rollout": (_int, (_vp, _i64, _i64, _vp, _int, _vp, _dbl, _int, _vp, _vp, C.POINTER(_i64),
+                                 C.POINTER(_int))),
     # RCCL collectives
     "sl_comm_unique_id": (_int, (C.c_char_p,)),
     "sl_comm_init": (_int, (_vp, C.c_char_p, _int, _int)),
@@ -603,6 +605,15 @@ class Context(object):
                 raise ValueError("equilibrium has %d entries, the states %d" % (equilibrium.size, d))
         self.lib.sl_rollout_mask(self.handle, int(n), int(d), _ptr(d_state), pe, float(tol), _ptr(d_bits),
                                  _ptr(d_count))
+
+    def reward_rollout(self, lo, hi, d_start, horizon, d_weights, tol, d_sum, d_state, steps_per_launch=0):
+        """``sl_reward_rollout``: the discounted returns of the trajectories ``[lo, hi)`` under the model
+        and its quadratic reward, with the reference's stopping rule -> ``(steps, converged)``."""
+        steps, converged = _i64(0), _int(0)
+        self.lib.sl_reward_rollout(self.handle, lo, hi, _ptr(d_start), int(horizon), _ptr(d_weights), float(tol),
+                                   int(steps_per_launch), _ptr(d_sum), _ptr(d_state), C.byref(steps),
+                                   C.byref(converged))
+        return int(steps.value), bool(converged.value)
 
     def synchronize(self):
         self.lib.sl_ctx_synchronize(self.handle)

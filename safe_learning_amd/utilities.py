@@ -1,11 +1,12 @@
 """Helpers kept from the reference's utilities (``safe_learning/utilities.py``) and closed-loop
-simulation on the GPU: ``compute_trajectory`` (``utilities.py:519-583``) and the ``compute_roa`` of
-the notebooks (``examples/utilities.py:654-686``)."""
+simulation on the GPU: ``compute_trajectory`` (``utilities.py:519-583``) and the ``compute_roa``
+(``examples/utilities.py:654-686``) and ``reward_rollout`` (``examples/utilities.py:522-545``) of the
+notebooks."""
 
 import numpy as np
 import scipy.linalg
 
-__all__ = ['dlqr', 'batchify', 'compute_trajectory', 'compute_roa']
+__all__ = ['dlqr', 'batchify', 'compute_trajectory', 'compute_roa', 'reward_rollout']
 
 
 def dlqr(a, b, q, r):
@@ -206,3 +207,108 @@ def compute_roa(grid, closed_loop_dynamics, horizon=100, tol=1e-3, equilibrium=N
         return roa
     trajectories = states.permute(1, 2, 0)                           # (n, d, horizon), a view
     return roa, (trajectories if keep else trajectories.cpu().numpy())
+
+
+def reward_rollout(grid, closed_loop_dynamics, reward_function, discount, horizon=250, tol=1e-3,
+                   full_output=False, steps_per_launch=0):
+    """The discounted return of the closed loop from every state of ``grid``
+    (``examples/utilities.py:522-545``)::
+
+        rollout = 0
+        for t in range(horizon):
+            temp = (discount ** t) * reward(x, policy(x));  rollout += temp
+            if max over all states of |temp| < tol: converged, stop
+            x = dynamics(x, policy(x))
+
+    The stopping rule is global: the step at which the loop ends depends on the whole point set
+    passed in, as in the reference.  A NaN or an infinite term never satisfies the test.
+
+    ``grid``: a ``GridWorld`` (all its points) or an ``[n, d]`` array of start states.
+    ``closed_loop_dynamics``: a ``(dynamics, policy)`` pair of specs as for ``compute_roa`` - the fused
+    kernel; ``reward_function`` is then a ``QuadraticFunction`` on ``[x, u]`` (the notebooks'
+    ``QuadraticFunction(block_diag(-Q, -R))``) - or any callable on ``[n, d]`` states with a callable
+    ``reward_function`` on states returning ``[n]`` or ``[n, 1]`` (a GP's mean ...), stepped on
+    device tensors with one maximum read back per step.  The weights ``discount ** t`` are computed
+    on the host with that Python expression, so they are the reference's bit for bit.
+
+    Returns ``rollout [n]`` (float64); with ``full_output=True`` ``(rollout, steps, converged)``:
+    the number of reward terms summed and whether the test stopped the loop.  ``steps_per_launch``
+    (0: chosen by the library) never changes the result.  Device-tensor start states keep the
+    result on the device.  Nothing is printed."""
+    import copy
+    import torch
+    from . import _evaluate
+    from .functions import GridWorld, QuadraticFunction
+    horizon = int(horizon)
+    if horizon < 1:
+        raise ValueError('horizon counts the reward terms: it must be at least 1')
+    if not np.isfinite(discount):
+        raise ValueError('discount must be finite, got %r' % (discount,))
+    keep = isinstance(grid, torch.Tensor)
+    pair = isinstance(closed_loop_dynamics, (tuple, list))
+    spec_reward = isinstance(reward_function, QuadraticFunction)
+    if pair and len(closed_loop_dynamics) != 2:
+        raise ValueError('closed_loop_dynamics must be a (dynamics, policy) pair or a callable')
+    if pair and not spec_reward:
+        raise TypeError('a (dynamics, policy) pair of specs takes the fused kernel, which needs '
+                        'reward_function as a QuadraticFunction on [x, u], got %r; for any other reward pass '
+                        'closed_loop_dynamics and reward_function both as callables on states'
+                        % (reward_function,))
+    if not pair and not callable(closed_loop_dynamics):
+        raise TypeError('closed_loop_dynamics must be a (dynamics, policy) pair of specs or a callable')
+    if not pair and spec_reward:
+        raise TypeError('a QuadraticFunction reward spec is a function of [x, u] and goes with a (dynamics, '
+                        'policy) pair of specs; with a callable closed_loop_dynamics pass a callable reward on '
+                        'states, e.g. `lambda x: reward(x, policy(x))`')
+    if not pair and not callable(reward_function):
+        raise TypeError('reward_function must be a callable on states when closed_loop_dynamics is one')
+    weights = np.array([discount ** t for t in range(horizon)], dtype=np.float64)
+    if pair:
+        dynamics, policy = closed_loop_dynamics
+        _check_pair(dynamics, policy)
+        _check_single_process()
+        d = int(grid.ndim) if isinstance(grid, GridWorld) else int(np.shape(grid)[-1])
+        ctx, builder = _engine(d)
+        world, start, n, d = _start_points(ctx, grid)
+        if n < 1:
+            raise ValueError('reward_rollout needs at least one start state')
+        if world is not None:
+            builder.grid = copy.copy(world)
+        p = d + _evaluate._policy_output_dim(policy)
+        if int(reward_function.matrix.shape[0]) != p:
+            raise ValueError('the reward is quadratic in %d inputs, [x, u] has %d'
+                             % (reward_function.matrix.shape[0], p))
+        builder.upload(policy, dynamics, QuadraticFunction(np.eye(d)), reward=reward_function)
+        dev = ctx.torch_device
+        rollout = torch.empty((n,), dtype=torch.float64, device=dev)
+        state = torch.empty((n, d), dtype=torch.float64, device=dev)
+        d_weights = torch.from_numpy(weights).to(dev)
+        steps, converged = ctx.reward_rollout(0, n, start, horizon, d_weights, tol, rollout, state,
+                                              steps_per_launch)
+    else:
+        _check_single_process()
+        ctx = _evaluate._ctx()
+        points = grid.all_points if isinstance(grid, GridWorld) else grid
+        if np.ndim(points) != 2:
+            raise ValueError('start states must be an [n, d] array')
+        states = _evaluate._to_device(ctx, points)
+        if states.shape[0] < 1:
+            raise ValueError('reward_rollout needs at least one start state')
+        rollout = torch.zeros((states.shape[0],), dtype=torch.float64, device=ctx.torch_device)
+        steps, converged = horizon, False
+        for t in range(horizon):
+            reward = reward_function(states)
+            reward = _evaluate._to_device(ctx, reward[0] if isinstance(reward, tuple) else reward).reshape(-1)
+            if reward.shape[0] != rollout.shape[0]:
+                raise ValueError('reward_function must return [n] or [n, 1] values, got %d for %d states'
+                                 % (reward.shape[0], rollout.shape[0]))
+            temp = float(weights[t]) * reward
+            rollout += temp
+            if float(temp.abs().max()) < tol:                        # (a NaN maximum compares false)
+                steps, converged = t + 1, True
+                break
+            nxt = closed_loop_dynamics(states)
+            states = _evaluate._to_device(ctx, nxt[0] if isinstance(nxt, tuple) else nxt)
+    if not keep:
+        rollout = rollout.cpu().numpy()
+    return (rollout, steps, converged) if full_output else rollout

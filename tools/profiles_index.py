@@ -110,7 +110,10 @@ def main():
              "* `r06_box_variance_ab.txt`: the round-5 library and the tree alternating on ONE box (C3, C4-lin, C4-det): boxes of the pool "
              "differ by 1-4 %, the libraries by < 0.3 %.",
              "* `rollout_roa.md`, `rollout_kernel_stats.md`: closed-loop rollouts (`k_rollout`, csrc/sl_rollout.hip) against the stepwise "
-             "composition of the point evaluations and against the sweep of the same cells (`tools/rollout_probe.py`; DESIGN.md 4.2b).", ""]
+             "composition of the point evaluations and against the sweep of the same cells (`tools/rollout_probe.py`; DESIGN.md 4.2b).",
+             "* `reward_rollout.md`: discounted returns (`k_reward_rollout`, `k_reward_fold`, csrc/sl_rollout.hip) against the stepwise "
+             "composition of the point evaluations and against `k_rollout` over the same steps, with the registers / LDS of the new "
+             "kernels (`tools/reward_rollout_probe.py`; DESIGN.md 4.2b).", ""]
     for key in sorted(by_round):
         text.append("* %s: %s" % (key, ", ".join("`%s`" % n for n in by_round[key])))
     with open(os.path.join(P, "README.md"), "w") as f:
