@@ -581,6 +581,40 @@ SL_API int  sl_reward_rollout(sl_ctx* ctx, int64_t lo, int64_t hi, const double*
                     const double* d_weights, double tol, int steps_per_launch, double* d_sum,
                     double* d_state, int64_t* h_steps, int* h_converged);
 
+/* ---- training a LyapunovNetwork (examples/lyapunov_function_learning.ipynb cells 25 and 30: the
+ * two optimizer.minimize(..., var_list=lyapunov_function.parameters)) -------------------------- *
+ * Both calls work on the network of sl_network_set alone (no sl_model_set needed); d is the width
+ * of the point rows and must be the network's input width, at most SL_MAX_STATE_DIM as in the sweeps.
+ * Without a network, with m <= 0 or with another d they return SL_ERR_INVALID.
+ * sl_nn_param_grad: for every layer l the [out_l][in_l] matrix
+ *     G_l = sum_{i < m} d_coeff[i] * dV(p_i)/dK_l,   p_i = d_points [m][d],
+ *   concatenated, row-major, unpadded - the layout sl_network_set takes h_kernels in - into
+ *   d_grad_kernels.  FP64 on the matrix cores; every workgroup adds its points into a slice of a
+ *   scratch area the context owns and a second kernel adds the slices in a fixed order (no atomics):
+ *   two calls with the same inputs return the same bits.  (The step from the layer kernels
+ *   [W^T W + eps I ; W'] to the variables W, W' is the caller's: dW = W (G_top + G_top^T),
+ *   dW' = G_bottom.)
+ * sl_nn_loss: the losses of a batch of m samples and the coefficients that turn them into a
+ *   gradient through sl_nn_param_grad, with V from the matrix-core evaluation of the sweeps.
+ *   SL_NN_LOSS_ROA (cell 30): states d_states [m][d], successors d_next [m][d], labels l_i in {0, 1}
+ *     (d_labels_or_targets [m], as doubles), class weights w_i (d_class_weights [m]):
+ *       classifier_i = w_i max(-(2 l_i - 1)(safe_level - V(x_i)), 0)
+ *       decrease_i   = l_i max(V(x_i+) - V(x_i), 0) / (V(x_i) + eps)     (denominator: a constant)
+ *       objective    = mean_i (classifier_i + lagrange * decrease_i)
+ *     d_losses[3] = the means {objective, classifier, decrease}; d_coeff [2 m] = d objective / d V(x_i)
+ *     then d objective / d V(x_i+), each already divided by m; d_points (may be NULL) [2 m][d] = the
+ *     point list [x; x+] those coefficients belong to.
+ *   SL_NN_LOSS_ABS (cell 25): objective = mean_i |V(x_i) - target_i| with the targets in
+ *     d_labels_or_targets; d_next and d_class_weights are NULL, the three scalars unused;
+ *     d_losses = {objective, objective, 0}, d_coeff [m] = sign(V(x_i) - target_i) / m, d_points [m][d].
+ *   max(., 0) and |.| have derivative 0 at the kink (as TensorFlow's gradients have). */
+enum sl_nn_loss_kind { SL_NN_LOSS_ABS = 1, SL_NN_LOSS_ROA = 2 };
+SL_API int  sl_nn_param_grad(sl_ctx* ctx, int64_t m, int d, const double* d_points, const double* d_coeff,
+                    double* d_grad_kernels);
+SL_API int  sl_nn_loss(sl_ctx* ctx, int kind, int64_t m, int d, const double* d_states, const double* d_next,
+                    const double* d_labels_or_targets, const double* d_class_weights, double safe_level,
+                    double lagrange, double eps, double* d_losses, double* d_coeff, double* d_points);
+
 /* ---- multi-GPU collectives directly on RCCL ----------------------------- *
  * For callers without torch.distributed (the Python package issues the same exchanges through
  * torch.distributed, backend "nccl" = RCCL).  One communicator per context, one rank per GPU; every
@@ -617,6 +651,12 @@ SL_API int  sl_debug_fp64_rate(sl_ctx* ctx, int which, int iters, double* h_out)
  * h_xs [p][n] (row q = input dimension q): lets the tests compare an incrementally extended head
  * (sl_gp_append_point) with a fresh upload bit for bit. */
 SL_API int  sl_debug_gp_inputs(sl_ctx* ctx, int head, double* h_xs);
+/* The scratch area of sl_nn_param_grad / sl_nn_loss (in the context's scratch buffer, which sl_eval_points
+ * uses too) lies between two guard zones that every such call writes in front of its kernels, one directly
+ * before the first and one directly behind the last double its kernels own: *h_bytes = the size of the
+ * area of the last such call (0: none yet, or the front zone is damaged), *h_guards_intact = 1 when the
+ * kernels of that call wrote neither in front of nor behind the area.  Synchronises the stream. */
+SL_API int  sl_debug_nn_train_scratch(sl_ctx* ctx, int64_t* h_bytes, int* h_guards_intact);
 
 #ifdef __cplusplus
 }

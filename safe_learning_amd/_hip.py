@@ -29,6 +29,7 @@ V_QUADRATIC, V_TRI, V_NETWORK = 1, 2, 3
 LIP_CONST, LIP_ABS_LINEAR, LIP_NORM_LINEAR, LIP_ABS_GRAD, LIP_NORM_GRAD = 0, 1, 2, 3, 4
 LF_CONST, LF_AFFINE_NORM1 = 0, 1
 EVAL_VALUE, EVAL_POLICY, EVAL_DYNAMICS, EVAL_DECREASE, EVAL_LV = 1, 2, 3, 4, 5
+NN_LOSS_ABS, NN_LOSS_ROA = 1, 2
 
 c_double_p = C.POINTER(C.c_double)
 
@@ -202,6 +203,9 @@ SIGNATURES = {
     "sl_rollout_mask": (_int, (_vp, _i64, _int, _vp, c_double_p, _dbl, _vp, _vp)),
     "sl_reward_rollout": (_int, (_vp, _i64, _i64, _vp, _int, _vp, _dbl, _int, _vp, _vp, C.POINTER(_i64),
                                  C.POINTER(_int))),
+    # training a LyapunovNetwork
+    "sl_nn_param_grad": (_int, (_vp, _i64, _int, _vp, _vp, _vp)),
+    "sl_nn_loss": (_int, (_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _vp, _vp, _vp)),
     # RCCL collectives
     "sl_comm_unique_id": (_int, (C.c_char_p,)),
     "sl_comm_init": (_int, (_vp, C.c_char_p, _int, _int)),
@@ -215,6 +219,7 @@ SIGNATURES = {
     "sl_debug_mfma4": (_int, (_vp, _int, c_double_p, c_double_p, c_double_p, _int, c_double_p)),
     "sl_debug_fp64_rate": (_int, (_vp, _int, _int, c_double_p)),
     "sl_debug_gp_inputs": (_int, (_vp, _int, c_double_p)),
+    "sl_debug_nn_train_scratch": (_int, (_vp, C.POINTER(_i64), C.POINTER(_int))),
 }
 EXPORTS = list(SIGNATURES)
 
@@ -614,6 +619,25 @@ class Context(object):
                                    int(steps_per_launch), _ptr(d_sum), _ptr(d_state), C.byref(steps),
                                    C.byref(converged))
         return int(steps.value), bool(converged.value)
+
+    def nn_param_grad(self, m, d, d_points, d_coeff, d_grad_kernels):
+        """``sl_nn_param_grad``: ``sum_i coeff_i dV(p_i)/dK_l`` of every layer of the uploaded network,
+        concatenated ``[out_l][in_l]`` (the layout of ``network_set``)."""
+        self.lib.sl_nn_param_grad(self.handle, int(m), int(d), _ptr(d_points), _ptr(d_coeff), _ptr(d_grad_kernels))
+
+    def nn_loss(self, kind, m, d, d_states, d_next, d_labels_or_targets, d_class_weights, safe_level, lagrange,
+                eps, d_losses, d_coeff, d_points=None):
+        """``sl_nn_loss``: the three means into ``d_losses``, the coefficients of ``[x; x+]`` into
+        ``d_coeff`` and that point list into ``d_points``."""
+        self.lib.sl_nn_loss(self.handle, int(kind), int(m), int(d), _ptr(d_states), _ptr(d_next),
+                            _ptr(d_labels_or_targets), _ptr(d_class_weights), float(safe_level), float(lagrange),
+                            float(eps), _ptr(d_losses), _ptr(d_coeff), _ptr(d_points))
+
+    def nn_train_scratch(self):
+        """``sl_debug_nn_train_scratch`` -> (bytes of the scratch area, its guard zones are intact)."""
+        nbytes, intact = _i64(0), _int(0)
+        self.lib.sl_debug_nn_train_scratch(self.handle, C.byref(nbytes), C.byref(intact))
+        return int(nbytes.value), bool(intact.value)
 
     def synchronize(self):
         self.lib.sl_ctx_synchronize(self.handle)

@@ -3,8 +3,10 @@
 //
 // Both kernels run the network on the FP64 matrix cores (see nn_mfma_eval).  The posterior (mean,
 // error) of GP dynamics comes from a first pass of k_gp_sweep that only emits its per-cell
-// records; deterministic dynamics are evaluated here.
+// records; deterministic dynamics are evaluated here.  Below them: the training step of
+// examples/lyapunov_function_learning.ipynb (k_nn_loss, k_nn_param_grad).
 #include "sl_common.h"
+#include "sl_nn_train.h"
 
 __device__ __forceinline__ void nn_lv_from_grad(int kind, int d, const double* g, double* lv) {
     if (kind == SL_LIP_ABS_GRAD) {
@@ -276,5 +278,415 @@ int sl_nn_check_launch(sl_ctx* ctx, const SlSweepArgs& a, const double* d_record
     if (rc) return rc;
     sl_note_kernel(ctx, d_records != nullptr, "k_nn_check_mfma<layers=%d, d=%d>", ctx->h_net.nlayers,
                    variant);
+    return SL_OK;
+}
+
+// ---- training: sum_m c_m dV(p_m)/dK_l and the notebook's losses (sl_nn_param_grad, sl_nn_loss) ----
+//
+// G_l = sum_m c_m t_l(p_m) h_{l-1}(p_m)^T with t_l = dV/d(pre-activation of layer l), the quantity
+// the backward chain of nn_mfma_eval carries, and h_{l-1} the layer's input (h_0 = p): per layer
+// one more FP64 MFMA GEMM, [out x cells] . [cells x in], whose reduction dimension is the cells.
+//
+// A workgroup of four wavefronts owns 64 points at a time.  Every wavefront runs the forward and
+// the transposed chain of its 16 points as nn_mfma_eval does (point on the lane, feature in the
+// register).  The outer product needs the point along the MFMA's k, so at every layer of the way
+// back the workgroup's c t_l and then its h_{l-1} cross one [64 points][64 features] staging tile
+// in LDS behind the weights: c t_l is written and wavefront w takes the A fragments of ITS 16 output
+// rows (16 fb = 16 w) into registers, the tile is overwritten with h_{l-1} and read back as B
+// fragments.  The 16 accumulator tiles of a [64 x 64] layer are thereby shared out over the four
+// wavefronts (4 tiles = 16 registers per lane and layer, kept for the whole grid-stride loop)
+// instead of standing 4 x 16 tiles beside each wavefront's activations, and one staging tile
+// (33 KB) rather than two keeps the largest network (four layers of 64: 108 KB of weights) inside
+// the 160 KB of a CU.  No atomics: a workgroup writes its G to its own slice of the context's
+// scratch buffer and k_nn_grad_reduce adds the slices in ascending order.
+// (The two chains are written out again here and not shared with nn_mfma_eval as helpers: with helpers
+// the register allocation of the sweeps' kernels changes - k_nn_values_mfma<2..4> go from 121 - 125
+// VGPRs without scratch to 256 with it; profiles/lyapunov_training.md.)
+#define SL_NNG_WAVES 4
+#define SL_NNG_CELLS (16 * SL_NNG_WAVES)
+#define SL_NNG_STRIDE (SL_NN_MAXW + 2)          // staging row of one point (+2: LDS bank spread)
+
+template <int NL>
+__global__ __launch_bounds__(64 * SL_NNG_WAVES) void k_nn_param_grad(SlAux aux, int64_t m, int d,
+                                                                     const double* __restrict__ points,
+                                                                     const double* __restrict__ coeff,
+                                                                     double* __restrict__ partials, int total) {
+    extern __shared__ __attribute__((aligned(16))) double wl[];
+    const SlNet& net = *aux.net;
+    nn_stage_weights(net, wl);
+    double* __restrict__ stage = wl + net.wtotal;
+    const int lane = threadIdx.x & 63, li = lane & 15, lg = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    double* __restrict__ my_row = stage + (16 * wave + li) * SL_NNG_STRIDE + lg;   // this lane's point
+    const double* __restrict__ frag = stage + lg * SL_NNG_STRIDE + li;             // point 4 s + lg, feature li
+    sl_nd4 gacc[NL][4];
+#pragma unroll
+    for (int l = 0; l < NL; ++l)
+#pragma unroll
+        for (int ib = 0; ib < 4; ++ib) gacc[l][ib] = (sl_nd4){0.0, 0.0, 0.0, 0.0};
+    const int64_t step = (int64_t)gridDim.x * SL_NNG_CELLS;
+    // (the trip count is the same for the four wavefronts: the barriers below are uniform)
+    for (int64_t base = (int64_t)blockIdx.x * SL_NNG_CELLS; base < m; base += step) {
+        int64_t idx = base + 16 * wave + li;
+        const bool valid = idx < m;
+        idx = valid ? idx : m - 1;
+        // a point past m: a real point's activations with coefficient 0 - it adds exactly nothing
+        const double c = valid ? coeff[idx] : 0.0;
+        double z[SL_D];
+#pragma unroll
+        for (int k = 0; k < SL_D; ++k) z[k] = k < d ? points[idx * d + k] : 0.0;
+        // forward, as nn_mfma_eval: input as B fragments, slab s holds feature 4 s + lg
+        double xin[2];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            double v = 0.0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (4 * s + q < SL_D) v = (lg == q && 4 * s + q < d) ? z[4 * s + q] : v;
+            xin[s] = v;
+        }
+        sl_nd4 h[NL][4];
+#pragma unroll
+        for (int l = 0; l < NL; ++l) {
+            const int nslab = net.nslab[l], nfb = net.nfb[l], stride = net.wstride[l], a = net.act[l];
+            const double* __restrict__ W = wl + net.woff[l] + li * stride + lg;
+            sl_nd4 acc[4];
+#pragma unroll
+            for (int fb = 0; fb < 4; ++fb) acc[fb] = (sl_nd4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int s = 0; s < 16; ++s) {
+                if (l == 0 && s >= 2) break;
+                if (s < nslab) {
+                    const double b = (l == 0) ? xin[s & 1] : nd4_get(h[l > 0 ? l - 1 : 0][s >> 2], s & 3);
+#pragma unroll
+                    for (int fb = 0; fb < 4; ++fb)
+                        if (fb < nfb)
+                            acc[fb] = __builtin_amdgcn_mfma_f64_16x16x4f64(W[16 * fb * stride + 4 * s], b,
+                                                                           acc[fb], 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int fb = 0; fb < 4; ++fb) {
+                h[l][fb].x = sl_act(a, acc[fb].x);
+                h[l][fb].y = sl_act(a, acc[fb].y);
+                h[l][fb].z = sl_act(a, acc[fb].z);
+                h[l][fb].w = sl_act(a, acc[fb].w);
+            }
+        }
+        // backward: t = dV/d(pre-activation) of layer l, feature 16 fb + 4 r + lg in register r
+        sl_nd4 t[4];
+        {
+            const int a = net.act[NL - 1];
+#pragma unroll
+            for (int fb = 0; fb < 4; ++fb) {
+                const sl_nd4 hh = h[NL - 1][fb];
+                t[fb].x = 2.0 * hh.x * sl_dact(a, hh.x > 0.0 ? 1.0 : -1.0, hh.x);
+                t[fb].y = 2.0 * hh.y * sl_dact(a, hh.y > 0.0 ? 1.0 : -1.0, hh.y);
+                t[fb].z = 2.0 * hh.z * sl_dact(a, hh.z > 0.0 ? 1.0 : -1.0, hh.z);
+                t[fb].w = 2.0 * hh.w * sl_dact(a, hh.w > 0.0 ? 1.0 : -1.0, hh.w);
+            }
+        }
+#pragma unroll
+        for (int l = NL - 1; l >= 0; --l) {
+            const int nfb = net.nfb[l], nib = net.nib[l], stride = net.wstride[l];
+            const bool mine = wave < nfb;                  // this wavefront owns output rows 16 wave ..
+            // c t_l of the 64 points -> A fragments of this wavefront's rows
+            __syncthreads();                               // (the tile's last readers are through)
+#pragma unroll
+            for (int fb = 0; fb < 4; ++fb)
+                if (fb < nfb) {
+                    my_row[16 * fb + 0] = c * t[fb].x;
+                    my_row[16 * fb + 4] = c * t[fb].y;
+                    my_row[16 * fb + 8] = c * t[fb].z;
+                    my_row[16 * fb + 12] = c * t[fb].w;
+                }
+            __syncthreads();
+            double af[16];
+#pragma unroll
+            for (int s = 0; s < 16; ++s) af[s] = mine ? frag[4 * s * SL_NNG_STRIDE + 16 * wave] : 0.0;
+            __syncthreads();
+            // h_{l-1} of the 64 points (the input, zero-padded to one block of 16, below layer 0)
+#pragma unroll
+            for (int ib = 0; ib < 4; ++ib)
+                if (ib < nib && (l > 0 || ib == 0)) {
+                    // (xin[s] is input feature 4 s + lg: the layout of a block's registers 0 and 1)
+                    const sl_nd4 hh = l > 0 ? h[l > 0 ? l - 1 : 0][ib] : (sl_nd4){xin[0], xin[1], 0.0, 0.0};
+                    my_row[16 * ib + 0] = hh.x;
+                    my_row[16 * ib + 4] = hh.y;
+                    my_row[16 * ib + 8] = hh.z;
+                    my_row[16 * ib + 12] = hh.w;
+                }
+            __syncthreads();
+            if (mine) {
+#pragma unroll
+                for (int s = 0; s < 16; ++s)
+#pragma unroll
+                    for (int ib = 0; ib < 4; ++ib)
+                        if (ib < nib && (l > 0 || ib == 0))
+                            gacc[l][ib] = __builtin_amdgcn_mfma_f64_16x16x4f64(
+                                af[s], frag[4 * s * SL_NNG_STRIDE + 16 * ib], gacc[l][ib], 0, 0, 0);
+            }
+            if (l > 0) {
+                // t_{l-1} = (K_l^T t_l) * act'(layer l - 1), as nn_mfma_eval
+                const double* __restrict__ W = wl + net.woff[l] + lg * stride + li;
+                sl_nd4 acc[4];
+#pragma unroll
+                for (int ib = 0; ib < 4; ++ib) acc[ib] = (sl_nd4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int s = 0; s < 16; ++s) {
+                    if ((s >> 2) < nfb) {
+                        const double b = nd4_get(t[s >> 2], s & 3);
+#pragma unroll
+                        for (int ib = 0; ib < 4; ++ib)
+                            if (ib < nib)
+                                acc[ib] = __builtin_amdgcn_mfma_f64_16x16x4f64(W[4 * s * stride + 16 * ib], b,
+                                                                               acc[ib], 0, 0, 0);
+                    }
+                }
+                const int a = net.act[l > 0 ? l - 1 : 0];
+#pragma unroll
+                for (int ib = 0; ib < 4; ++ib) {
+                    const sl_nd4 hh = h[l > 0 ? l - 1 : 0][ib];
+                    t[ib].x = acc[ib].x * sl_dact(a, hh.x > 0.0 ? 1.0 : -1.0, hh.x);
+                    t[ib].y = acc[ib].y * sl_dact(a, hh.y > 0.0 ? 1.0 : -1.0, hh.y);
+                    t[ib].z = acc[ib].z * sl_dact(a, hh.z > 0.0 ? 1.0 : -1.0, hh.z);
+                    t[ib].w = acc[ib].w * sl_dact(a, hh.w > 0.0 ? 1.0 : -1.0, hh.w);
+                }
+            }
+        }
+    }
+    // accumulator tile (wave, ib) of layer l: register r of lane (li, lg) = G_l[16 wave + 4 r + lg][16 ib + li]
+    double* __restrict__ out = partials + (size_t)blockIdx.x * total;
+#pragma unroll
+    for (int l = 0; l < NL; ++l) {
+        const int in = net.dims[l], rows = net.dims[l + 1];
+#pragma unroll
+        for (int ib = 0; ib < 4; ++ib) {
+            const int col = 16 * ib + li;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = 16 * wave + 4 * r + lg;
+                if (row < rows && col < in) out[net.koff[l] + row * in + col] = nd4_get(gacc[l][ib], r);
+            }
+        }
+    }
+}
+
+// out[e] = partials[0][e] + partials[1][e] + ... in that order: the same bits at every call
+__global__ __launch_bounds__(SL_BLOCK) void k_nn_grad_reduce(const double* __restrict__ partials, int nblocks,
+                                                             int total, double* __restrict__ out) {
+    const int e = blockIdx.x * SL_BLOCK + threadIdx.x;
+    if (e >= total) return;
+    double s = 0.0;
+    for (int b = 0; b < nblocks; ++b) s = s + partials[(size_t)b * total + e];
+    out[e] = s;
+}
+
+// The losses: V(x) (and V(x+)) of 16 samples per wavefront on the matrix cores, the per-sample terms
+// of sl_nn_train.h on lanes 0..15, the coefficients and the point list [x; x+] written in place, the
+// three sums per workgroup to the scratch area (lane sums -> LDS -> thread 0, ascending).
+struct SlNnLossArgs {
+    int kind, d;
+    int64_t m;
+    const double* states;
+    const double* next;
+    const double* labels;          // ROA: labels; ABS: targets
+    const double* weights;
+    double safe_level, lagrange, eps;
+    double* coeff;
+    double* points;
+    double* partials;              // [gridDim.x][3]
+};
+
+template <int NL>
+__global__ __launch_bounds__(64 * SL_NNM_WAVES) void k_nn_loss(SlAux aux, SlNnLossArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double wl[];
+    __shared__ double red[16 * SL_NNM_WAVES][3];
+    const SlNet& net = *aux.net;
+    nn_stage_weights(net, wl);
+    const int d = a.d, lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const bool roa = a.kind == SL_NN_LOSS_ROA;
+    const double batch = (double)a.m;
+    double sum[3] = {0.0, 0.0, 0.0};
+    const int64_t step = (int64_t)gridDim.x * SL_NNM_WAVES * 16;
+    for (int64_t base = ((int64_t)blockIdx.x * SL_NNM_WAVES + wave) * 16; base < a.m; base += step) {
+        int64_t idx = base + (lane & 15);
+        const bool valid = idx < a.m;
+        idx = valid ? idx : a.m - 1;
+        double x[SL_D], xn[SL_D];
+#pragma unroll
+        for (int k = 0; k < SL_D; ++k) if (k < d) x[k] = a.states[idx * d + k];
+        const double v = nn_mfma_eval<NL>(net, wl, lane, x, d, false, nullptr);
+        double v_next = 0.0;
+        if (roa) {
+#pragma unroll
+            for (int k = 0; k < SL_D; ++k) if (k < d) xn[k] = a.next[idx * d + k];
+            v_next = nn_mfma_eval<NL>(net, wl, lane, xn, d, false, nullptr);
+        }
+        if (valid && lane < 16) {
+            const SlNnLossSample s = roa ? sl_nn_loss_roa(v, v_next, a.labels[idx], a.weights[idx], a.safe_level,
+                                                          a.lagrange, a.eps, batch)
+                                         : sl_nn_loss_abs(v, a.labels[idx], batch);
+            a.coeff[idx] = s.coeff_x;
+            if (roa) a.coeff[a.m + idx] = s.coeff_next;
+            if (a.points) {
+#pragma unroll
+                for (int k = 0; k < SL_D; ++k)
+                    if (k < d) {
+                        a.points[idx * d + k] = x[k];
+                        if (roa) a.points[(a.m + idx) * d + k] = xn[k];
+                    }
+            }
+            sum[0] = sum[0] + s.objective;
+            sum[1] = sum[1] + s.classifier;
+            sum[2] = sum[2] + s.decrease;
+        }
+    }
+    if (lane < 16) {
+        red[16 * wave + lane][0] = sum[0];
+        red[16 * wave + lane][1] = sum[1];
+        red[16 * wave + lane][2] = sum[2];
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        double s = 0.0;
+        for (int k = 0; k < 16 * SL_NNM_WAVES; ++k) s = s + red[k][threadIdx.x];
+        a.partials[3 * blockIdx.x + threadIdx.x] = s;
+    }
+}
+
+// losses[j] = (partials[0][j] + partials[1][j] + ...) / m
+__global__ void k_nn_loss_finish(const double* __restrict__ partials, int nblocks, int64_t m,
+                                 double* __restrict__ losses) {
+    if (threadIdx.x >= 3) return;
+    double s = 0.0;
+    for (int b = 0; b < nblocks; ++b) s = s + partials[3 * b + threadIdx.x];
+    losses[threadIdx.x] = s / (double)m;
+}
+
+// The two calls keep their per-workgroup slices in the context's scratch buffer (d_scratch, shared with
+// sl_eval_points, whose use of it ends on the stream before theirs begins), between two guard zones of
+// SL_NN_GUARD_WORDS words, written in front of the kernels of every call: one in the first words of the
+// allocation and one directly behind the last double the kernels of that call own (not at the end of the
+// allocation, which grows in steps of 1 MiB: a slice written a little past its area must hit it).  Word
+// 0 of the front zone holds the number of doubles between the two, the other words a fixed pattern.
+// sl_debug_nn_train_scratch reads them back.
+#define SL_NN_GUARD_WORDS 8
+#define SL_NN_GUARD_PATTERN 0x7ff8a5a55a5aa5a5ull
+
+__global__ void k_nn_guards(uint64_t* __restrict__ front, uint64_t doubles) {
+    uint64_t* __restrict__ back = front + SL_NN_GUARD_WORDS + doubles;
+    if (threadIdx.x == 0) front[0] = doubles;
+    else if (threadIdx.x < SL_NN_GUARD_WORDS) front[threadIdx.x] = SL_NN_GUARD_PATTERN;
+    else if (threadIdx.x < 2 * SL_NN_GUARD_WORDS) back[threadIdx.x - SL_NN_GUARD_WORDS] = SL_NN_GUARD_PATTERN;
+}
+
+static int nn_train_scratch(sl_ctx* ctx, size_t doubles, double** out) {
+    const size_t need = sizeof(double) * (doubles + 2 * SL_NN_GUARD_WORDS);
+    SL_HIP_CHECK(ctx, sl_grow(ctx, &ctx->d_scratch, &ctx->scratch_bytes, need, (size_t)1 << 20));
+    uint64_t* words = reinterpret_cast<uint64_t*>(ctx->d_scratch);
+    hipLaunchKernelGGL(k_nn_guards, dim3(1), dim3(64), 0, ctx->stream, words, (uint64_t)doubles);
+    SL_HIP_CHECK(ctx, hipGetLastError());
+    *out = reinterpret_cast<double*>(words + SL_NN_GUARD_WORDS);
+    return SL_OK;
+}
+
+extern "C" int sl_debug_nn_train_scratch(sl_ctx* ctx, int64_t* h_bytes, int* h_guards_intact) {
+    if (!ctx || !h_bytes || !h_guards_intact)
+        return sl_fail(ctx, SL_ERR_INVALID, "sl_debug_nn_train_scratch: NULL argument");
+    *h_bytes = 0;
+    *h_guards_intact = 0;
+    const size_t capacity = ctx->scratch_bytes / sizeof(uint64_t);
+    if (capacity < 2 * SL_NN_GUARD_WORDS) return SL_OK;
+    SL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    SL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    uint64_t guard[2][SL_NN_GUARD_WORDS];
+    const uint64_t* words = reinterpret_cast<const uint64_t*>(ctx->d_scratch);
+    SL_HIP_CHECK(ctx, hipMemcpy(guard[0], words, sizeof(guard[0]), hipMemcpyDeviceToHost));
+    const uint64_t doubles = guard[0][0];
+    // (a count that does not fit the allocation: the front zone was overwritten, or no call has run yet)
+    if (doubles > capacity - 2 * SL_NN_GUARD_WORDS) return SL_OK;
+    SL_HIP_CHECK(ctx, hipMemcpy(guard[1], words + SL_NN_GUARD_WORDS + doubles, sizeof(guard[1]),
+                                hipMemcpyDeviceToHost));
+    *h_bytes = (int64_t)(sizeof(double) * doubles);
+    *h_guards_intact = 1;
+    for (int k = 1; k < SL_NN_GUARD_WORDS; ++k)
+        if (guard[0][k] != SL_NN_GUARD_PATTERN) *h_guards_intact = 0;
+    for (int k = 0; k < SL_NN_GUARD_WORDS; ++k)
+        if (guard[1][k] != SL_NN_GUARD_PATTERN) *h_guards_intact = 0;
+    return SL_OK;
+}
+
+static int nn_train_check(sl_ctx* ctx, const char* who, int64_t m, int d) {
+    if (!ctx) return sl_fail(nullptr, SL_ERR_INVALID, "%s: NULL context", who);
+    if (!ctx->h_net.set) return sl_fail(ctx, SL_ERR_INVALID, "%s: network not set (sl_network_set)", who);
+    if (m <= 0) return sl_fail(ctx, SL_ERR_INVALID, "%s: m = %lld points", who, (long long)m);
+    if (d != ctx->h_net.dims[0])
+        return sl_fail(ctx, SL_ERR_INVALID, "%s: points of %d columns, the network takes %d inputs", who, d,
+                       ctx->h_net.dims[0]);
+    // (sl_network_set takes inputs up to SL_NN_MAXW wide and these calls run without sl_model_set, where
+    // the sweeps meet this limit: the kernels hold a point in SL_D registers)
+    if (d < 1 || d > SL_MAX_STATE_DIM)
+        return sl_fail(ctx, SL_ERR_INVALID, "%s: state dimension %d outside [1,%d]", who, d, SL_MAX_STATE_DIM);
+    return SL_OK;
+}
+
+static int64_t nn_blocks_per_cu(size_t lds) { return lds > 75 * 1024 ? 1 : 2; }
+
+extern "C" int sl_nn_param_grad(sl_ctx* ctx, int64_t m, int d, const double* d_points, const double* d_coeff,
+                                double* d_grad_kernels) {
+    if (const int rc = nn_train_check(ctx, "sl_nn_param_grad", m, d)) return rc;
+    if (!d_points || !d_coeff || !d_grad_kernels)
+        return sl_fail(ctx, SL_ERR_INVALID, "sl_nn_param_grad: NULL argument");
+    SL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    const SlNet& n = ctx->h_net;
+    const int total = n.koff[n.nlayers - 1] + n.dims[n.nlayers - 1] * n.dims[n.nlayers];
+    const size_t lds = nn_weight_bytes(ctx) + sizeof(double) * SL_NNG_CELLS * SL_NNG_STRIDE;
+    int64_t blocks = (m + SL_NNG_CELLS - 1) / SL_NNG_CELLS;
+    const int64_t cap = (int64_t)ctx->num_cu * nn_blocks_per_cu(lds);
+    if (blocks > cap) blocks = cap;
+    double* partials = nullptr;
+    if (const int rc = nn_train_scratch(ctx, (size_t)blocks * total, &partials)) return rc;
+    SlAux aux{ctx->d_tri, ctx->d_net};
+    const int rc = sl_with_dim<1, 2, 3, 4>(n.nlayers, [&](auto nl) {
+        SL_HIP_CHECK(ctx, sl_launch_lds(k_nn_param_grad<nl>, dim3((unsigned)blocks), dim3(64 * SL_NNG_WAVES), lds,
+                                        ctx->stream, aux, m, d, d_points, d_coeff, partials, total));
+        return SL_OK;
+    });
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_nn_grad_reduce, dim3((total + SL_BLOCK - 1) / SL_BLOCK), dim3(SL_BLOCK), 0, ctx->stream,
+                       partials, (int)blocks, total, d_grad_kernels);
+    SL_HIP_CHECK(ctx, hipGetLastError());
+    return SL_OK;
+}
+
+extern "C" int sl_nn_loss(sl_ctx* ctx, int kind, int64_t m, int d, const double* d_states, const double* d_next,
+                          const double* d_labels_or_targets, const double* d_class_weights, double safe_level,
+                          double lagrange, double eps, double* d_losses, double* d_coeff, double* d_points) {
+    if (const int rc = nn_train_check(ctx, "sl_nn_loss", m, d)) return rc;
+    if (kind != SL_NN_LOSS_ABS && kind != SL_NN_LOSS_ROA)
+        return sl_fail(ctx, SL_ERR_INVALID, "sl_nn_loss: unknown loss kind %d", kind);
+    if (!d_states || !d_labels_or_targets || !d_losses || !d_coeff)
+        return sl_fail(ctx, SL_ERR_INVALID, "sl_nn_loss: NULL argument");
+    if (kind == SL_NN_LOSS_ROA && (!d_next || !d_class_weights))
+        return sl_fail(ctx, SL_ERR_INVALID, "sl_nn_loss: SL_NN_LOSS_ROA needs the successors and the class weights");
+    SL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    int64_t blocks = (m + 16 * SL_NNM_WAVES - 1) / (16 * SL_NNM_WAVES);
+    const int64_t cap = (int64_t)ctx->num_cu * nn_blocks_per_cu(nn_weight_bytes(ctx));
+    if (blocks > cap) blocks = cap;
+    double* partials = nullptr;
+    if (const int rc = nn_train_scratch(ctx, (size_t)blocks * 3, &partials)) return rc;
+    SlAux aux{ctx->d_tri, ctx->d_net};
+    const SlNnLossArgs a{kind, d, m, d_states, d_next, d_labels_or_targets, d_class_weights, safe_level, lagrange,
+                         eps, d_coeff, d_points, partials};
+    const int rc = sl_with_dim<1, 2, 3, 4>(ctx->h_net.nlayers, [&](auto nl) {
+        SL_HIP_CHECK(ctx, sl_launch_lds(k_nn_loss<nl>, dim3((unsigned)blocks), dim3(64 * SL_NNM_WAVES),
+                                        nn_weight_bytes(ctx), ctx->stream, aux, a));
+        return SL_OK;
+    });
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_nn_loss_finish, dim3(1), dim3(64), 0, ctx->stream, partials, (int)blocks, m, d_losses);
+    SL_HIP_CHECK(ctx, hipGetLastError());
     return SL_OK;
 }

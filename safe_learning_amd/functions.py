@@ -1018,3 +1018,57 @@ class LyapunovNetwork(DeterministicFunction):
     def _upload(self, ctx):
         dims = [self.input_dim] + self.output_dims
         ctx.network_set(dims, [_ACTIVATIONS[a] for a in self.activations], self.kernels())
+
+    def _on_engine(self):
+        """The point-evaluation context with this network's current kernels on it (uploaded again only
+        when the weights changed: ``ModelBuilder._write_value``)."""
+        from . import _evaluate
+        ctx, builder = _evaluate._builder(self.input_dim)
+        builder._write_value(_hip.ValueDesc(), self)
+        return ctx
+
+    def _weights_gradient(self, kernel_gradients):
+        """The derivative with respect to the variables from the derivative ``G_l`` with respect to the
+        layer kernels ``[W^T W + eps I ; W']`` (flat, ``[out_l][in_l]`` per layer): ``W (G_top +
+        G_top^T)`` and ``G_bottom``, in the order of ``weights``.  NumPy float64 on the host, where
+        the master copy of the weights lives."""
+        flat = np.asarray(kernel_gradients, dtype=np.float64).ravel()
+        out, it, offset = [], iter(self.weights), 0
+        for i in range(self.num_layers):
+            in_dim = self.input_dim if i == 0 else self.output_dims[i - 1]
+            rows = self.output_dims[i]
+            G = flat[offset:offset + rows * in_dim].reshape(rows, in_dim)
+            offset += rows * in_dim
+            W = next(it)
+            out.append(W.dot(G[:in_dim] + G[:in_dim].T))
+            if rows > in_dim:
+                next(it)
+                out.append(G[in_dim:].copy())
+        return out
+
+    def parameter_gradient(self, points, coefficients):
+        """``sum_m coefficients[m] * dV(points[m]) / d theta`` for every array ``theta`` of ``weights``
+        (a list shaped like ``weights``): what ``tf.gradients(sum(c * V(p)), parameters)`` returns
+        for the reference's network.  ``points`` ``[M, d]`` and ``coefficients`` ``[M]`` are NumPy
+        arrays or device tensors; the sum over the points runs on the GPU (``sl_nn_param_grad``) and
+        is the same bit for bit at every call."""
+        from . import _evaluate
+        ctx = self._on_engine()
+        d_points = _evaluate._to_device(ctx, points)
+        m, d = d_points.shape
+        if d != self.input_dim:
+            raise ValueError('the network expects %d inputs, the points have %d columns' % (self.input_dim, d))
+        d_coeff = _evaluate._to_device(ctx, coefficients).reshape(-1)
+        if d_coeff.numel() != m:
+            raise ValueError('%d coefficients for %d points' % (d_coeff.numel(), m))
+        gradient = self._weights_gradient(self._kernel_gradient(ctx, d_points, d_coeff))
+        return [-g for g in gradient] if self.negate else gradient
+
+    def _kernel_gradient(self, ctx, d_points, d_coeff):
+        """``sl_nn_param_grad`` on device tensors -> the flat ``G_l`` on the host."""
+        import torch
+        dims = [self.input_dim] + self.output_dims
+        total = sum(a * b for a, b in zip(dims[:-1], dims[1:]))
+        out = torch.empty(total, dtype=torch.float64, device=ctx.torch_device)
+        ctx.nn_param_grad(d_points.shape[0], d_points.shape[1], d_points, d_coeff, out)
+        return out.cpu().numpy()

@@ -1,0 +1,124 @@
+"""Training steps for a ``LyapunovNetwork`` (``examples/lyapunov_function_learning.ipynb``).
+
+The notebook grows the verified level set of a network towards the true region of attraction with
+two ``optimizer.minimize(..., var_list=lyapunov_function.parameters)`` calls of plain gradient
+descent: a pre-training towards given values (cell 25) and the region-of-attraction classifier with
+a decrease penalty (cell 30).  Here a step is two engine calls - ``sl_nn_loss`` evaluates the loss
+terms of the batch and the coefficient of every point, ``sl_nn_param_grad`` sums coefficient times
+``dV/dK`` over the points on the matrix cores - and the update ``theta <- theta - lr * grad`` of
+``network.weights`` on the host, where the master copy of the weights lives: the sweeps and the point
+evaluations notice the edit through that copy.
+"""
+
+import numpy as np
+
+from . import _hip
+
+__all__ = ['balanced_class_weights', 'pretraining_step', 'roa_classification_step']
+
+
+def _check_single_process():
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise NotImplementedError('the training steps run on one GPU; under torch.distributed call them on '
+                                  'one rank and broadcast network.weights')
+
+
+def balanced_class_weights(y_true, scale_by_total=True):
+    """Per-sample weights that give both classes of a binary labelling the same total weight, and the
+    class counts ``[negatives, positives]`` (``examples/utilities.py:737-750``).  A sample weighs one
+    over the size of its class, times the number of samples with ``scale_by_total``; a class that is
+    absent weighs nothing."""
+    labels = np.asarray(y_true).astype(bool)
+    positives = int(labels.sum())
+    negatives = labels.size - positives
+    weights = np.ones(labels.shape, dtype=float)
+    weights[labels] /= max(positives, 1)
+    weights[~labels] /= max(negatives, 1)
+    if scale_by_total:
+        weights *= labels.size
+    return weights, np.array([negatives, positives])
+
+
+def _column(ctx, values, m, what):
+    """``values`` as a float64 device vector of ``m`` entries."""
+    from . import _evaluate
+    import torch
+    if not isinstance(values, torch.Tensor):
+        values = np.asarray(values, dtype=np.float64).reshape(-1, 1)
+    out = _evaluate._to_device(ctx, values).reshape(-1)
+    if out.numel() != m:
+        raise ValueError('%d %s for %d states' % (out.numel(), what, m))
+    return out
+
+
+def _states(network, ctx, states):
+    from . import _evaluate
+    d_states = _evaluate._to_device(ctx, states)
+    if d_states.shape[1] != network.input_dim:
+        raise ValueError('the network expects %d inputs, the states have %d columns'
+                         % (network.input_dim, d_states.shape[1]))
+    return d_states
+
+
+def _descend(network, ctx, d_points, d_coeff, learning_rate):
+    gradient = network._weights_gradient(network._kernel_gradient(ctx, d_points, d_coeff))
+    network.weights = [w - learning_rate * g for w, g in zip(network.weights, gradient)]
+
+
+def pretraining_step(network, states, targets, learning_rate):
+    """One gradient-descent step on ``mean |V(states) - targets|`` (cell 25 of the notebook); returns
+    the objective BEFORE the step.  ``learning_rate=None`` evaluates the objective only."""
+    import torch
+    _check_single_process()
+    if network.negate:
+        raise ValueError('train the network itself, not its negation')
+    ctx = network._on_engine()
+    d_states = _states(network, ctx, states)
+    m, d = d_states.shape
+    d_targets = _column(ctx, targets, m, 'targets')
+    losses = torch.empty(3, dtype=torch.float64, device=ctx.torch_device)
+    coeff = torch.empty(m, dtype=torch.float64, device=ctx.torch_device)
+    ctx.nn_loss(_hip.NN_LOSS_ABS, m, d, d_states, None, d_targets, None, 0.0, 0.0, 0.0, losses, coeff)
+    if learning_rate is not None:
+        _descend(network, ctx, d_states, coeff, float(learning_rate))
+    return float(losses[0])
+
+
+def roa_classification_step(lyapunov, states, roa_labels, class_weights, safe_level, lagrange_multiplier,
+                            learning_rate, eps=1e-8):
+    """One gradient-descent step of the notebook's cell 30 on the network ``lyapunov.lyapunov_function``:
+
+        classifier_i = w_i max(-(2 l_i - 1)(safe_level - V(x_i)), 0)
+        decrease_i   = l_i max(V(x_i+) - V(x_i), 0) / stop_gradient(V(x_i) + eps)
+        objective    = mean_i (classifier_i + lagrange_multiplier * decrease_i)
+
+    with ``x+ = dynamics(x, policy(x))`` of ``lyapunov`` (the mean, for uncertain dynamics), evaluated on
+    the device and held constant.  Returns ``dict(objective, classifier_loss, decrease_loss)`` - the three
+    means BEFORE the step; ``learning_rate=None`` evaluates them only (the notebook's test set)."""
+    import torch
+    from . import _evaluate
+    _check_single_process()
+    network = lyapunov.lyapunov_function
+    if not hasattr(network, '_kernel_gradient') or network.negate:
+        raise TypeError('lyapunov.lyapunov_function must be a LyapunovNetwork')
+    ctx = _evaluate._ctx()
+    d_states = _states(network, ctx, states)
+    m, d = d_states.shape
+    d_labels = _column(ctx, roa_labels, m, 'labels')
+    d_weights = _column(ctx, class_weights, m, 'class weights')
+    actions = _evaluate.policy(lyapunov.policy, d_states)
+    successors = _evaluate.dynamics(lyapunov.dynamics, d_states, actions)
+    if isinstance(successors, tuple):
+        successors = successors[0]
+    d_next = successors.contiguous()
+    ctx = network._on_engine()
+    losses = torch.empty(3, dtype=torch.float64, device=ctx.torch_device)
+    coeff = torch.empty(2 * m, dtype=torch.float64, device=ctx.torch_device)
+    points = torch.empty((2 * m, d), dtype=torch.float64, device=ctx.torch_device)
+    ctx.nn_loss(_hip.NN_LOSS_ROA, m, d, d_states, d_next, d_labels, d_weights, float(safe_level),
+                float(lagrange_multiplier), float(eps), losses, coeff, points)
+    if learning_rate is not None:
+        _descend(network, ctx, points, coeff, float(learning_rate))
+    objective, classifier, decrease = losses.tolist()
+    return dict(objective=objective, classifier_loss=classifier, decrease_loss=decrease)

@@ -1,0 +1,340 @@
+"""NumPy reference of the LyapunovNetwork training steps (safe_learning_amd/training.py,
+``examples/lyapunov_function_learning.ipynb`` cells 25 and 30), on ``oracle.LyapunovNetwork``.
+
+``parameter_gradient`` backpropagates ``sum_m c_m V(p_m)`` to the variables and returns the error
+companion ``A`` beside it: the same backward pass with every matrix, activation derivative,
+coefficient and layer input replaced by its absolute value.  ``A`` bounds what a rounding error of
+the pass can grow to, so gradients are compared as ``|g - g_ref| <= tol * A`` (a tolerance relative
+to ``|g|`` fails on entries that cancel).  The pass runs in the precision of ``dtype``: ``np.float64``
+is the reference, ``np.longdouble`` measures the reference's own error.
+
+The loss functions repeat ``safe_learning_amd/csrc/sl_nn_train.h`` line by line - one rounding per
+operation, in that order - so the host build of the header equals them bit for bit.
+"""
+
+import numpy as np
+
+from oracle.np_functions import LyapunovNetwork
+
+
+def _kernels(net, dtype):
+    """Layer kernels ``[W^T W + eps I ; W']`` in ``dtype``, and the weights grouped per layer."""
+    kernels, groups, it = [], [], iter(net.weights)
+    for i in range(net.num_layers):
+        in_dim = net.input_dim if i == 0 else net.output_dims[i - 1]
+        W = np.asarray(next(it), dtype=dtype)
+        kernel = W.T.dot(W) + dtype(net.eps) * np.eye(in_dim, dtype=dtype)
+        extra = None
+        if net.output_dims[i] > in_dim:
+            extra = np.asarray(next(it), dtype=dtype)
+            kernel = np.concatenate([kernel, extra], axis=0)
+        kernels.append(kernel)
+        groups.append((W, extra))
+    return kernels, groups
+
+
+def forward(net, points, dtype=np.float64):
+    """-> kernels, weight groups, [(pre, post)] per layer, V [M]."""
+    kernels, groups = _kernels(net, dtype)
+    h = np.atleast_2d(np.asarray(points, dtype=dtype))
+    cache = []
+    for kernel, act in zip(kernels, net.activations):
+        pre = h.dot(kernel.T)
+        post = LyapunovNetwork._act(act, pre)
+        cache.append((h, pre, post))
+        h = post
+    return kernels, groups, cache, np.sum(np.square(h), axis=1)
+
+
+def values(net, points):
+    return forward(net, points)[3]
+
+
+def kernel_gradient(net, points, coefficients, dtype=np.float64, order=None):
+    """``G_l = sum_m c_m t_l(p_m) h_{l-1}(p_m)^T`` per layer and its companion; ``order``: a permutation
+    of the points (another summation order)."""
+    points = np.atleast_2d(np.asarray(points, dtype=dtype))
+    c = np.asarray(coefficients, dtype=dtype).reshape(-1, 1)
+    if order is not None:
+        points, c = points[order], c[order]
+    kernels, groups, cache, _ = forward(net, points, dtype)
+    G, GA = [None] * net.num_layers, [None] * net.num_layers
+    t = ta = None
+    for l in reversed(range(net.num_layers)):
+        h_in, pre, post = cache[l]
+        dact = LyapunovNetwork._dact(net.activations[l], pre, post).astype(dtype)
+        if l == net.num_layers - 1:
+            t = dtype(2) * post * dact
+            ta = dtype(2) * np.abs(post) * np.abs(dact)
+        else:
+            t = t.dot(kernels[l + 1]) * dact
+            ta = ta.dot(np.abs(kernels[l + 1])) * np.abs(dact)
+        G[l] = (c * t).T.dot(h_in)
+        GA[l] = (np.abs(c) * ta).T.dot(np.abs(h_in))
+    return G, GA, groups
+
+
+def parameter_gradient(net, points, coefficients, dtype=np.float64, order=None):
+    """-> (gradients, companions), two lists shaped like ``net.weights``."""
+    G, GA, groups = kernel_gradient(net, points, coefficients, dtype, order)
+    grads, comps = [], []
+    for l, (W, extra) in enumerate(groups):
+        n = W.shape[1]
+        grads.append(W.dot(G[l][:n] + G[l][:n].T))
+        comps.append(np.abs(W).dot(GA[l][:n] + GA[l][:n].T))
+        if extra is not None:
+            grads.append(G[l][n:].copy())
+            comps.append(GA[l][n:].copy())
+    return grads, comps
+
+
+def max_abs_tanh(net, points):
+    """Largest |tanh| output of any tanh layer (the amplification 2 h^2 / (1 - h^2) of 1 - h^2)."""
+    worst = 0.0
+    for (_, _, post), act in zip(forward(net, points)[2], net.activations):
+        if act == 'tanh':
+            worst = max(worst, float(np.abs(post).max()))
+    return worst
+
+
+def ratio_to_companion(got, ref, comp):
+    """max over all entries of |got - ref| / A, in units of 2^-53 (entries with A = 0 must agree exactly)."""
+    worst = 0.0
+    for g, r, a in zip(got, ref, comp):
+        g, r, a = (np.asarray(v, dtype=np.longdouble) for v in (g, r, a))
+        diff = np.abs(g - r)
+        assert np.all(diff[a == 0] == 0)
+        if (a > 0).any():
+            worst = max(worst, float((diff[a > 0] / a[a > 0]).max()))
+    return worst * 2.0 ** 53
+
+
+# ---- the losses (sl_nn_train.h) --------------------------------------------------------------------
+
+def roa_terms(v, v_next, labels, weights, safe_level, lagrange, eps):
+    """Per-sample terms and coefficients of SL_NN_LOSS_ROA; ``hinge`` / ``dv`` are the arguments of
+    the two max(., 0)."""
+    v, v_next, labels, weights = (np.asarray(a, dtype=np.float64).ravel() for a in (v, v_next, labels, weights))
+    batch = float(len(v))
+    sign = 2.0 * labels - 1.0
+    hinge = -sign * (safe_level - v)
+    hinge_on = hinge > 0.0
+    classifier = weights * np.where(hinge_on, hinge, 0.0)
+    dv = v_next - v
+    dec_on = dv > 0.0
+    denom = v + eps
+    decrease = labels * np.where(dec_on, dv, 0.0) / denom
+    objective = classifier + lagrange * decrease
+    d_cls = np.where(hinge_on, weights * sign, 0.0)
+    d_dec = np.where(dec_on, lagrange * (labels / denom), 0.0)
+    return dict(classifier=classifier, decrease=decrease, objective=objective, hinge=hinge, dv=dv,
+                hinge_on=hinge_on, dec_on=dec_on, coeff_x=(d_cls - d_dec) / batch, coeff_next=d_dec / batch)
+
+
+def abs_terms(v, targets):
+    v, targets = (np.asarray(a, dtype=np.float64).ravel() for a in (v, targets))
+    diff = v - targets
+    return dict(classifier=np.abs(diff), decrease=np.zeros_like(diff), objective=np.abs(diff), diff=diff,
+                coeff_x=np.sign(diff) / float(len(v)), coeff_next=np.zeros_like(diff))
+
+
+def _descend(net, points, coeff, learning_rate):
+    grads, comps = parameter_gradient(net, points, coeff)
+    net.weights = [w - learning_rate * g for w, g in zip(net.weights, grads)]
+    return comps
+
+
+def pretraining_step(net, states, targets, learning_rate):
+    """-> (objective before the step, terms, companions of the gradient or None)."""
+    terms = abs_terms(values(net, states), targets)
+    comps = None if learning_rate is None else _descend(net, states, terms['coeff_x'], learning_rate)
+    return float(terms['objective'].mean()), terms, comps
+
+
+def roa_classification_step(net, states, successors, labels, weights, safe_level, lagrange, learning_rate,
+                            eps=1e-8):
+    """-> (dict of the three means before the step, terms, companions or None)."""
+    terms = roa_terms(values(net, states), values(net, successors), labels, weights, safe_level, lagrange, eps)
+    comps = None
+    if learning_rate is not None:
+        comps = _descend(net, np.vstack((states, successors)), np.concatenate((terms['coeff_x'], terms['coeff_next'])),
+                         learning_rate)
+    means = dict(objective=float(terms['objective'].mean()), classifier_loss=float(terms['classifier'].mean()),
+                 decrease_loss=float(terms['decrease'].mean()))
+    return means, terms, comps
+
+
+# ---- the four networks of the tests -------------------------------------------------------------------
+
+NETWORKS = {
+    "notebook": (2, [64, 64, 64], ['tanh', 'tanh', 'tanh']),
+    "one-layer": (4, [4], ['tanh']),
+    "ragged": (2, [5, 5, 17], ['tanh', 'relu', 'linear']),
+    "four-layers": (3, [16, 16, 16, 64], ['tanh'] * 4),
+}
+
+
+# Xavier-uniform weights, scaled so that with points in [-1, 1]^d no tanh output exceeds 0.96: the
+# error of a tanh is amplified by 2 h^2 / (1 - h^2) in its derivative 1 - h^2 (24 at 0.96; unscaled
+# weights reach 0.999 on the four-layer network).
+WEIGHT_SCALE = 0.6
+MAX_TANH = 0.96
+
+
+def xavier_weights(shapes, seed):
+    rng = np.random.default_rng(seed)
+    return [WEIGHT_SCALE * rng.uniform(-1, 1, s) * np.sqrt(6. / (s[0] + s[1])) for s in shapes]
+
+
+def make_network(key, seed=0):
+    d, dims, acts = NETWORKS[key]
+    shapes = LyapunovNetwork(d, dims, acts, weights=[]).weight_shapes()
+    return LyapunovNetwork(d, dims, acts, weights=xavier_weights(shapes, seed))
+
+
+def make_batch(key, m, seed=1):
+    """Points in [-1, 1]^d and coefficients with both signs and exact zeros."""
+    d = NETWORKS[key][0]
+    rng = np.random.default_rng(seed + m)
+    points = rng.uniform(-1, 1, (m, d))
+    coeff = rng.normal(size=m)
+    coeff[rng.uniform(size=m) < 0.2] = 0.0
+    if m > 2 and not (coeff == 0).any():
+        coeff[m // 2] = 0.0                        # (a small batch whose draw left no zero)
+    if m > 1:
+        coeff[0], coeff[-1] = 0.75, -1.25          # never all zero, both signs
+    else:
+        coeff[0] = -1.25
+    return points, coeff
+
+
+# ---- the batches of the loss and step tests -----------------------------------------------------------
+
+SAFE_LEVEL, LAGRANGE, EPS = 0.04, 10.0, 1e-8
+HINGE_MARGIN = 1e-12           # samples whose hinge / decrease argument is this close to 0 are not
+                               # compared decision by decision (at most 1 % of a batch)
+
+
+def training_case(kind):
+    """The 41 x 41 pendulum grid under its saturated LQR policy with a [16, 16, 16] tanh network that is a
+    Lyapunov candidate (``cases.lyapunov_like_network_weights``: its level set is not empty);
+    ``kind``: 'pendulum' (Euler dynamics) or 'linear' (a LinearSystem)."""
+    import cases
+    case = cases.make_case("pendulum", num_points=41, dynamics={"pendulum": "analytic", "linear": "linear"}[kind],
+                           tau_scale=0.0)
+    dims = [16, 16, 16]
+    case["V"] = {"kind": "network", "layer_dims": dims, "activations": ["tanh"] * 3, "eps": 1e-8,
+                 "weights": cases.lyapunov_like_network_weights(case["P"], dims)}
+    case["lv"] = ("norm_grad",)
+    return case
+
+
+def training_batch(case):
+    """States = the grid points, successors from the oracle's closed loop, labels = a disc (its edge
+    crosses the network's level ``SAFE_LEVEL``, so both classes have samples on the wrong side, and it is
+    large enough that V increases along the closed loop at some labelled states), balanced
+    class weights, pre-training targets."""
+    import cases
+    import oracle
+    states = oracle.GridWorld(case["limits"], case["num_points"]).all_points
+    policy, dynamics, _, _ = cases.oracle_specs(case)
+    successors = dynamics(states, policy(states))
+    cost = np.einsum("ij,jk,ik->i", states, case["P"], states)
+    labels = (np.sum(states * states, axis=1) <= 0.8).astype(np.float64)
+    positives = labels.sum()
+    weights = np.where(labels > 0, len(labels) / positives, len(labels) / (len(labels) - positives))
+    return dict(states=states, successors=successors, labels=labels, weights=weights, targets=0.09 * cost * (1.0 + 0.5 * states[:, 0]))
+
+
+def oracle_network(case):
+    spec = case["V"]
+    return LyapunovNetwork(case["d"], spec["layer_dims"], spec["activations"], spec["eps"],
+                           [w.copy() for w in spec["weights"]])
+
+
+def undecided(terms, kind):
+    """Samples of a batch whose max(., 0) / |.| arguments lie within HINGE_MARGIN of the kink."""
+    if kind == "abs":
+        return np.abs(terms["diff"]) <= HINGE_MARGIN
+    return (np.abs(terms["hinge"]) <= HINGE_MARGIN) | (np.abs(terms["dv"]) <= HINGE_MARGIN)
+
+
+# ---- the tolerance of the gradient comparisons ------------------------------------------------------------
+# max |g_float64 - g_longdouble| / A of this oracle, in units of 2^-53, on every batch of make_batch the GPU
+# test uses (measured by reference_ratio below, rounded up; tests/test_lyapunov_training_host.py asserts
+# that a re-measurement stays below these figures).  The ratio belongs to the BATCH, not to the network alone:
+# A carries the absolute values of the layer inputs but not the forward pass's own rounding, so where a
+# pre-activation cancels (its error is 2^-53 sum |K| |h|, not 2^-53 |K h|) the float64 reference itself is
+# hundreds of 2^-53 A away from long double.  Summed over M points A grows like M and that error like
+# sqrt(M): 445 at M = 1 and 0.22 at M = 70 001 on the four-layer network.  ("steps-pre", k) / ("steps-roa", k):
+# the [16, 16, 16] network of training_case('pendulum') at the weights the reference's own descent (learning
+# rates STEP_LR) has BEFORE its step k, with the coefficients of the pre-training / ROA batch at those weights:
+# one figure per step, since the weights and with them the batch's coefficients change from step to step.
+REFERENCE_RATIO = {
+    ("four-layers", 1): 446., ("four-layers", 15): 23.3, ("four-layers", 16): 8.97, ("four-layers", 17): 8.25,
+    ("four-layers", 1000): 1.36, ("four-layers", 70001): 0.217,
+    ("notebook", 1): 79.5, ("notebook", 15): 3.14, ("notebook", 16): 2.65, ("notebook", 17): 2.32,
+    ("notebook", 1000): 0.58, ("notebook", 70001): 0.05,
+    ("one-layer", 1): 1.84, ("one-layer", 15): 0.409, ("one-layer", 16): 0.624, ("one-layer", 17): 0.812,
+    ("one-layer", 1000): 0.37, ("one-layer", 70001): 0.029,
+    ("ragged", 1): 2013., ("ragged", 15): 12.6, ("ragged", 16): 59.3, ("ragged", 17): 13.0,
+    ("ragged", 1000): 5.9, ("ragged", 70001): 0.70,
+    ("steps-pre", 0): 6.28, ("steps-pre", 1): 6.29, ("steps-pre", 2): 6.83, ("steps-pre", 3): 7.54,
+    ("steps-pre", 4): 3.91,
+    ("steps-roa", 0): 10.3, ("steps-roa", 1): 7.60, ("steps-roa", 2): 5.77, ("steps-roa", 3): 9.62,
+    ("steps-roa", 4): 4.50}
+STEP_LR = {"steps-pre": 0.05, "steps-roa": 0.01}
+NUM_STEPS = 5
+
+
+def measure_step_ratios(key):
+    """-> the NUM_STEPS figures of REFERENCE_RATIO[key, k]: float64 against long double on the batch of every
+    step of the reference's descent from the weights of training_case('pendulum')."""
+    case = training_case("pendulum")
+    batch = training_batch(case)
+    net = oracle_network(case)
+    ratios = []
+    for _ in range(NUM_STEPS):
+        if key == "steps-pre":
+            _, terms, _ = pretraining_step(net, batch["states"], batch["targets"], None)
+            points, coeff = batch["states"], terms["coeff_x"]
+        else:
+            _, terms, _ = roa_classification_step(net, batch["states"], batch["successors"], batch["labels"],
+                                                  batch["weights"], SAFE_LEVEL, LAGRANGE, None, EPS)
+            points = np.vstack((batch["states"], batch["successors"]))
+            coeff = np.concatenate((terms["coeff_x"], terms["coeff_next"]))
+        assert max_abs_tanh(net, points) <= MAX_TANH
+        g64, comp = parameter_gradient(net, points, coeff)
+        g80, _ = parameter_gradient(net, points, coeff, dtype=np.longdouble)
+        ratios.append(ratio_to_companion(g64, g80, comp))
+        if key == "steps-pre":
+            pretraining_step(net, batch["states"], batch["targets"], STEP_LR[key])
+        else:
+            roa_classification_step(net, batch["states"], batch["successors"], batch["labels"], batch["weights"],
+                                    SAFE_LEVEL, LAGRANGE, STEP_LR[key], EPS)
+    return ratios
+
+
+def measure_reference_ratio(key, m):
+    """The float64 reference against the same pass in long double on make_batch(key, m)."""
+    if key in STEP_LR:
+        return measure_step_ratios(key)[m]
+    net = make_network(key)
+    points, coeff = make_batch(key, m)
+    g64, comp = parameter_gradient(net, points, coeff)
+    g80, _ = parameter_gradient(net, points, coeff, dtype=np.longdouble)
+    return ratio_to_companion(g64, g80, comp)
+
+
+def reference_ratio(key, m):
+    """The recorded figure of a batch (m: its size, or the step of "steps-pre" / "steps-roa"); a batch size
+    without one (the largest depends on the device's CU count) is measured on the spot, once."""
+    if (key, m) not in REFERENCE_RATIO:
+        REFERENCE_RATIO[key, m] = measure_reference_ratio(key, m)
+    return REFERENCE_RATIO[key, m]
+
+
+def tolerance(key, m):
+    """32 times the reference's own error on that batch: room for another summation order, a device tanh a
+    few ulp off where libm is within one, and that error's amplification by up to 24 in 1 - h^2 (MAX_TANH)."""
+    return 32.0 * reference_ratio(key, m) * 2.0 ** -53

@@ -113,7 +113,10 @@ def main():
              "composition of the point evaluations and against the sweep of the same cells (`tools/rollout_probe.py`; DESIGN.md 4.2b).",
              "* `reward_rollout.md`: discounted returns (`k_reward_rollout`, `k_reward_fold`, csrc/sl_rollout.hip) against the stepwise "
              "composition of the point evaluations and against `k_rollout` over the same steps, with the registers / LDS of the new "
-             "kernels (`tools/reward_rollout_probe.py`; DESIGN.md 4.2b).", ""]
+             "kernels (`tools/reward_rollout_probe.py`; DESIGN.md 4.2b).",
+             "* `lyapunov_training.md`: training a LyapunovNetwork (`k_nn_loss`, `k_nn_param_grad`, csrc/sl_nn.hip): registers / LDS, "
+             "the tolerance of the gradient comparisons and what it was measured from, one gradient against torch autograd "
+             "(`tools/lyapunov_training_probe.py`).", ""]
     for key in sorted(by_round):
         text.append("* %s: %s" % (key, ", ".join("`%s`" % n for n in by_round[key])))
     with open(os.path.join(P, "README.md"), "w") as f:
