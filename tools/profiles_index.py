@@ -116,7 +116,10 @@ def main():
              "kernels (`tools/reward_rollout_probe.py`; DESIGN.md 4.2b).",
              "* `lyapunov_training.md`: training a LyapunovNetwork (`k_nn_loss`, `k_nn_param_grad`, csrc/sl_nn.hip): registers / LDS, "
              "the tolerance of the gradient comparisons and what it was measured from, one gradient against torch autograd "
-             "(`tools/lyapunov_training_probe.py`).", ""]
+             "(`tools/lyapunov_training_probe.py`).",
+             "* `gp_posterior_truth.md`: the GP posterior of `k_gp_sweep4`, `k_gp_sweep` and `k_gp_small` against the posterior in "
+             "extended precision (`tests/np_gp_truth.py`): per case cond(K), the oracle's own error, a NumPy restatement of the "
+             "engine's formula and the engine's measured error (`tests/test_gpu_gp_truth.py`; DESIGN.md 6 (iv)).", ""]
     for key in sorted(by_round):
         text.append("* %s: %s" % (key, ", ".join("`%s`" % n for n in by_round[key])))
     with open(os.path.join(P, "README.md"), "w") as f:
