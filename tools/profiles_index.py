@@ -119,7 +119,11 @@ def main():
              "(`tools/lyapunov_training_probe.py`).",
              "* `gp_posterior_truth.md`: the GP posterior of `k_gp_sweep4`, `k_gp_sweep` and `k_gp_small` against the posterior in "
              "extended precision (`tests/np_gp_truth.py`): per case cond(K), the oracle's own error, a NumPy restatement of the "
-             "engine's formula and the engine's measured error (`tests/test_gpu_gp_truth.py`; DESIGN.md 6 (iv)).", ""]
+             "engine's formula and the engine's measured error (`tests/test_gpu_gp_truth.py`; DESIGN.md 6 (iv)).",
+             "* `dispatch_matrix.md`: every instantiation the `sl_with_dim` lists of `sl_bellman.hip`, `sl_bellman4.hip`, "
+             "`sl_succ.hip` and `sl_policy_solve.hip` compile - the test that reaches it or why none can "
+             "(`tests/bellman_matrix.py`), the largest oracle and cross-kernel differences of the newly covered ones "
+             "(`tests/test_gpu_bellman_matrix.py`) and the outcome of two numerically perturbed scratch builds.", ""]
     for key in sorted(by_round):
         text.append("* %s: %s" % (key, ", ".join("`%s`" % n for n in by_round[key])))
     with open(os.path.join(P, "README.md"), "w") as f:
