@@ -224,6 +224,11 @@ SL_API int  sl_gp_configure(sl_ctx* ctx, int nheads, double beta);
  * panel of every tile (the A/B baseline and the other side of the bit-identity tests); the default
  * is 1.  Takes effect at the next sweep. */
 SL_API int  sl_gp4_early_configure(sl_ctx* ctx, int enable);
+/* At most `workgroups` workgroups per launch of k_gp_sweep4 (0, the default: as many as the device
+ * holds).  For tests: on a small grid one workgroup then draws many tiles, and the queues of its open
+ * 16-cell blocks fill composite tiles from different source tiles.  The value is kept once per
+ * process, not per context, and takes effect at the next sweep. */
+SL_API int  sl_gp4_workgroups_configure(sl_ctx* ctx, int workgroups);
 
 /* Auxiliary grid #slot with a per-vertex table (Triangulation: functions.py:1002-1032,
  * 1064-1101): slot 0 = value function, slot 1 = policy.  h_simplices [nsimplex][d+1] are the

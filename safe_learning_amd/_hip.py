@@ -149,6 +149,7 @@ SIGNATURES = {
     "sl_gp_append_point": (_int, (_vp, _int, c_double_p, c_double_p, c_double_p)),
     "sl_gp_configure": (_int, (_vp, _int, _dbl)),
     "sl_gp4_early_configure": (_int, (_vp, _int)),
+    "sl_gp4_workgroups_configure": (_int, (_vp, _int)),
     "sl_tri_set": (_int, (_vp, _int, C.POINTER(GridDesc), _int, _int32_p, c_double_p, c_double_p, _int, _int,
                           _vp)),
     "sl_tri_set_table": (_int, (_vp, _int, _vp)),
@@ -319,6 +320,10 @@ class Context(object):
         # every tile.  Read here, once per context; `roofline.kernel` / last_kernel() name what ran.
         if os.environ.get("SL_GP4_EARLY") == "0":
             self.lib.sl_gp4_early_configure(self.handle, 0)
+        # SL_GP4_WORKGROUPS=N (tests): at most N workgroups of k_gp_sweep4, so that one workgroup of a
+        # small grid draws many tiles.  Set by every new context (unset: no cap).
+        if hasattr(self.lib, "sl_gp4_workgroups_configure"):
+            self.lib.sl_gp4_workgroups_configure(self.handle, int(os.environ.get("SL_GP4_WORKGROUPS") or 0))
 
     def close(self):
         if getattr(self, "handle", None):

@@ -38,6 +38,7 @@
 // 4x4x4 kernel 60.5 (profiles/r02_summary.md); round 3: 62.4 TFLOP/s at 128^4 (profiles/r03_summary.md).
 #include "sl_common.h"
 #include "sl_gp4_clobbers.h"
+#include "sl_gp4_queue.h"
 
 #ifdef SL_NO_GP4
 // Compiled out: the build's audit of the fixed-accumulator code failed on this toolchain
@@ -46,7 +47,12 @@ bool sl_gp4_supports(const SlDevModel&) { return false; }
 int sl_gp4_sweep_launch(sl_ctx* ctx, const SlDevModel&, const SlSweepArgs&, int*) {
     return sl_fail(ctx, SL_ERR_UNSUPPORTED, "k_gp_sweep4 is compiled out of this build");
 }
+extern "C" int sl_gp4_workgroups_configure(sl_ctx*, int) { return SL_OK; }
 #else
+
+// sl_gp4_workgroups_configure: at most this many workgroups per launch (0: no cap).  One value for
+// the process - a knob of the tests, which run one context at a time.
+extern int sl_gp4_workgroup_cap;
 
 typedef double sl_d2 __attribute__((ext_vector_type(2)));
 typedef unsigned sl_u4 __attribute__((ext_vector_type(4)));
@@ -81,6 +87,21 @@ constexpr int RUNC = SL_P + 2;             // per (wavefront, run): step[SL_P], 
 constexpr int KXS2 = CB * 128 + 4;
 constexpr int KXBUF = 8 * KXS2;
 static_assert(R == 4, "256-row panels (tools/audit_gp4.py is told the same number by the build)");
+
+// Block mode (EARLY): a pending record of an open 16-cell block in the workgroup's scratch -
+// [0] first cell (int64), [8 ..) 16 x SL_D means, then the four |a|^2 planes x 16 cells - and the
+// workgroup's control block in LDS (thread 0 keeps the queues, sl_gp4_queue.h).
+constexpr int REC_MEAN = 8, REC_SS = REC_MEAN + 16 * SL_D, REC = REC_SS + W * 16;   // doubles
+struct BlockCtl {
+    Gp4Queues q;
+    int action;            // panel of the composite tile to run; SOURCE: a source tile; DONE
+    int pos[GP4Q_SLOTS];   // ring positions of the composite's four slots (-1: empty)
+    int open[W];           // wavefront w pushes its block (to stage push_stage)
+    int push_stage;
+    int src_done;          // the source tiles are used up
+    int nsrc;              // source tiles drawn (round-robin lists)
+};
+constexpr int ACT_SOURCE = GP4Q_SOURCE, ACT_DONE = GP4Q_DONE;
 
 struct AFrag { sl_d2 v[R]; };
 struct BFrag { sl_d2 v[CB]; };
@@ -408,15 +429,19 @@ __device__ __forceinline__ double uniform(double v) {
 }  // namespace gp4
 
 #ifdef SL_DIAG
-// development builds: tiles decided before panel 0 .. 3 ([0..3]) and tiles asked but left open ([7],
-// once per question) - printed and cleared by launch4 when SL_GP4_SKIP has bit 16 (which skips nothing)
+// development builds: 16-cell blocks decided before panel 0 .. 3 ([0..3]) and composite tiles run
+// for panel 0 .. 3 ([4..7]) - printed and cleared by launch4 when SL_GP4_SKIP has bit 16 (which
+// skips nothing)
 static __device__ unsigned long long sl_gp4_stage_count[8];
 #endif
 
 // (The scaled training inputs and alpha' are read from L2 through buffer resources: two workgroups
 // per CU leave no LDS for them beside the k_x buffers.)
-// EARLY: tiles may be decided from bounds of the decrease (see try_decide); its own instantiation,
-// so that the plain path (EARLY = false: records, several heads, switched off) stays the code it was.
+// EARLY: 16-cell blocks may be decided from bounds of the decrease (see decide_block) and the
+// variance panels run on composite tiles of four blocks still open; its own instantiation, so
+// that the plain path (EARLY = false: records, several heads, switched off) stays the code it was.
+// `seeds` is then the workgroups' record scratch ([workgroup][stage][GP4Q_CAP][REC], seed_chunks
+// = stages) - a queued block regenerates its k_x from the exponentials.
 template <int DT, int MT, bool EARLY>
 __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
     const SlDevModel M, const SlGpDev gp, SlAux aux, int64_t lo, int64_t hi, int64_t ntiles,
@@ -448,7 +473,8 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
     uint64_t* sv = reinterpret_cast<uint64_t*>(runc + W * RUNS * RUNC);   // [W]
     int64_t* si = reinterpret_cast<int64_t*>(sv + W);                  // [W]
     int64_t* next_tile = si + W;                                       // the tile the workgroup drew
-    uint64_t* tile_decided = reinterpret_cast<uint64_t*>(next_tile + 1);   // wavefront 0 to the others
+    uint64_t* tile_decided = reinterpret_cast<uint64_t*>(next_tile + 1);   // (a spare word: the layout is the plain path's)
+    BlockCtl* ctl = reinterpret_cast<BlockCtl*>(tile_decided + 1);        // block mode only
 
     const SlDims nd = sl_dims<DT, MT>(M);
     const int d = nd.d, p = nd.p;
@@ -476,7 +502,7 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
     // is addressed by a scalar offset (chunk, run, wavefront) + 16 lane: no 64-bit pointer per lane
     // to carry through (or spill around) the MFMA streams; the same for the training inputs and
     // alpha' below.
-    const bool use_seeds = seeds != nullptr;
+    const bool use_seeds = !early && seeds != nullptr;
     const int seed_run_bytes = seed_chunks * W * 1024;          // one run's seeds of this workgroup
     __amdgpu_buffer_rsrc_t rs_seed = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(seeds + (size_t)blockIdx.x * RUNS * seed_chunks * W * 128), 0, 0x7fffffff, 0x27000);
@@ -489,16 +515,67 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
     // (Few tiles per workgroup - small grids, C2's 1024 tiles on 512 workgroups: the counter hands
     // one workgroup three tiles and another one, and the sweep lasts as long as the three; a fixed
     // round-robin list is the better balance there: ticket == nullptr.)
+    //
+    // Block mode (EARLY): a pass of the loop is either a SOURCE tile - cin, runs and the mean phase
+    // of 64 fresh cells, then every wavefront decides its own 16-cell block - or panel `stage` on a
+    // COMPOSITE tile of up to four blocks that earlier passes left open, slot w regenerated by
+    // wavefront w from the block's first cell.  Thread 0 chooses (sl_gp4_queue.h); queues, records
+    // and the final flush are the workgroup's own, the tile counter stays the only shared object.
+    const int nstages = early ? (gp.head[0].n + RP - 1) / RP : 0;
+    double* recs = seeds + (size_t)blockIdx.x * nstages * GP4Q_CAP * REC;
+    if (early && tid == 0) {
+        gp4q_init(ctl->q);
+        for (int w = 0; w < W; ++w) ctl->open[w] = 0;
+        ctl->push_stage = 0;
+        ctl->src_done = 0;
+        ctl->nsrc = 0;
+    }
     for (int64_t round = 0;; ++round) {
-        if (tid == 0) *next_tile = ticket ? (int64_t)atomicAdd(ticket, 1ull) : (int64_t)blockIdx.x + round * gridDim.x;
-        __syncthreads();
+        int stage = ACT_SOURCE;                    // block mode: the panel of a composite tile
+        if constexpr (early) {
+            if (tid == 0) {
+                int n = 0;                         // the blocks the pass before left open are queued
+                for (int w = 0; w < W; ++w) { n += ctl->open[w]; ctl->open[w] = 0; }
+                if (n) gp4q_push(ctl->q, ctl->push_stage, n);
+                const int st = gp4q_schedule(ctl->q, nstages, ctl->src_done, ctl->pos, [&]() {
+                    const int64_t t = ticket ? (int64_t)atomicAdd(ticket, 1ull)
+                                             : (int64_t)blockIdx.x + (int64_t)ctl->nsrc * gridDim.x;
+                    ctl->nsrc += 1;
+                    if (t < ntiles) *next_tile = t;
+                    return t < ntiles;
+                });
+                ctl->action = st;
+            }
+            __syncthreads();
+            stage = __builtin_amdgcn_readfirstlane(ctl->action);
+            if (stage == ACT_DONE) break;
+        } else {
+            if (tid == 0) *next_tile = ticket ? (int64_t)atomicAdd(ticket, 1ull) : (int64_t)blockIdx.x + round * gridDim.x;
+            __syncthreads();
+        }
         const int64_t tile = *next_tile;       // rewritten after the barriers of the tile
-        if (tile >= ntiles) break;
+        if (!early && tile >= ntiles) break;
         const int64_t tile_base = lo + tile * C;
-        if (tile_base >= hi) {                     // padding tile: only clears mask bits
+        if ((!early || stage == ACT_SOURCE) && tile_base >= hi) {   // padding tile: only clears mask bits
             if (tid == 0) neg_bits[(tile_base - lo) >> 6] = 0ull;
             __syncthreads();                       // everybody has read next_tile
             continue;
+        }
+        // block mode: the first cell of this wavefront's block (an empty slot of a partly filled
+        // composite generates nothing and writes nothing)
+        bool have_blk = true;
+        int64_t blk0 = tile_base + 16 * wave;
+        const double* rec_in = nullptr;
+        if (early && stage >= 0) {
+            const int pos = __builtin_amdgcn_readfirstlane(ctl->pos[wave]);
+            have_blk = pos >= 0;
+            rec_in = recs + (size_t)(stage * GP4Q_CAP + (have_blk ? pos : 0)) * REC;
+            blk0 = hi - 1;
+            if (have_blk) {
+                const int64_t b = *reinterpret_cast<const int64_t*>(rec_in);
+                blk0 = ((int64_t)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) |
+                       (int64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)b);
+            }
         }
 
         // mask word and failing-cell key of the tile (wavefront 0, lane = cell)
@@ -510,8 +587,11 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
             const bool okc = negative || ((init >> lane) & 1ull);
             if (valid && !okc) sl_key_min(best_v, best_i, sl_vbits(v_x), idx);
         };
-        bool decided = false;                      // (early only) the bounds settled all 64 cells
 
+        // (Never set: the tile-wide early decision left with the block mode.  The tests on it keep the
+        // EARLY = false instantiation instruction for instruction the code it was - the register
+        // allocation of this kernel follows the shape of its source, tools/compare_device_code.py.)
+        bool decided = false;
         for (int h = 0; h < gp.nheads; ++h) {
             const SlGpHeadDev& hd = gp.head[h];
             const int n_pad = hd.n_pad, dout = hd.dout;
@@ -525,7 +605,7 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
             // scaled GP input [x, policy(x)] / lengthscales of the 64 cells (lane = cell of block `wave`)
             if (lk == 0) {
                 double xg[SL_P], u[SL_M];
-                int64_t gidx = tile_base + 16 * wave + lcol;
+                int64_t gidx = (early ? blk0 : tile_base + 16 * wave) + lcol;
                 gidx = gidx < hi ? gidx : hi - 1;
                 // (opaque: the decode of the index stays here - hoisted out of the loop over the
                 // heads its results were spilled to scratch at every tile)
@@ -536,6 +616,12 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
 #pragma unroll
                 for (int q = 0; q < SL_P; ++q)
                     cin[(16 * wave + lcol) * SL_P + q] = (q < p) ? xg[q] * hd.inv_ls[q] : 0.0;
+            }
+            if (early && stage >= 0 && have_blk) {
+                // slot `wave` of a composite tile: the block's means and the |a|^2 of the panels
+                // before this one (the plane update then starts from them, from 0 at panel 0)
+                for (int i = lane; i < 16 * SL_D; i += 64) cell_mean[16 * wave * SL_D + i] = rec_in[REC_MEAN + i];
+                part_ss[lk * C + 16 * wave + lcol] = stage > 0 ? rec_in[REC_SS + lane] : 0.0;
             }
             __syncthreads();
             // Where the input is affine in the cell index, z_j(c) = |X_j - x(c)|^2 is quadratic in
@@ -814,71 +900,79 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
             // below (a cell that fails with it fails) and err_hi = beta sqrt(variance - partial |a|^2)
             // from above (a cell that passes with it passes); every operation between |a|^2 and the
             // comparison rounds monotonically, so a bit both bounds agree on is the bit of the full
-            // sum.  A tile whose 64 cells are all decided needs no further panel.
-            // try_decide: every wavefront calls it (two barriers); wavefront 0 evaluates both bounds
-            // for its 64 cells, writes word and key if they agree everywhere, and tells the others.
-            auto try_decide = [&](int stage, bool have_ss) -> bool {
-                __syncthreads();                   // cell_mean (and part_ss) of every wavefront
-                if (wave == 0) {
-                    const int64_t idx = tile_base + lane;
-                    const bool valid = idx < hi;
-                    bool neg_hi = false, open = false;
-                    double v_x = 0.0;
-                    if (valid) {
-                        double x[SL_P], u[SL_M], prior[SL_D], mean[SL_D], err0[SL_D], err1[SL_D];
-                        sl_cell_state(M, d, idx, points, x);
-                        sl_policy_any<false>(M, nd, aux.tri, idx, x, u);
-                        sl_append_action(nd, u, x);
-                        sl_rows_dot<SL_D, SL_P>(M.m.dynamics.matrix, d, p, x, prior);
-                        double var = variance;
-                        if (have_ss) {
-                            double sumsq = 0.0;
-                            for (int k = 0; k < PSS; ++k) sumsq += part_ss[k * C + lane];
-                            var = variance - sumsq;
-                        }
-                        const double e = gp.beta * sqrt(var);
+            // sum.  A 16-cell block whose cells are all decided needs no further panel.
+            // decide_block: every wavefront for its own 16 cells (lanes 0 .. 15), `done` panels in
+            // part_ss.  A block whose valid cells all agree (every decrease finite) is finished: its 16
+            // mask bits go into the tile's word with a 2-byte store and the failing key is folded
+            // with the block's 16 initial-set bits; cells >= hi write zeros.  After the last panel
+            // the upper bound IS the decrease of the full sum (the arithmetic of the plain
+            // epilogue: sum of the planes k = 0 .. 3, variance - sum, beta sqrt, sl_cell_check).
+            auto decide_block = [&](int done) -> bool {
+                const bool last = done == npanels;
+                const int64_t idx = blk0 + lcol;
+                const bool valid = lk == 0 && idx < hi;
+                const int cl = 16 * wave + lcol;
+                bool neg_hi = false, open = false;
+                double v_x = 0.0;
+                if (valid) {
+                    double x[SL_P], u[SL_M], prior[SL_D], mean[SL_D], err0[SL_D], err1[SL_D];
+                    sl_cell_state(M, d, idx, points, x);
+                    sl_policy_any<false>(M, nd, aux.tri, idx, x, u);
+                    sl_append_action(nd, u, x);
+                    sl_rows_dot<SL_D, SL_P>(M.m.dynamics.matrix, d, p, x, prior);
+                    double var = variance;
+                    if (done > 0) {
+                        double sumsq = 0.0;
+                        for (int k = 0; k < PSS; ++k) sumsq += part_ss[k * C + cl];
+                        var = variance - sumsq;
+                    }
+                    const double e = gp.beta * sqrt(var);
 #pragma unroll
-                        for (int k = 0; k < SL_D; ++k) {
-                            if (k < d) {
-                                mean[k] = cell_mean[lane * SL_D + k] + prior[k];
-                                err0[k] = 0.0;
-                                err1[k] = e;
-                            }
+                    for (int k = 0; k < SL_D; ++k) {
+                        if (k < d) {
+                            mean[k] = cell_mean[cl * SL_D + k] + prior[k];
+                            err0[k] = 0.0;
+                            err1[k] = e;
                         }
-                        const SlCellCheck c0 = sl_cell_check<SL_FAST>(M, d, aux, x, mean, err0);
-                        const SlCellCheck c1 = sl_cell_check<SL_FAST>(M, d, aux, x, mean, err1);
-                        neg_hi = c1.negative;
-                        // (a non-finite mean or err_hi leaves the cell, and so the tile, undecided)
-                        open = c0.negative != c1.negative || !(fabs(c0.decrease) < INFINITY) ||
-                               !(fabs(c1.decrease) < INFINITY);
-                        v_x = values ? values[idx - lo] : c1.v_x;
                     }
-                    const bool all = __ballot(open) == 0ull;
-                    if (all) finish_tile(neg_hi, valid, v_x, idx);
-                    if (lane == 0) {
-                        *tile_decided = all ? 1ull : 0ull;
-#ifdef SL_DIAG
-                        atomicAdd(&sl_gp4_stage_count[all ? stage : 7], 1ull);
-#endif
-                    }
+                    const SlCellCheck c0 = sl_cell_check<SL_FAST>(M, d, aux, x, mean, err0);
+                    const SlCellCheck c1 = sl_cell_check<SL_FAST>(M, d, aux, x, mean, err1);
+                    neg_hi = c1.negative;
+                    // (a non-finite mean or err_hi leaves the cell, and so the block, undecided)
+                    open = c0.negative != c1.negative || !(fabs(c0.decrease) < INFINITY) ||
+                           !(fabs(c1.decrease) < INFINITY);
+                    v_x = values ? values[idx - lo] : c1.v_x;
                 }
-                (void)stage;
-                __syncthreads();
-                return __builtin_amdgcn_readfirstlane((int)*tile_decided) != 0;
+                const bool all = last || __ballot(open) == 0ull;
+                if (all) {
+                    const unsigned word = (unsigned)(__ballot(neg_hi) & 0xffffull);
+                    const int64_t b16 = (blk0 - lo) >> 4;
+                    unsigned init = 0u;
+                    if (init_bits) init = reinterpret_cast<const unsigned short*>(init_bits)[b16];
+                    if (lane == 0) reinterpret_cast<unsigned short*>(neg_bits)[b16] = (unsigned short)word;
+                    const bool okc = neg_hi || ((init >> lcol) & 1u);
+                    if (valid && !okc) sl_key_min(best_v, best_i, sl_vbits(v_x), idx);
+#ifdef SL_DIAG
+                    if (lane == 0 && !last && done < 4) atomicAdd(&sl_gp4_stage_count[done], 1ull);
+#endif
+                }
+                return all;
             };
-            if (early) {
+            if (early && stage == ACT_SOURCE) {
                 // The mean first: every chunk once, without the factor (a wavefront's mean_run reads
                 // the k_x values it has just written itself - no workgroup barrier between chunks),
                 // in the order and through the accumulators of the interleaved pass: the same bits.
-                // The seeds are stored as the first generation stores them; every generation of
-                // the panels below is then a re-generation (no chunk is new to them).
-                for (int ch = 0; ch < nchunks_head; ++ch) produce(ch, ch & 1, 0, true);
+                for (int ch = 0; ch < nchunks_head; ++ch) produce(ch, ch & 1, 0, false);
                 if (lk < dout)
                     cell_mean[(16 * wave + 4 * blk + low) * SL_D + hd.col0 + lk] =
                         (macc[0] + macc[1]) + (macc[2] + macc[3]);
-                decided = try_decide(0, false);
             }
-            for (int pan = decided ? npanels : 0; pan < npanels; ++pan) {
+#ifdef SL_DIAG
+            if (early && stage >= 0 && stage < 4 && tid == 0) atomicAdd(&sl_gp4_stage_count[4 + stage], 1ull);
+#endif
+            // (block mode: the one panel `stage` of a composite tile, none of a source tile)
+            for (int pan = early ? (stage >= 0 ? stage : npanels) : (decided ? npanels : 0);
+                 pan < (early ? stage + 1 : npanels); ++pan) {
                 acc_zero_all();
                 int rowoff[R];                     // byte offset of each owned row block's fragments
                 int nzd[R];                        // slab pairs of its diagonal chunk that are not zero
@@ -891,14 +985,14 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
                 const int nchunks = (pan + 1) * CPP;
                 const int first_new_chunk = early ? INT_MAX : pan * CPP;   // chunks not generated before (EARLY: none)
                 const bool keep = pan + 1 < npanels;
-                produce(0, 0, first_new_chunk, keep);
+                if (!early || have_blk) produce(0, 0, first_new_chunk, keep);
                 __syncthreads();
                 for (int ch = 0; ch < nchunks; ++ch) {
                     const int buf = ch & 1;
                     const int q = __builtin_amdgcn_readfirstlane(ch - CPP * pan);
                     const double* kxb = kx_l + buf * KXBUF;
                     if (!(skip & 8)) chunk_any(rsrc, kxb, rowoff, q, ch, lane, boff, nzd);
-                    if (ch + 1 < nchunks) produce(ch + 1, buf ^ 1, first_new_chunk, keep);
+                    if (ch + 1 < nchunks && (!early || have_blk)) produce(ch + 1, buf ^ 1, first_new_chunk, keep);
                     __syncthreads();
                 }
                 // |a|^2 of this panel's rows.  The rows of a block live in the four lane groups
@@ -918,7 +1012,7 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
                     // one plane per wavefront (LDS is short): the four rotations of a lane belong
                     // to four different cells, and within a rotation the lanes hit distinct cells,
                     // so the rotations are added one after the other (in-order LDS, same wavefront)
-                    if (pan == 0) {
+                    if (!early && pan == 0) {          // (block mode: the planes come with the record)
                         if (lane < 16) {
 #pragma unroll
                             for (int cb = 0; cb < CB; ++cb) part_ss[wave * C + 16 * cb + lane] = 0.0;
@@ -937,11 +1031,29 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
                         __builtin_amdgcn_wave_barrier();
                     }
                 }
-                // the rows so far may already decide the tile (the last panel ends in the epilogue)
-                if (early && pan + 1 < npanels) {
-                    decided = try_decide(pan + 1, true);
-                    if (decided) break;
+            }
+            if constexpr (early) {
+                // Every wavefront decides its block with the panels so far; a block still open
+                // waits in the queue of the next stage: first cell, means and planes go to the ring
+                // position of its rank among this pass's open blocks (thread 0 books the push at
+                // the top of the next pass, when every wavefront has asked for its position).
+                __syncthreads();                   // part_ss of every wavefront
+                const int done = stage + 1;
+                bool open_blk = false;
+                if (have_blk) open_blk = !decide_block(done);
+                if (open_blk && lane == 0) ctl->open[wave] = 1;
+                __syncthreads();
+                if (open_blk) {
+                    int rank = 0;
+                    for (int w = 0; w < wave; ++w) rank += ctl->open[w];
+                    double* rec_out = recs + (size_t)(done * GP4Q_CAP + gp4q_push_pos(ctl->q, done, rank)) * REC;
+                    if (lane == 0) *reinterpret_cast<int64_t*>(rec_out) = blk0;
+                    for (int i = lane; i < 16 * SL_D; i += 64) rec_out[REC_MEAN + i] = cell_mean[16 * wave * SL_D + i];
+                    if (done > 0) rec_out[REC_SS + lane] = part_ss[lk * C + 16 * wave + lcol];
                 }
+                if (tid == 0) ctl->push_stage = done;
+                __syncthreads();                   // positions asked, records written
+                break;
             }
             if (decided) break;
             if (!early && lk < dout)
@@ -958,7 +1070,8 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
             __syncthreads();
         }
 
-        if (decided) continue;                     // wavefront 0 wrote the word and folded the key
+        if constexpr (early) continue;             // every block wrote its bits or waits in a queue
+        if (decided) continue;
         // ---- per-cell decrease check, mask word, failing-cell key (as k_gp_sweep) -------------------
         const int64_t idx = tile_base + tid;
         const bool valid = (tid < C) && (idx < hi);
@@ -1001,10 +1114,10 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
 static size_t gp4_fixed_lds() {
     return sizeof(double) * (2 * gp4::KXBUF + gp4::W * gp4::C +
                              2 * gp4::C * SL_D + gp4::C * SL_P + gp4::W * gp4::RUNS * gp4::RUNC) +
-           (2 * gp4::W + 4) * sizeof(uint64_t);
+           (2 * gp4::W + 4) * sizeof(uint64_t) + sizeof(gp4::BlockCtl);
 }
 
-// May tiles be decided from bounds of the decrease (the kernel's try_decide)?  Conditions, not
+// May blocks be decided from bounds of the decrease (the kernel's decide_block)?  Conditions, not
 // measurements:
 //  * one GP head that fills every output column, no record output, no forced configuration
 //    (SL_GP_CFG), not switched off (sl_gp4_early_configure);
@@ -1046,12 +1159,18 @@ static int launch4(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, i
     }
     const size_t lds = gp4_fixed_lds();                       // two workgroups per CU: < 80 KB each
     static_assert(sizeof(double) * (2 * gp4::KXBUF + gp4::W * gp4::C + 2 * gp4::C * SL_D + gp4::C * SL_P +
-                                    gp4::W * gp4::RUNS * gp4::RUNC) + (2 * gp4::W + 4) * sizeof(uint64_t)
+                                    gp4::W * gp4::RUNS * gp4::RUNC) + (2 * gp4::W + 4) * sizeof(uint64_t) +
+                          sizeof(gp4::BlockCtl)
                       <= 80 * 1024, "two workgroups of k_gp_sweep4 per CU");
-    const bool early = gp4_early_ok(ctx, model, a.dbg);
+    // (block mode queues one stage per panel: larger training sets than GP4Q_STAGES panels stay plain)
+    const bool early = gp4_early_ok(ctx, model, a.dbg) &&
+                       (ctx->gp_heads[0].n + gp4::RP - 1) / gp4::RP <= GP4Q_STAGES;
     const int64_t resident = (int64_t)ctx->num_cu * 2;
     int64_t blocks = ntiles < resident ? ntiles : resident;
     if (blocks > SL_MAX_GRID) blocks = SL_MAX_GRID;
+    // sl_gp4_workgroups_configure (tests): few workgroups on a small grid, so that each draws many
+    // tiles and its queues fill composite tiles from different source tiles
+    if (sl_gp4_workgroup_cap > 0 && blocks > sl_gp4_workgroup_cap) blocks = sl_gp4_workgroup_cap;
     *nblocks = (int)blocks;
     SlAux aux{ctx->d_tri, ctx->d_net};
     const int skip = sl_diag_flags("SL_GP4_SKIP");            // (development builds only: 0 otherwise)
@@ -1062,10 +1181,15 @@ static int launch4(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, i
         seed_chunks = c > seed_chunks ? c : seed_chunks;
     }
     const size_t head_bytes = 16;                               // the tile counter
-    const size_t seed_bytes = head_bytes + (size_t)gp4::RUNS * blocks * seed_chunks * gp4::W * 128 * sizeof(double);
+    // block mode: the same scratch holds the pending records instead, [workgroup][stage][GP4Q_CAP][REC]
+    // (1344 B a record, 10.5 KiB per stage and workgroup: 42 KiB at 1024 points, 21 MiB for 512 workgroups)
+    const int stages = early ? (ctx->gp_heads[0].n + gp4::RP - 1) / gp4::RP : 0;
+    const size_t seed_bytes = head_bytes +
+        (early ? (size_t)blocks * stages * GP4Q_CAP * gp4::REC * sizeof(double)
+               : (size_t)gp4::RUNS * blocks * seed_chunks * gp4::W * 128 * sizeof(double));
     SL_HIP_CHECK(ctx, sl_grow(ctx, &ctx->d_gp4_seeds, &ctx->gp4_seed_bytes, seed_bytes));
     // SL_GP4_SEEDS=0: every generation from scratch (same k_x bit for bit: the test of that)
-    double* seeds = ctx->env.gp4_seeds == 0 ? nullptr : ctx->d_gp4_seeds + head_bytes / sizeof(double);
+    double* seeds = (ctx->env.gp4_seeds == 0 && !early) ? nullptr : ctx->d_gp4_seeds + head_bytes / sizeof(double);
     unsigned long long* ticket = reinterpret_cast<unsigned long long*>(ctx->d_gp4_seeds);
     const bool counter = ntiles >= 4 * blocks;
     if (counter) SL_HIP_CHECK(ctx, hipMemsetAsync(ticket, 0, head_bytes, ctx->stream));
@@ -1083,14 +1207,15 @@ static int launch4(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, i
         unsigned long long c[8];
         SL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         SL_HIP_CHECK(ctx, hipMemcpyFromSymbol(c, HIP_SYMBOL(sl_gp4_stage_count), sizeof(c)));
-        fprintf(stderr, "k_gp_sweep4 stages: tiles %lld decided before panel 0/1/2/3: %llu %llu %llu %llu "
-                        "(questions left open: %llu)\n", (long long)ntiles, c[0], c[1], c[2], c[3], c[7]);
+        fprintf(stderr, "k_gp_sweep4 stages: tiles %lld, 16-cell blocks decided before panel 0/1/2/3: %llu %llu %llu "
+                        "%llu, composite tiles run for panel 0/1/2/3: %llu %llu %llu %llu\n", (long long)ntiles,
+                c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7]);
         memset(c, 0, sizeof(c));
         SL_HIP_CHECK(ctx, hipMemcpyToSymbol(HIP_SYMBOL(sl_gp4_stage_count), c, sizeof(c)));
     }
 #endif
     sl_note_kernel(ctx, false, "k_gp_sweep4<d=%d, m=%d> (%d-row panels, %d workgroup(s) per CU%s)",
-                   DT, MT, gp4::RP, 2, early ? ", early decision" : "");
+                   DT, MT, gp4::RP, 2, early ? ", early decision, 16-cell blocks" : "");
     return SL_OK;
 }
 
@@ -1118,6 +1243,13 @@ SL_GP4_DIM_ENTRY(3)
 #endif
 #if !defined(SL_GP4_DIM) || SL_GP4_DIM == 4
 SL_GP4_DIM_ENTRY(4)
+
+int sl_gp4_workgroup_cap = 0;
+extern "C" int sl_gp4_workgroups_configure(sl_ctx* ctx, int workgroups) {
+    if (!ctx) return sl_fail(nullptr, SL_ERR_INVALID, "sl_gp4_workgroups_configure: NULL context");
+    sl_gp4_workgroup_cap = workgroups > 0 ? workgroups : 0;
+    return SL_OK;
+}
 
 // Fast-path models (closed-form or per-vertex table policy, quadratic V) with panels of 512 rows.
 int sl_gp4_sweep_launch(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, int* nblocks) {

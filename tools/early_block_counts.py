@@ -1,0 +1,119 @@
+"""How much variance-panel work does k_gp_sweep4's early decision leave, by the granule of cells
+that must be wholly decided before its panels stop?  Counted on the CPU with the oracle alone (no
+GPU): random 64-cell tiles of ``benchmarks.headline_case(variant)``, the bounds the kernel uses
+(``err = 0`` from below, ``beta sqrt(variance - partial |a|^2)`` from above, 256-row panels), for
+granules of 64 / 32 / 16 / 1 cells.  The kernel's granule is the 16-cell block; the
+64-cell row is what its predecessor counted on the device (profiles/early_stage_counts.txt), the
+1-cell row the floor.
+
+    python tools/early_block_counts.py [--variant informed|tight|survey] [--tiles 3000] [--seed 0]
+
+Panel p of a tile multiplies (p + 1) 4 chunks against its 16 row blocks, the diagonal band a
+triangle: 40 / 104 / 168 / 232 (row block, chunk) products for p = 0 .. 3, 64 more per panel
+after that."""
+import argparse
+import os
+import sys
+
+import numpy as np
+import scipy.linalg
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+RP = 256                                         # rows per panel of k_gp_sweep4
+GRANULES = (64, 32, 16, 1)
+
+
+def panel_weights(npan):
+    """(row block, chunk) products of panel 0 .. npan - 1 of a tile."""
+    return np.array([40 + 64 * p for p in range(npan)], dtype=float)
+
+
+def cell_stages(case, idx):
+    """Per cell of ``idx``: the stage at which the bounds decide it (0 = from the mean alone, s =
+    with s panels in |a|^2, npan = only the full sum does), its final mask bit, and whether its
+    decrease is clear of the threshold (beyond the 1e-7 relative agreement of engine and oracle).
+    Returns (stage, final, clear, npan)."""
+    import cases
+    ol = cases.oracle_lyapunov(case, compute_values=False)
+    grid, G = ol.discretization, ol.dynamics
+    gp = G.gaussian_process
+    L = gp.cholesky
+    npan = (L.shape[0] + RP - 1) // RP
+    x = grid.index_to_state(np.asarray(idx))
+    Xn = np.hstack((x, ol.policy(x)))
+    a = scipy.linalg.solve_triangular(L, gp.kern.K(gp.X, Xn), lower=True)
+    mean = a.T.dot(gp.alpha) + gp._mean(Xn)
+    var0 = gp.kern.Kdiag(Xn)
+    thr = np.broadcast_to(ol.threshold(x, ol.tau), (len(idx), 1))[:, 0]
+
+    def decrease(sumsq):
+        err = G.beta * np.sqrt(np.maximum(var0 - sumsq, 0))[:, None] * np.ones((1, mean.shape[1]))
+        return ol.v_decrease_bound(x, (mean, err))[:, 0]
+
+    dec = decrease(np.sum(a ** 2, 0))
+    final = dec < thr
+    clear = np.abs(dec - thr) > 1e-7 * (np.abs(dec) + np.abs(thr)) + 1e-12
+    sure_fail = ~(decrease(var0) < thr)                  # err = 0
+    stage = np.full(len(idx), npan)
+    part = np.zeros_like(var0)
+    for s in range(npan):
+        if s:
+            part = part + np.sum(a[(s - 1) * RP:s * RP] ** 2, 0)
+        done = sure_fail | (decrease(part) < thr)
+        stage[(stage == npan) & done] = s
+    return stage, final, clear, npan
+
+
+def granule_stages(stage, granule):
+    """Stage at which every cell of a granule of consecutive cells is decided."""
+    return stage.reshape(-1, granule).max(1)
+
+
+def open_fractions(gstage, npan):
+    """Fraction of granules still open before panel 0 .. npan - 1."""
+    return np.array([(gstage > p).mean() for p in range(npan)])
+
+
+def panel_work(gstage, npan):
+    """Panel work executed, as a fraction of every panel of every granule."""
+    w = panel_weights(npan)
+    return float(open_fractions(gstage, npan).dot(w) / w.sum())
+
+
+def sample_tiles(case, tiles, seed):
+    """Cell indices of ``tiles`` random 64-cell tiles of the case's grid (tile-aligned)."""
+    n = int(np.prod(case["num_points"]))
+    rng = np.random.default_rng(seed)
+    first = rng.choice(n // 64, size=min(tiles, n // 64), replace=False) * 64
+    return (first[:, None] + np.arange(64)[None, :]).reshape(-1)
+
+
+def count(variant=None, tiles=3000, seed=0, batch=500):
+    """{granule: (open fractions before each panel, panel work)} over random tiles."""
+    from safe_learning_amd.benchmarks import headline_case
+    case = headline_case(variant=variant)
+    idx = sample_tiles(case, tiles, seed)
+    stages = []
+    for b in range(0, len(idx), batch * 64):             # (bounded memory: n x cells factors)
+        st, _, _, npan = cell_stages(case, idx[b:b + batch * 64])
+        stages.append(st)
+    stage = np.concatenate(stages)
+    return {g: (open_fractions(granule_stages(stage, g), npan), panel_work(granule_stages(stage, g), npan))
+            for g in GRANULES}, npan
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--variant", default=None)
+    ap.add_argument("--tiles", type=int, default=3000)
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+    result, npan = count(args.variant, args.tiles, args.seed)
+    print("# headline_case(variant=%r), %d random tiles, seed %d, %d panels" % (args.variant, args.tiles, args.seed, npan))
+    print("# granule (cells) | open before panel 0 .. %d | panel work executed" % (npan - 1))
+    for g in GRANULES:
+        frac, work = result[g]
+        print("%5d | %s | %.3f" % (g, " / ".join("%.3f" % f for f in frac), work))

@@ -1,7 +1,7 @@
 """Regenerate profiles/README.md: one row per shipped kernel (source file, the configuration that
 measures it, ms, fraction of its roof, the counter / A-B files behind the number) and a list of what
 else is in profiles/.  Reads profiles/r06_configs.jsonl (tools/bench_configs.sh), the headline line
-profiles/r06_bench_driver_command.log and profiles/early_bench_headline.jsonl, profiles/pmc_traffic.json and
+profiles/r06_bench_driver_command.log, profiles/early_bench_headline.jsonl and profiles/blocks_ab_headline.jsonl, profiles/pmc_traffic.json and
 profiles/pmc_valu.json.
 
     python tools/profiles_index.py"""
@@ -13,7 +13,8 @@ P = os.path.join(ROOT, "profiles")
 
 # kernel -> (source, configuration that measures it, files with the evidence)
 KERNELS = [
-    ("k_gp_sweep4", "csrc/sl_gp4.hip", "C4", "early_ab_headline.jsonl (parent / early / plain, interleaved on one box), early_kernel_stats.md, early_pmc_48.txt, early_pmc_128.txt, "
+    ("k_gp_sweep4", "csrc/sl_gp4.hip", "C4", "blocks_ab_headline.jsonl (parent / 16-cell blocks, alternating on one box), blocks_other_lines.txt, blocks_kernel_stats.md, "
+     "blocks_stage_counts.txt, blocks_pmc_128.txt, blocks_little_skipped.txt, blocks_cpu_counts.txt (tools/early_block_counts.py); the 64-cell early decision before it: early_ab_headline.jsonl (parent / early / plain, interleaved on one box), early_kernel_stats.md, early_pmc_48.txt, early_pmc_128.txt, "
      "early_stage_counts.txt, early_ab_other_lines.jsonl, early_dump_outputs.txt, early_little_skipped.txt; the plain instantiation (every panel of every tile): r06_kernel_stats.md, r06_pmc_48.txt, r06_pmc_128.txt, r05_pmc_l2_64.txt, pmc_traffic.json; "
      "A/B: dropped/r06_gp4_alias_ab.txt (phases; every factor read an L2 hit: -1 %), dropped/r06_gp4_seeds_nontemporal_ab.txt, dropped/r06_gp4_seed_latency_ab.txt, r05_gp4_diag_ab.txt"),
     ("k_gp_sweep4 (n = 512, 1024 tiles)", "csrc/sl_gp4.hip", "C2", "r06_C2_kernel_stats.md, r05_C2_ab.txt; dropped/r06_gp4_stagger_ab.txt (tile-count series at 512 points)"),
@@ -51,6 +52,7 @@ def main():
     lines = load_lines("r06_configs.jsonl")
     lines.update(load_lines("r06_bench_driver_command.log"))
     lines.update(load_lines("early_bench_headline.jsonl"))      # the headline with the early tile decision
+    lines.update(load_lines("blocks_ab_headline.jsonl"))        # ... on packed 16-cell blocks (the last line: this commit)
     try:
         valu = json.load(open(os.path.join(P, "pmc_valu.json")))
     except (OSError, ValueError):
