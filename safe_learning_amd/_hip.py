@@ -150,6 +150,7 @@ SIGNATURES = {
     "sl_gp_configure": (_int, (_vp, _int, _dbl)),
     "sl_gp4_early_configure": (_int, (_vp, _int)),
     "sl_gp4_workgroups_configure": (_int, (_vp, _int)),
+    "sl_gp4_segment_configure": (_int, (_vp, _int)),
     "sl_tri_set": (_int, (_vp, _int, C.POINTER(GridDesc), _int, _int32_p, c_double_p, c_double_p, _int, _int,
                           _vp)),
     "sl_tri_set_table": (_int, (_vp, _int, _vp)),
@@ -324,6 +325,10 @@ class Context(object):
         # small grid draws many tiles.  Set by every new context (unset: no cap).
         if hasattr(self.lib, "sl_gp4_workgroups_configure"):
             self.lib.sl_gp4_workgroups_configure(self.handle, int(os.environ.get("SL_GP4_WORKGROUPS") or 0))
+        # SL_GP4_SEGMENT_TILES=N (tests): every block-mode launch of k_gp_sweep4 runs k_gp_mean_blocks
+        # first, in segments of N source tiles
+        if hasattr(self.lib, "sl_gp4_segment_configure"):
+            self.lib.sl_gp4_segment_configure(self.handle, int(os.environ.get("SL_GP4_SEGMENT_TILES") or 0))
 
     def close(self):
         if getattr(self, "handle", None):

@@ -38,6 +38,8 @@
 // 4x4x4 kernel 60.5 (profiles/r02_summary.md); round 3: 62.4 TFLOP/s at 128^4 (profiles/r03_summary.md).
 #include "sl_common.h"
 #include "sl_gp4_clobbers.h"
+#include "sl_gp4_gen.h"
+#include "sl_gp4_mean.h"
 #include "sl_gp4_queue.h"
 
 #ifdef SL_NO_GP4
@@ -48,14 +50,16 @@ int sl_gp4_sweep_launch(sl_ctx* ctx, const SlDevModel&, const SlSweepArgs&, int*
     return sl_fail(ctx, SL_ERR_UNSUPPORTED, "k_gp_sweep4 is compiled out of this build");
 }
 extern "C" int sl_gp4_workgroups_configure(sl_ctx*, int) { return SL_OK; }
+extern "C" int sl_gp4_segment_configure(sl_ctx*, int) { return SL_OK; }
 #else
 
 // sl_gp4_workgroups_configure: at most this many workgroups per launch (0: no cap).  One value for
 // the process - a knob of the tests, which run one context at a time.
 extern int sl_gp4_workgroup_cap;
+// sl_gp4_segment_configure: source tiles per segment of a block-mode launch, which then always runs
+// the mean kernel (0: large launches only, segments from the scratch budget).  A knob of the tests too.
+extern int sl_gp4_segment_tiles;
 
-typedef double sl_d2 __attribute__((ext_vector_type(2)));
-typedef unsigned sl_u4 __attribute__((ext_vector_type(4)));
 
 namespace gp4 {
 
@@ -100,6 +104,8 @@ struct BlockCtl {
     int push_stage;
     int src_done;          // the source tiles are used up
     int nsrc;              // source tiles drawn (round-robin lists)
+    int from_list;         // the composite's slots are records of the segment's list, not ring positions
+    unsigned nlist;        // records of that list
 };
 constexpr int ACT_SOURCE = GP4Q_SOURCE, ACT_DONE = GP4Q_DONE;
 
@@ -390,42 +396,6 @@ __device__ __forceinline__ void chunk_any(__amdgpu_buffer_rsrc_t rsrc, const dou
     }
 }
 
-// exp of two arguments (sl_exp_nonpos twice), the two dependent FMA chains written alternately: a
-// single wavefront per SIMD has nobody else to fill the latency of a 13-deep chain
-__device__ __forceinline__ void exp_pair(double x1, double x2, double& e1, double& e2) {
-    x1 = x1 < -800.0 ? -800.0 : x1;
-    x2 = x2 < -800.0 ? -800.0 : x2;
-    const double k1 = rint(x1 * 1.4426950408889634), k2 = rint(x2 * 1.4426950408889634);
-    double r1 = fma(k1, -6.93147180369123816490e-01, x1), r2 = fma(k2, -6.93147180369123816490e-01, x2);
-    r1 = fma(k1, -1.90821492927058770002e-10, r1);
-    r2 = fma(k2, -1.90821492927058770002e-10, r2);
-    double q1 = 1.6059043836821613e-10, q2 = 1.6059043836821613e-10;
-#define SL_EXP_STEP(C) q1 = fma(q1, r1, C); q2 = fma(q2, r2, C)
-    SL_EXP_STEP(2.08767569878681e-09);
-    SL_EXP_STEP(2.505210838544172e-08);
-    SL_EXP_STEP(2.755731922398589e-07);
-    SL_EXP_STEP(2.7557319223985893e-06);
-    SL_EXP_STEP(2.48015873015873e-05);
-    SL_EXP_STEP(1.984126984126984e-04);
-    SL_EXP_STEP(1.3888888888888889e-03);
-    SL_EXP_STEP(8.333333333333333e-03);
-    SL_EXP_STEP(4.1666666666666664e-02);
-    SL_EXP_STEP(1.6666666666666666e-01);
-    SL_EXP_STEP(0.5);
-    SL_EXP_STEP(1.0);
-    SL_EXP_STEP(1.0);
-#undef SL_EXP_STEP
-    e1 = ldexp(q1, (int)k1);
-    e2 = ldexp(q2, (int)k2);
-}
-
-// a wave-uniform double held in scalar registers
-__device__ __forceinline__ double uniform(double v) {
-    const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
-    const int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
-    return __hiloint2double(hi, lo);
-}
-
 }  // namespace gp4
 
 #ifdef SL_DIAG
@@ -442,13 +412,17 @@ static __device__ unsigned long long sl_gp4_stage_count[8];
 // that the plain path (EARLY = false: records, several heads, switched off) stays the code it was.
 // `seeds` is then the workgroups' record scratch ([workgroup][stage][GP4Q_CAP][REC], seed_chunks
 // = stages) - a queued block regenerates its k_x from the exponentials.
+// `lst` (block mode of large launches: lst.cell != nullptr): the source pass has run in
+// k_gp_mean_blocks (sl_gp4_mean.hip), which decided what the mean decides and listed the blocks it
+// left open; a "source" action then draws the next four records of that list with the ticket - a
+// full stage-0 composite, only the last draw partly filled - and the kernel runs panels only.
 template <int DT, int MT, bool EARLY>
 __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
     const SlDevModel M, const SlGpDev gp, SlAux aux, int64_t lo, int64_t hi, int64_t ntiles,
     const uint64_t* __restrict__ init_bits, const double* __restrict__ values,
     uint64_t* __restrict__ neg_bits, sl_key* __restrict__ partials, double* __restrict__ dbg,
     const double* __restrict__ points, int skip_arg, double* __restrict__ seeds, int seed_chunks,
-    unsigned long long* __restrict__ ticket) {
+    unsigned long long* __restrict__ ticket, const Gp4ListArgs lst) {
     constexpr bool early = EARLY;
     // skip (SL_GP4_SKIP; development builds, -DSL_DIAG, only): 1 no k_x generation, 2 no mean pass,
     // 4 no per-cell check, 8 no MFMA chunks - timing attribution, the results are then meaningless;
@@ -529,6 +503,8 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
         ctl->push_stage = 0;
         ctl->src_done = 0;
         ctl->nsrc = 0;
+        ctl->from_list = 0;
+        ctl->nlist = lst.cell ? *lst.count : 0u;
     }
     for (int64_t round = 0;; ++round) {
         int stage = ACT_SOURCE;                    // block mode: the panel of a composite tile
@@ -537,13 +513,20 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
                 int n = 0;                         // the blocks the pass before left open are queued
                 for (int w = 0; w < W; ++w) { n += ctl->open[w]; ctl->open[w] = 0; }
                 if (n) gp4q_push(ctl->q, ctl->push_stage, n);
-                const int st = gp4q_schedule(ctl->q, nstages, ctl->src_done, ctl->pos, [&]() {
+                const int64_t nsource = lst.cell ? (int64_t)gp4l_draws(ctl->nlist) : ntiles;
+                int st = gp4q_schedule(ctl->q, nstages, ctl->src_done, ctl->pos, [&]() {
                     const int64_t t = ticket ? (int64_t)atomicAdd(ticket, 1ull)
                                              : (int64_t)blockIdx.x + (int64_t)ctl->nsrc * gridDim.x;
                     ctl->nsrc += 1;
-                    if (t < ntiles) *next_tile = t;
-                    return t < ntiles;
+                    if (t < nsource) *next_tile = t;
+                    return t < nsource;
                 });
+                ctl->from_list = 0;
+                if (lst.cell && st == ACT_SOURCE) {    // draw *next_tile of the list: panel 0 on its records
+                    for (int w = 0; w < GP4Q_SLOTS; ++w) ctl->pos[w] = (int)gp4l_slot(*next_tile, w, ctl->nlist);
+                    ctl->from_list = 1;
+                    st = 0;
+                }
                 ctl->action = st;
             }
             __syncthreads();
@@ -566,13 +549,16 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
         bool have_blk = true;
         int64_t blk0 = tile_base + 16 * wave;
         const double* rec_in = nullptr;
+        const double* list_mean = nullptr;             // the block's record in the segment's list: [16][d] means
         if (early && stage >= 0) {
             const int pos = __builtin_amdgcn_readfirstlane(ctl->pos[wave]);
             have_blk = pos >= 0;
-            rec_in = recs + (size_t)(stage * GP4Q_CAP + (have_blk ? pos : 0)) * REC;
+            const bool listed = __builtin_amdgcn_readfirstlane(ctl->from_list) != 0;
+            rec_in = recs + (size_t)(stage * GP4Q_CAP + (have_blk && !listed ? pos : 0)) * REC;
+            if (listed) list_mean = lst.mean + (size_t)(have_blk ? pos : 0) * 16 * d;
             blk0 = hi - 1;
             if (have_blk) {
-                const int64_t b = *reinterpret_cast<const int64_t*>(rec_in);
+                const int64_t b = listed ? (int64_t)lst.cell[pos] : *reinterpret_cast<const int64_t*>(rec_in);
                 blk0 = ((int64_t)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) |
                        (int64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)b);
             }
@@ -620,7 +606,12 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
             if (early && stage >= 0 && have_blk) {
                 // slot `wave` of a composite tile: the block's means and the |a|^2 of the panels
                 // before this one (the plane update then starts from them, from 0 at panel 0)
-                for (int i = lane; i < 16 * SL_D; i += 64) cell_mean[16 * wave * SL_D + i] = rec_in[REC_MEAN + i];
+                if (list_mean) {
+                    for (int i = lane; i < 16 * d; i += 64)
+                        cell_mean[(16 * wave + i / d) * SL_D + i % d] = list_mean[i];
+                } else {
+                    for (int i = lane; i < 16 * SL_D; i += 64) cell_mean[16 * wave * SL_D + i] = rec_in[REC_MEAN + i];
+                }
                 part_ss[lk * C + 16 * wave + lcol] = stage > 0 ? rec_in[REC_SS + lane] : 0.0;
             }
             __syncthreads();
@@ -1105,7 +1096,11 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
     }
     __syncthreads();
     sl_block_reduce_key<true>(best_v, best_i, sv, si);
-    if (tid == 0) { partials[blockIdx.x].vbits = best_v; partials[blockIdx.x].index = best_i; }
+    if (tid == 0) {
+        if (early && lst.fold) sl_key_min(best_v, best_i, partials[blockIdx.x].vbits, partials[blockIdx.x].index);
+        partials[blockIdx.x].vbits = best_v;
+        partials[blockIdx.x].index = best_i;
+    }
 }
 
 // =============================================================================================
@@ -1180,33 +1175,79 @@ static int launch4(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, i
         const int c = ctx->gp_heads[h].n_pad / 64;
         seed_chunks = c > seed_chunks ? c : seed_chunks;
     }
-    const size_t head_bytes = 16;                               // the tile counter
+    const size_t head_bytes = 64;       // the tile counter; block mode: [1] tiles the mean kernel drew, [2] its list length
     // block mode: the same scratch holds the pending records instead, [workgroup][stage][GP4Q_CAP][REC]
     // (1344 B a record, 10.5 KiB per stage and workgroup: 42 KiB at 1024 points, 21 MiB for 512 workgroups)
     const int stages = early ? (ctx->gp_heads[0].n + gp4::RP - 1) / gp4::RP : 0;
+    const bool counter = ntiles >= 4 * blocks;
+    // Block mode of a large launch (the condition of the tile counter; sl_gp4_segment_configure forces
+    // it): the source pass runs in k_gp_mean_blocks, segment by segment of `seg` source tiles, and
+    // leaves the open blocks of a segment in a list behind the records - first cells, then the
+    // means, sized for every block open (4 seg records: it cannot overflow).  `seg` is the largest
+    // power of two whose list fits GP4_LIST_BUDGET.  A small launch keeps the source pass in the
+    // panel kernel: two launches and a memset more per sweep are a tenth of C2's 0.3 ms step.
+    constexpr long long GP4_LIST_BUDGET = 520ll << 20;          // 512 MiB of means + 8 MiB of first cells at d = 4
+    const bool split = early && (sl_gp4_segment_tiles > 0 || counter);
+    long long seg = 0, nseg = 1;
+    if (split) {
+        seg = gp4l_segment_tiles(GP4_LIST_BUDGET, DT);
+        if (sl_gp4_segment_tiles > 0) seg = sl_gp4_segment_tiles;
+        if (seg > ntiles) seg = ntiles;
+        nseg = gp4l_segments(ntiles, seg);
+    }
+    const size_t list_cap = (size_t)GP4Q_SLOTS * (size_t)seg;
+    const size_t rec_bytes = early ? (size_t)blocks * stages * GP4Q_CAP * gp4::REC * sizeof(double) : 0;
     const size_t seed_bytes = head_bytes +
-        (early ? (size_t)blocks * stages * GP4Q_CAP * gp4::REC * sizeof(double)
+        (early ? rec_bytes + list_cap * (sizeof(long long) + 16 * DT * sizeof(double))
                : (size_t)gp4::RUNS * blocks * seed_chunks * gp4::W * 128 * sizeof(double));
+    if (split && list_cap * (sizeof(long long) + 16 * DT * sizeof(double)) > (size_t)GP4_LIST_BUDGET &&
+        sl_gp4_segment_tiles <= 0)
+        return sl_fail(ctx, SL_ERR_INVALID, "k_gp_sweep4: the list of a segment exceeds its scratch budget");
     SL_HIP_CHECK(ctx, sl_grow(ctx, &ctx->d_gp4_seeds, &ctx->gp4_seed_bytes, seed_bytes));
     // SL_GP4_SEEDS=0: every generation from scratch (same k_x bit for bit: the test of that)
     double* seeds = (ctx->env.gp4_seeds == 0 && !early) ? nullptr : ctx->d_gp4_seeds + head_bytes / sizeof(double);
     unsigned long long* ticket = reinterpret_cast<unsigned long long*>(ctx->d_gp4_seeds);
-    const bool counter = ntiles >= 4 * blocks;
-    if (counter) SL_HIP_CHECK(ctx, hipMemsetAsync(ticket, 0, head_bytes, ctx->stream));
-    else ticket = nullptr;
-    const int rc = sl_with_dim<1, 0>(early, [&](auto e) {
-        SL_HIP_CHECK(ctx, sl_launch_lds(k_gp_sweep4<DT, MT, e != 0>, dim3((unsigned)blocks), dim3(gp4::W * 64), lds,
-                                        ctx->stream, model, ctx->h_gp, aux, lo, hi, ntiles, a.init_bits, a.values,
-                                        a.neg_bits, ctx->d_partials, a.dbg, a.points, skip, seeds, seed_chunks,
-                                        ticket));
-        return SL_OK;
-    });
-    if (rc) return rc;
+    if (!split) {
+        if (counter) SL_HIP_CHECK(ctx, hipMemsetAsync(ticket, 0, head_bytes, ctx->stream));
+        else ticket = nullptr;
+        const int rc = sl_with_dim<1, 0>(early, [&](auto e) {
+            SL_HIP_CHECK(ctx, sl_launch_lds(k_gp_sweep4<DT, MT, e != 0>, dim3((unsigned)blocks), dim3(gp4::W * 64), lds,
+                                            ctx->stream, model, ctx->h_gp, aux, lo, hi, ntiles, a.init_bits, a.values,
+                                            a.neg_bits, ctx->d_partials, a.dbg, a.points, skip, seeds, seed_chunks,
+                                            ticket, Gp4ListArgs{nullptr, nullptr, nullptr, 0}));
+            return SL_OK;
+        });
+        if (rc) return rc;
+    } else {
+        long long* list_cell = reinterpret_cast<long long*>(reinterpret_cast<char*>(seeds) + rec_bytes);
+        double* list_mean = reinterpret_cast<double*>(list_cell + list_cap);
+        unsigned* list_count = reinterpret_cast<unsigned*>(ticket + 2);
+        const int mean_wg = sl_gp4_mean_workgroups(ctx, seg);
+        if (blocks + 4 * (int64_t)mean_wg > 4 * SL_MAX_GRID)
+            return sl_fail(ctx, SL_ERR_INVALID, "k_gp_sweep4: more keys than d_partials holds");
+        for (long long k = 0; k < nseg; ++k) {
+            const long long t0 = gp4l_segment_first(seg, k), nt = gp4l_segment_count(ntiles, seg, k);
+            if ((size_t)GP4Q_SLOTS * (size_t)nt > list_cap)
+                return sl_fail(ctx, SL_ERR_INVALID, "k_gp_sweep4: a segment larger than its list");
+            SL_HIP_CHECK(ctx, hipMemsetAsync(ticket, 0, head_bytes, ctx->stream));
+            const Gp4MeanLaunch ml{mean_wg, t0, t0 + nt, ctx->d_partials + blocks, k > 0, ticket + 1, list_count,
+                                   list_cell, list_mean, (unsigned)list_cap};
+            const int rc = sl_gp4_mean_launch_dim<DT>(ctx, model, a, ml);
+            if (rc) return rc;
+            // (the ticket also hands out the round-robin draws of a capped launch: few workgroups, any list)
+            SL_HIP_CHECK(ctx, sl_launch_lds(k_gp_sweep4<DT, MT, true>, dim3((unsigned)blocks), dim3(gp4::W * 64), lds,
+                                            ctx->stream, model, ctx->h_gp, aux, lo, hi, ntiles, a.init_bits, a.values,
+                                            a.neg_bits, ctx->d_partials, a.dbg, a.points, skip, seeds, seed_chunks,
+                                            ticket, Gp4ListArgs{list_cell, list_mean, list_count, k > 0}));
+        }
+        *nblocks = (int)blocks + 4 * mean_wg;
+    }
 #ifdef SL_DIAG
     if (skip & 16) {
         unsigned long long c[8];
         SL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         SL_HIP_CHECK(ctx, hipMemcpyFromSymbol(c, HIP_SYMBOL(sl_gp4_stage_count), sizeof(c)));
+        c[0] += sl_gp4_mean_decided_fetch(ctx);               // (a -DSL_DIAG build of sl_gp4_mean.hip counts them)
         fprintf(stderr, "k_gp_sweep4 stages: tiles %lld, 16-cell blocks decided before panel 0/1/2/3: %llu %llu %llu "
                         "%llu, composite tiles run for panel 0/1/2/3: %llu %llu %llu %llu\n", (long long)ntiles,
                 c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7]);
@@ -1214,6 +1255,10 @@ static int launch4(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, i
         SL_HIP_CHECK(ctx, hipMemcpyToSymbol(HIP_SYMBOL(sl_gp4_stage_count), c, sizeof(c)));
     }
 #endif
+    if (split)
+        sl_note_kernel(ctx, false, "k_gp_sweep4<d=%d, m=%d> (%d-row panels, %d workgroup(s) per CU, early decision, 16-cell "
+                                   "blocks) after k_gp_mean_blocks, %lld segment(s)", DT, MT, gp4::RP, 2, nseg);
+    else
     sl_note_kernel(ctx, false, "k_gp_sweep4<d=%d, m=%d> (%d-row panels, %d workgroup(s) per CU%s)",
                    DT, MT, gp4::RP, 2, early ? ", early decision, 16-cell blocks" : "");
     return SL_OK;
@@ -1245,6 +1290,12 @@ SL_GP4_DIM_ENTRY(3)
 SL_GP4_DIM_ENTRY(4)
 
 int sl_gp4_workgroup_cap = 0;
+int sl_gp4_segment_tiles = 0;
+extern "C" int sl_gp4_segment_configure(sl_ctx* ctx, int tiles) {
+    if (!ctx) return sl_fail(nullptr, SL_ERR_INVALID, "sl_gp4_segment_configure: NULL context");
+    sl_gp4_segment_tiles = tiles > 0 ? tiles : 0;
+    return SL_OK;
+}
 extern "C" int sl_gp4_workgroups_configure(sl_ctx* ctx, int workgroups) {
     if (!ctx) return sl_fail(nullptr, SL_ERR_INVALID, "sl_gp4_workgroups_configure: NULL context");
     sl_gp4_workgroup_cap = workgroups > 0 ? workgroups : 0;

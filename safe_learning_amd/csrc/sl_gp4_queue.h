@@ -78,6 +78,43 @@ SL_HD bool gp4q_empty(const Gp4Queues& q, int nstages) {
     return true;
 }
 
+// ---- the list of stage-0 records and the segments of a launch ---------------------------------
+// Large launches decide the blocks in a kernel of their own (k_gp_mean_blocks, sl_gp4_mean.hip):
+// the shard is cut into segments of S source tiles, the mean kernel appends one record per block it
+// leaves open to a list (order free, position from a device counter), and the panel kernel's
+// "source" action draws the next four records of that list: a full stage-0 composite, only the
+// last draw may be partly filled.
+struct Gp4ListArgs {
+    const long long* cell;       // first cell of every record (nullptr: source tiles in the kernel itself)
+    const double* mean;          // [record][16][d] posterior means
+    const unsigned* count;       // records the mean kernel appended
+    int fold;                    // a later segment: fold the key already in the workgroup's partial
+};
+
+SL_HD long long gp4l_draws(long long n) { return (n + GP4Q_SLOTS - 1) / GP4Q_SLOTS; }
+
+// Record of slot w of draw t for a list of n records, -1: the slot stays empty.
+SL_HD long long gp4l_slot(long long t, int w, long long n) {
+    const long long r = t * GP4Q_SLOTS + w;
+    return r < n ? r : -1;
+}
+
+// Source tiles per segment: the largest power of two whose worst case - every block of every tile
+// open, 4 S records of 16 d means and a first cell - fits `budget` bytes (at least one tile).
+SL_HD long long gp4l_segment_tiles(long long budget, int d) {
+    const long long per_tile = GP4Q_SLOTS * (16LL * d * 8 + 8);
+    long long s = 1;
+    while (2 * s * per_tile <= budget) s *= 2;
+    return s;
+}
+SL_HD long long gp4l_segments(long long ntiles, long long seg) { return (ntiles + seg - 1) / seg; }
+// Tiles [first, first + n) of segment k.
+SL_HD long long gp4l_segment_first(long long seg, long long k) { return k * seg; }
+SL_HD long long gp4l_segment_count(long long ntiles, long long seg, long long k) {
+    const long long left = ntiles - k * seg;
+    return left < 0 ? 0 : (left < seg ? left : seg);
+}
+
 // What a workgroup does next: the stage (>= 0) whose panel runs on the composite tile of the
 // records at pos[0 .. 3], GP4Q_SOURCE (draw() handed out a source tile) or GP4Q_DONE.  draw()
 // returns false once the source tiles are used up (remembered in src_done: it is not asked again).

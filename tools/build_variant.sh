@@ -14,6 +14,7 @@ obj=safe_learning_amd/build/variants/${name}_${unit}.o
 extra=""
 case $unit in sl_gp4_*) extra="-mllvm -amdgpu-spill-vgpr-to-agpr=0";; esac
 case $unit in sl_gp4_d?) extra="$extra -DSL_GP4_DIM=${unit#sl_gp4_d}";; esac
+case $unit in sl_gp4_mean_d?) extra="$extra -DSL_GP4_DIM=${unit#sl_gp4_mean_d}";; esac
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC ${SL_VARIANT_VIS--fvisibility=hidden} \
     -DSL_DIAG -Iinclude -Isafe_learning_amd/csrc $extra "$@" -c "$src" -o "$obj"
 objs=""

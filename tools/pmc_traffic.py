@@ -17,14 +17,22 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def per_dispatch(db, counter, kernel_substr):
+    """(name of the sweep kernel, counter per SWEEP).  A block-mode sweep of a large grid is several
+    launches - k_gp_mean_blocks and k_gp_sweep4 once per segment - so the counter is summed over
+    both kernels and divided by the number of sweeps (one k_reduce_fail each)."""
     cur = sqlite3.connect(db).cursor()
     rows = list(cur.execute(
         "select kernel_name, sum(value), count(*) from counters_collection where counter_name = ? "
         "group by kernel_name", (counter,)))
-    for name, total, count in rows:
-        if kernel_substr in name:
-            return name, total / count
-    raise SystemExit("kernel %s not found in %s" % (kernel_substr, db))
+    mine = [(name, total, count) for name, total, count in rows
+            if kernel_substr in name or "k_gp_mean_blocks" in name]
+    if not any(kernel_substr in name for name, _, _ in mine):
+        raise SystemExit("kernel %s not found in %s" % (kernel_substr, db))
+    sweeps = sum(count for name, _, count in rows if "k_reduce_fail" in name)
+    if not sweeps:
+        sweeps = max(count for name, _, count in mine if kernel_substr in name)
+    name = next(name for name, _, _ in mine if kernel_substr in name)
+    return name, sum(total for _, total, _ in mine) / sweeps
 
 
 def kernel_source_sha():
@@ -44,7 +52,7 @@ def main():
            "fetch_size_kib_reported": fetch_kib, "write_size_kib_reported": write_kib,
            "bytes_per_launch": (2.0 * fetch_kib + write_kib) * 1024.0,
            "source_sha256": kernel_source_sha(),
-           "note": "L2<->fabric bytes per launch of the GP sweep kernel: (2 x FETCH_SIZE + WRITE_SIZE) x 1024 "
+           "note": "L2<->fabric bytes per sweep of the GP sweep kernels (k_gp_mean_blocks + k_gp_sweep4, all segments): (2 x FETCH_SIZE + WRITE_SIZE) x 1024 "
                    "(KiB units, FETCH_SIZE doubled for gfx950 as MI355X_MICROARCH.md prescribes): L2 misses "
                    "of the inverse Cholesky factor's fragments served by the Infinity Cache (an upper bound "
                    "of the HBM reads) + mask words and set-up scratch; profiles/README.md."}
