@@ -226,15 +226,15 @@ SL_API int  sl_gp_configure(sl_ctx* ctx, int nheads, double beta);
 SL_API int  sl_gp4_early_configure(sl_ctx* ctx, int enable);
 /* At most `workgroups` workgroups per launch of k_gp_sweep4 (0, the default: as many as the device
  * holds).  For tests: on a small grid one workgroup then draws many tiles, and the queues of its open
- * 16-cell blocks fill composite tiles from different source tiles.  The value is kept once per
- * process, not per context, and takes effect at the next sweep. */
+ * 16-cell blocks fill composite tiles from different source tiles.  The value belongs to the
+ * context and takes effect at its next sweep. */
 SL_API int  sl_gp4_workgroups_configure(sl_ctx* ctx, int workgroups);
 /* A block-mode launch of k_gp_sweep4 that is large enough for the tile counter decides the blocks in
  * a kernel of its own (k_gp_mean_blocks), segment by segment of source tiles, and runs the panels on
  * the list of open blocks each segment leaves.  tiles > 0: every block-mode launch does, in segments
  * of `tiles` source tiles (tests: several segments, empty and ragged lists on small grids); 0, the
- * default: large launches only, the segment size from the scratch budget.  Kept once per process,
- * takes effect at the next sweep. */
+ * default: large launches only, the segment size from the scratch budget.  Belongs to the context,
+ * takes effect at its next sweep. */
 SL_API int  sl_gp4_segment_configure(sl_ctx* ctx, int tiles);
 
 /* Auxiliary grid #slot with a per-vertex table (Triangulation: functions.py:1002-1032,

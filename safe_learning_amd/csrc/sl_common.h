@@ -98,6 +98,10 @@ struct sl_ctx {
     size_t scratch_bytes = 0;
     double* d_gp4_seeds = nullptr;     // k_gp_sweep4: seeds of the k_x sequences, per workgroup
     bool gp4_early = true;             // k_gp_sweep4 may decide tiles early (sl_gp4_early_configure)
+    // knobs of the tests on k_gp_sweep4's block mode, 0 = off:
+    int gp4_workgroup_cap = 0;         // at most this many workgroups per launch (sl_gp4_workgroups_configure)
+    int gp4_segment_tiles = 0;         // source tiles per segment; the launch then always runs the mean kernel
+                                       // (sl_gp4_segment_configure; off: large launches only, segments from the scratch budget)
     size_t gp4_seed_bytes = 0;
     void* d_records = nullptr;         // GP posterior records of the two-pass network check
     size_t records_bytes = 0;

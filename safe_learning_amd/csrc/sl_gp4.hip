@@ -53,14 +53,6 @@ extern "C" int sl_gp4_workgroups_configure(sl_ctx*, int) { return SL_OK; }
 extern "C" int sl_gp4_segment_configure(sl_ctx*, int) { return SL_OK; }
 #else
 
-// sl_gp4_workgroups_configure: at most this many workgroups per launch (0: no cap).  One value for
-// the process - a knob of the tests, which run one context at a time.
-extern int sl_gp4_workgroup_cap;
-// sl_gp4_segment_configure: source tiles per segment of a block-mode launch, which then always runs
-// the mean kernel (0: large launches only, segments from the scratch budget).  A knob of the tests too.
-extern int sl_gp4_segment_tiles;
-
-
 namespace gp4 {
 
 // R row blocks per wavefront: 256 registers (64 accumulators, 256-row panels) and at most 80 KB of
@@ -86,8 +78,6 @@ constexpr int RB = R * W;                  // row blocks per panel
 #ifndef SL_GP4_WRITE_SKEW
 #define SL_GP4_WRITE_SKEW 1
 #endif
-constexpr int RUNS = 4;                    // affine runs per wavefront handled by the recurrence
-constexpr int RUNC = SL_P + 2;             // per (wavefront, run): step[SL_P], a^2, Q
 constexpr int KXS2 = CB * 128 + 4;
 constexpr int KXBUF = 8 * KXS2;
 static_assert(R == 4, "256-row panels (tools/audit_gp4.py is told the same number by the build)");
@@ -664,17 +654,17 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
             // exponent of rho is capped (b > 700 implies e_0 = 0 exactly: 0 * finite, not 0 * inf).
             const bool direct = __builtin_popcount(runs) > 4 || (__ballot(wide) & 0xffffull) != 0ull;
             // constants of the first run (the only one for most tiles) in scalar registers
-            double x0[SL_P], dlt[SL_P], a2 = 0.0;
+            double x0[SL_P], run0[RUNC], a2 = 0.0;      // run0: step, a^2, Q like a row of runc
 #pragma unroll
             for (int q = 0; q < SL_P; ++q) {
                 if (q < p) {
                     x0[q] = uniform(cin[(16 * wave) * SL_P + q]);
-                    dlt[q] = uniform(cin[(16 * wave + 1) * SL_P + q] - x0[q]);
-                    a2 = fma(dlt[q], dlt[q], a2);
+                    run0[q] = uniform(cin[(16 * wave + 1) * SL_P + q] - x0[q]);
+                    a2 = fma(run0[q], run0[q], a2);
                 }
             }
-            a2 = uniform(a2);
-            const double qstep = uniform(sl_exp_nonpos(-a2));
+            run0[SL_P] = uniform(a2);
+            run0[SL_P + 1] = uniform(sl_exp_nonpos(-run0[SL_P]));
             // a tile with a kink: the step, |step|^2 and Q of every run once per tile (lane r
             // for run r), not once per training point and chunk
             if (runs != 1u && !direct) {
@@ -725,17 +715,7 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
                         rho = sd.y;
                     } else {
                         load_xv();
-                        double z = 0.0, bj = 0.0;
-#pragma unroll
-                        for (int q = 0; q < SL_P; ++q) {
-                            if (q < p) {
-                                const double dq = xv[q] - x0[q];
-                                z = fma(dq, dq, z);
-                                bj = fma(dq, dlt[q], bj);
-                            }
-                        }
-                        exp_pair(-0.5 * z, fmin(bj - 0.5 * a2, 700.0), e, rho);
-                        e = variance * e;
+                        run_seed(xv, x0, run0, variance, p, e, rho);
                         if (use_seeds && keep) {
                             sl_d2 sd;
                             sd.x = e;
@@ -744,15 +724,7 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
                                                                    ch * (W * 1024) + seed_wave, 0);
                         }
                     }
-                    // slot (c + wswz) & 15 with wswz 0 or 4: two bases, immediate offsets
-                    double* w_lo = kxw + 2 * wswz;               // cells 0..11
-                    double* w_hi = w_lo - 8 * wswz;              // cells 12..15 wrap for wswz = 4
-#pragma unroll
-                    for (int c = 0; c < 16; ++c) {
-                        (c < 12 ? w_lo : w_hi)[2 * c] = e;
-                        e *= rho;
-                        rho *= qstep;
-                    }
+                    store_run16(kxw, wswz, rho, e, run0[SL_P + 1]);      // (rho BEFORE e: see there)
                 } else if (!direct) {              // a few runs: the recurrence restarts at each
                     const bool reuse = use_seeds && ch < first_new;
                     if (!reuse) load_xv();
@@ -772,17 +744,7 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
                             e = sd.x;
                             rho = sd.y;
                         } else {
-                            double z = 0.0, bj = 0.0;
-#pragma unroll
-                            for (int q = 0; q < SL_P; ++q) {
-                                if (q < p) {
-                                    const double dq = xv[q] - at[q];
-                                    z = fma(dq, dq, z);
-                                    bj = fma(dq, rc[q], bj);
-                                }
-                            }
-                            exp_pair(-0.5 * z, fmin(bj - 0.5 * rc[SL_P], 700.0), e, rho);
-                            e = variance * e;
+                            run_seed(xv, at, rc, variance, p, e, rho);
                             if (use_seeds && keep) {
                                 sl_d2 sd;
                                 sd.x = e;
@@ -800,17 +762,7 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
                     }
                 } else {
                     load_xv();
-                    for (int c = 0; c < 16; ++c) {
-                        double z = 0.0;
-#pragma unroll
-                        for (int q = 0; q < SL_P; ++q) {
-                            if (q < p) {
-                                const double dq = xv[q] - cin[(16 * wave + c) * SL_P + q];
-                                z = fma(dq, dq, z);
-                            }
-                        }
-                        kxw[2 * ((c + wswz) & 15)] = variance * sl_exp_nonpos(-0.5 * z);
-                    }
+                    direct_run(kxw, wswz, xv, cin, 16 * wave, variance, p);
                 }
             };
             // Posterior mean k_x . alpha' on the matrix cores as well: for the wavefront's own 16
@@ -824,53 +776,17 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
             // both), mean_run multiplies once the wavefront has written its k_x values - its
             // OWN values (lane = training point, the 16 cells of block `wave`): LDS serves a
             // wavefront's instructions in order, no workgroup barrier is needed in between.
-            struct MeanIn { double a0[8], a1[8]; };
             auto mean_run = [&](int buf, const MeanIn& mi) {
                 const double* kxr = kx_l + buf * KXBUF + wave * 128 + own;
                 sl_d2 kx[8];
-#pragma unroll
-                for (int s2 = 0; s2 < 8; ++s2) kx[s2] = *reinterpret_cast<const sl_d2*>(kxr + s2 * KXS2);
-                // Accumulators in vector registers (the builtin would route them through a0:a1).
-                // A dependent FP64 MFMA must not issue right behind its producer (no interlock:
-                // measured, the second product was lost): four accumulators in rotation keep
-                // three MFMAs between a write and its reuse.
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-                    asm volatile("s_nop 3\n\t"
-                                 "v_mfma_f64_4x4x4_4b_f64 %0, %4, %5, %0\n\t"
-                                 "v_mfma_f64_4x4x4_4b_f64 %1, %6, %7, %1\n\t"
-                                 "v_mfma_f64_4x4x4_4b_f64 %2, %8, %9, %2\n\t"
-                                 "v_mfma_f64_4x4x4_4b_f64 %3, %10, %11, %3\n\t"
-                                 "v_mfma_f64_4x4x4_4b_f64 %0, %12, %13, %0\n\t"
-                                 "v_mfma_f64_4x4x4_4b_f64 %1, %14, %15, %1\n\t"
-                                 "v_mfma_f64_4x4x4_4b_f64 %2, %16, %17, %2\n\t"
-                                 "v_mfma_f64_4x4x4_4b_f64 %3, %18, %19, %3"
-                                 : "+v"(macc[0]), "+v"(macc[1]), "+v"(macc[2]), "+v"(macc[3])
-                                 : "v"(mi.a0[4 * h]), "v"(kx[4 * h].x), "v"(mi.a1[4 * h]), "v"(kx[4 * h].y),
-                                   "v"(mi.a0[4 * h + 1]), "v"(kx[4 * h + 1].x), "v"(mi.a1[4 * h + 1]), "v"(kx[4 * h + 1].y),
-                                   "v"(mi.a0[4 * h + 2]), "v"(kx[4 * h + 2].x), "v"(mi.a1[4 * h + 2]), "v"(kx[4 * h + 2].y),
-                                   "v"(mi.a0[4 * h + 3]), "v"(kx[4 * h + 3].x), "v"(mi.a1[4 * h + 3]), "v"(kx[4 * h + 3].y));
-                // retired before any other reader (a register copy, the final sum)
-                asm volatile("s_nop 15\n\ts_nop 7" : "+v"(macc[0]), "+v"(macc[1]), "+v"(macc[2]), "+v"(macc[3]));
+                load_own_kx<KXS2>(kx, kxr);
+                mean_mfma(kx, mi, macc);
             };
             // chunk `ch` -> LDS buffer `buf`, and its contribution to the posterior mean
             auto produce = [&](int ch, int buf, int first_new, bool keep) {
                 const bool with_mean = ch >= first_new && !(skip & 2);
                 MeanIn mi;
-                if (with_mean) {
-                    // alpha' from L2 through the head's buffer resource: one lane offset, the row
-                    // of the slab in the scalar operand.  Rows dd >= dout of A hold whatever a valid
-                    // column holds: row dd of the product depends on row dd of A only, and the rows
-                    // >= dout of the result are never read.
-                    const int voff = (lk * dout + (low < dout ? low : 0)) * 8;
-#pragma unroll
-                    for (int s2 = 0; s2 < 8; ++s2) {
-                        mi.a0[s2] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(
-                            rs_alpha, voff, (64 * ch + 8 * s2) * dout * 8, 0));
-                        mi.a1[s2] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(
-                            rs_alpha, voff, (64 * ch + 8 * s2 + 4) * dout * 8, 0));
-                    }
-                }
+                if (with_mean) load_alpha(mi, rs_alpha, lk, low, dout, ch);
                 if (!(skip & 1)) generate(ch, buf, first_new, keep);
                 if (with_mean) {
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -903,37 +819,18 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
                 const int64_t idx = blk0 + lcol;
                 const bool valid = lk == 0 && idx < hi;
                 const int cl = 16 * wave + lcol;
-                bool neg_hi = false, open = false;
-                double v_x = 0.0;
+                CellBounds b{false, false, 0.0};
                 if (valid) {
-                    double x[SL_P], u[SL_M], prior[SL_D], mean[SL_D], err0[SL_D], err1[SL_D];
-                    sl_cell_state(M, d, idx, points, x);
-                    sl_policy_any<false>(M, nd, aux.tri, idx, x, u);
-                    sl_append_action(nd, u, x);
-                    sl_rows_dot<SL_D, SL_P>(M.m.dynamics.matrix, d, p, x, prior);
                     double var = variance;
                     if (done > 0) {
                         double sumsq = 0.0;
                         for (int k = 0; k < PSS; ++k) sumsq += part_ss[k * C + cl];
                         var = variance - sumsq;
                     }
-                    const double e = gp.beta * sqrt(var);
-#pragma unroll
-                    for (int k = 0; k < SL_D; ++k) {
-                        if (k < d) {
-                            mean[k] = cell_mean[cl * SL_D + k] + prior[k];
-                            err0[k] = 0.0;
-                            err1[k] = e;
-                        }
-                    }
-                    const SlCellCheck c0 = sl_cell_check<SL_FAST>(M, d, aux, x, mean, err0);
-                    const SlCellCheck c1 = sl_cell_check<SL_FAST>(M, d, aux, x, mean, err1);
-                    neg_hi = c1.negative;
-                    // (a non-finite mean or err_hi leaves the cell, and so the block, undecided)
-                    open = c0.negative != c1.negative || !(fabs(c0.decrease) < INFINITY) ||
-                           !(fabs(c1.decrease) < INFINITY);
-                    v_x = values ? values[idx - lo] : c1.v_x;
+                    b = cell_bounds(M, nd, aux, gp.beta, idx, lo, points, values, cell_mean + cl * SL_D, var);
                 }
+                const bool neg_hi = b.neg_hi, open = b.open;
+                const double v_x = b.v_x;
                 const bool all = last || __ballot(open) == 0ull;
                 if (all) {
                     const unsigned word = (unsigned)(__ballot(neg_hi) & 0xffffull);
@@ -955,8 +852,7 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
                 // in the order and through the accumulators of the interleaved pass: the same bits.
                 for (int ch = 0; ch < nchunks_head; ++ch) produce(ch, ch & 1, 0, false);
                 if (lk < dout)
-                    cell_mean[(16 * wave + 4 * blk + low) * SL_D + hd.col0 + lk] =
-                        (macc[0] + macc[1]) + (macc[2] + macc[3]);
+                    cell_mean[(16 * wave + 4 * blk + low) * SL_D + hd.col0 + lk] = mean_sum(macc);
             }
 #ifdef SL_DIAG
             if (early && stage >= 0 && stage < 4 && tid == 0) atomicAdd(&sl_gp4_stage_count[4 + stage], 1ull);
@@ -1048,8 +944,7 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
             }
             if (decided) break;
             if (!early && lk < dout)
-                cell_mean[(16 * wave + 4 * blk + low) * SL_D + hd.col0 + lk] =
-                    (macc[0] + macc[1]) + (macc[2] + macc[3]);
+                cell_mean[(16 * wave + 4 * blk + low) * SL_D + hd.col0 + lk] = mean_sum(macc);
             __syncthreads();
             if (tid < C) {
                 double sumsq = 0.0;
@@ -1165,7 +1060,7 @@ static int launch4(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, i
     if (blocks > SL_MAX_GRID) blocks = SL_MAX_GRID;
     // sl_gp4_workgroups_configure (tests): few workgroups on a small grid, so that each draws many
     // tiles and its queues fill composite tiles from different source tiles
-    if (sl_gp4_workgroup_cap > 0 && blocks > sl_gp4_workgroup_cap) blocks = sl_gp4_workgroup_cap;
+    if (ctx->gp4_workgroup_cap > 0 && blocks > ctx->gp4_workgroup_cap) blocks = ctx->gp4_workgroup_cap;
     *nblocks = (int)blocks;
     SlAux aux{ctx->d_tri, ctx->d_net};
     const int skip = sl_diag_flags("SL_GP4_SKIP");            // (development builds only: 0 otherwise)
@@ -1187,11 +1082,11 @@ static int launch4(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, i
     // power of two whose list fits GP4_LIST_BUDGET.  A small launch keeps the source pass in the
     // panel kernel: two launches and a memset more per sweep are a tenth of C2's 0.3 ms step.
     constexpr long long GP4_LIST_BUDGET = 520ll << 20;          // 512 MiB of means + 8 MiB of first cells at d = 4
-    const bool split = early && (sl_gp4_segment_tiles > 0 || counter);
+    const bool split = early && (ctx->gp4_segment_tiles > 0 || counter);
     long long seg = 0, nseg = 1;
     if (split) {
         seg = gp4l_segment_tiles(GP4_LIST_BUDGET, DT);
-        if (sl_gp4_segment_tiles > 0) seg = sl_gp4_segment_tiles;
+        if (ctx->gp4_segment_tiles > 0) seg = ctx->gp4_segment_tiles;
         if (seg > ntiles) seg = ntiles;
         nseg = gp4l_segments(ntiles, seg);
     }
@@ -1201,7 +1096,7 @@ static int launch4(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, i
         (early ? rec_bytes + list_cap * (sizeof(long long) + 16 * DT * sizeof(double))
                : (size_t)gp4::RUNS * blocks * seed_chunks * gp4::W * 128 * sizeof(double));
     if (split && list_cap * (sizeof(long long) + 16 * DT * sizeof(double)) > (size_t)GP4_LIST_BUDGET &&
-        sl_gp4_segment_tiles <= 0)
+        ctx->gp4_segment_tiles <= 0)
         return sl_fail(ctx, SL_ERR_INVALID, "k_gp_sweep4: the list of a segment exceeds its scratch budget");
     SL_HIP_CHECK(ctx, sl_grow(ctx, &ctx->d_gp4_seeds, &ctx->gp4_seed_bytes, seed_bytes));
     // SL_GP4_SEEDS=0: every generation from scratch (same k_x bit for bit: the test of that)
@@ -1289,16 +1184,14 @@ SL_GP4_DIM_ENTRY(3)
 #if !defined(SL_GP4_DIM) || SL_GP4_DIM == 4
 SL_GP4_DIM_ENTRY(4)
 
-int sl_gp4_workgroup_cap = 0;
-int sl_gp4_segment_tiles = 0;
 extern "C" int sl_gp4_segment_configure(sl_ctx* ctx, int tiles) {
     if (!ctx) return sl_fail(nullptr, SL_ERR_INVALID, "sl_gp4_segment_configure: NULL context");
-    sl_gp4_segment_tiles = tiles > 0 ? tiles : 0;
+    ctx->gp4_segment_tiles = tiles > 0 ? tiles : 0;
     return SL_OK;
 }
 extern "C" int sl_gp4_workgroups_configure(sl_ctx* ctx, int workgroups) {
     if (!ctx) return sl_fail(nullptr, SL_ERR_INVALID, "sl_gp4_workgroups_configure: NULL context");
-    sl_gp4_workgroup_cap = workgroups > 0 ? workgroups : 0;
+    ctx->gp4_workgroup_cap = workgroups > 0 ? workgroups : 0;
     return SL_OK;
 }
 

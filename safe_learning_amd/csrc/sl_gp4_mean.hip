@@ -18,12 +18,25 @@
 //    the segment's list, position from a device counter (order free).  The panel kernel then
 //    draws its stage-0 composite tiles from that list (sl_gp4_queue.h).
 //
-// The arithmetic of a cell is that of sl_gp4.hip statement for statement - exponential
-// (sl_gp4_gen.h), recurrence, run split, direct path, the MFMA statements of the mean, the
-// rotation of its four accumulators, the final (macc0 + macc1) + (macc2 + macc3), the two
-// sl_cell_check calls: tests/test_gpu_gp4_mean_kernel.py holds the result against SL_GP4_EARLY=0
-// bit for bit.  The statements are COPIES: the plain path's lambdas stay where they are (the
-// register allocation of k_gp_sweep4<.., false> follows the shape of its source).
+// The arithmetic of a block is that of sl_gp4.hip because it is the same source, sl_gp4_gen.h: seed
+// of a run, 16-cell recurrence, direct path, alpha' and k_x fragment loads, the MFMA group of the
+// mean, the final sum, the two-bound decision of a cell.  tests/test_gpu_gp4_mean_kernel.py holds
+// the result against SL_GP4_EARLY=0 bit for bit.
+//
+// Six pieces are still written here AND in sl_gp4.hip, statement for statement, because as header
+// functions they changed a kernel that the contract keeps fixed (gfx950 listings, before -> after;
+// profiles/shared_block_source.md has the commands).  Edit both copies together:
+//  * scaled inputs of a block: k_gp_sweep4<4, 1, false> scratch 224 -> 236 B, 94 -> 113 scratch ops,
+//    another kernel descriptor at d = 2, 3, 4;
+//  * run detection (`runs`, `wide`): k_gp_sweep4<4, 1, false> scratch 224 -> 268 B, 94 -> 123 scratch
+//    ops (d = 2: 176 -> 200 B), another descriptor in every dimension;
+//  * constants of the first run (x0, run0): k_gp_sweep4<.., false> reordered in 212 - 932 lines far
+//    from the piece, at d = 1 lane-spill ops in the MFMA streams 24 -> 28 (another audit line);
+//  * rows of `runc`: k_gp_sweep4<1, 1, true> scratch 156 -> 164 B, 66 -> 75 scratch ops;
+//  * the recurrence of a block with kinks (the loop over c0 .. c1): k_gp_sweep4<1, 1, true> scratch
+//    156 -> 164 B, 66 -> 69 scratch ops, in every argument form tried;
+//  * mask store and key fold of a decided block: k_gp_mean_blocks<4, 1> has 25 scratch ops in the
+//    parent; with cell_bounds alone in the header 21, with the mask store alone 25, with both 26.
 #include "sl_common.h"
 #include "sl_gp4_gen.h"
 #include "sl_gp4_mean.h"
@@ -33,13 +46,12 @@
 
 namespace gp4m {
 
-using gp4::exp_pair;
+using gp4::RUNC;
+using gp4::RUNS;
 using gp4::uniform;
 
 constexpr int W = 4;                       // wavefronts per workgroup, each on its own
 constexpr int WG_PER_CU = 4;
-constexpr int RUNS = 4;                    // affine runs per block handled by the recurrence
-constexpr int RUNC = SL_P + 2;             // per run: step[SL_P], a^2, Q
 // k_x chunk of one wavefront: [slab pair 8][k 4][slot 16][slab of the pair 2] - cell block `wave` of
 // the panel kernel's layout, the slab pairs 4 doubles apart modulo the banks as there
 constexpr int KXS2 = 128 + 4;
@@ -170,17 +182,17 @@ __global__ __launch_bounds__(256, 4) void k_gp_mean_blocks(
             runs = (unsigned)__builtin_amdgcn_readfirstlane((int)runs);
             const bool direct = __builtin_popcount(runs) > 4 || (__ballot(wide) & 0xffffull) != 0ull;
             // constants of the first run (the only one for most blocks) in scalar registers
-            double x0[SL_P], dlt[SL_P], a2 = 0.0;
+            double x0[SL_P], run0[RUNC], a2 = 0.0;      // run0: step, a^2, Q like a row of runc
 #pragma unroll
             for (int q = 0; q < SL_P; ++q) {
                 if (q < p) {
                     x0[q] = uniform(cin[q]);
-                    dlt[q] = uniform(cin[SL_P + q] - x0[q]);
-                    a2 = fma(dlt[q], dlt[q], a2);
+                    run0[q] = uniform(cin[SL_P + q] - x0[q]);
+                    a2 = fma(run0[q], run0[q], a2);
                 }
             }
-            a2 = uniform(a2);
-            const double qstep = uniform(sl_exp_nonpos(-a2));
+            run0[SL_P] = uniform(a2);
+            run0[SL_P + 1] = uniform(sl_exp_nonpos(-run0[SL_P]));
             // a block with a kink: the step, |step|^2 and Q of every run once (lane r for run r)
             if (runs != 1u && !direct) {
                 if (lane < RUNS) {
@@ -218,48 +230,19 @@ __global__ __launch_bounds__(256, 4) void k_gp_mean_blocks(
                     if (q < p)
                         xv[q] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(
                             rs_xs, lane * 8, (q * n_pad + 64 * ch) * 8, 0));
-                if (runs == 1u) {                  // one affine run: e_{c+1} = e_c rho_c, rho_{c+1} = rho_c Q
+                if (runs == 1u) {                  // one affine run
                     double e, rho;
-                    double z = 0.0, bj = 0.0;
-#pragma unroll
-                    for (int q = 0; q < SL_P; ++q) {
-                        if (q < p) {
-                            const double dq = xv[q] - x0[q];
-                            z = fma(dq, dq, z);
-                            bj = fma(dq, dlt[q], bj);
-                        }
-                    }
-                    exp_pair(-0.5 * z, fmin(bj - 0.5 * a2, 700.0), e, rho);
-                    e = variance * e;
-                    // slot (c + wswz) & 15 with wswz 0 or 4: two bases, immediate offsets
-                    double* w_lo = kxw + 2 * wswz;               // cells 0..11
-                    double* w_hi = w_lo - 8 * wswz;              // cells 12..15 wrap for wswz = 4
-#pragma unroll
-                    for (int c = 0; c < 16; ++c) {
-                        (c < 12 ? w_lo : w_hi)[2 * c] = e;
-                        e *= rho;
-                        rho *= qstep;
-                    }
+                    gp4::run_seed(xv, x0, run0, variance, p, e, rho);
+                    gp4::store_run16(kxw, wswz, rho, e, run0[SL_P + 1]);   // (rho BEFORE e: see there)
                 } else if (!direct) {              // a few runs: the recurrence restarts at each
                     unsigned m = runs;
                     for (int r = 0; m; ++r) {
                         const int c0 = __builtin_ctz(m);
                         m &= m - 1;
                         const int c1 = m ? __builtin_ctz(m) : 16;
-                        const double* at = cin + c0 * SL_P;
                         const double* rc = runc + r * RUNC;
                         double e, rho;
-                        double z = 0.0, bj = 0.0;
-#pragma unroll
-                        for (int q = 0; q < SL_P; ++q) {
-                            if (q < p) {
-                                const double dq = xv[q] - at[q];
-                                z = fma(dq, dq, z);
-                                bj = fma(dq, rc[q], bj);
-                            }
-                        }
-                        exp_pair(-0.5 * z, fmin(bj - 0.5 * rc[SL_P], 700.0), e, rho);
-                        e = variance * e;
+                        gp4::run_seed(xv, cin + c0 * SL_P, rc, variance, p, e, rho);
                         const double qr = rc[SL_P + 1];
                         for (int c = c0; c < c1; ++c) {
                             kxw[2 * ((c + wswz) & 15)] = e;
@@ -268,107 +251,39 @@ __global__ __launch_bounds__(256, 4) void k_gp_mean_blocks(
                         }
                     }
                 } else {
-                    for (int c = 0; c < 16; ++c) {
-                        double z = 0.0;
-#pragma unroll
-                        for (int q = 0; q < SL_P; ++q) {
-                            if (q < p) {
-                                const double dq = xv[q] - cin[c * SL_P + q];
-                                z = fma(dq, dq, z);
-                            }
-                        }
-                        kxw[2 * ((c + wswz) & 15)] = variance * sl_exp_nonpos(-0.5 * z);
-                    }
+                    gp4::direct_run(kxw, wswz, xv, cin, 0, variance, p);
                 }
-            };
-            // mean[dd][cell] += sum_j alpha'[j][dd] k_x[j][cell] over the chunk's 64 points: A =
-            // alpha'^T (row dd = lane & 3), B = the k_x values the wavefront has just written.
-            // Lane (k, blk, low) ends up with the mean of output dd = k at cell 4 blk + low.
-            struct MeanIn { double a0[8], a1[8]; };
-            auto mean_run = [&](const MeanIn& mi) {
-                const double* kxr = kx_l + own;
-                sl_d2 kx[8];
-#pragma unroll
-                for (int s2 = 0; s2 < 8; ++s2) kx[s2] = *reinterpret_cast<const sl_d2*>(kxr + s2 * KXS2);
-                // A dependent FP64 MFMA must not issue right behind its producer (no interlock):
-                // four accumulators in rotation keep three MFMAs between a write and its reuse.
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-                    asm volatile("s_nop 3\n\t"
-                                 "v_mfma_f64_4x4x4_4b_f64 %0, %4, %5, %0\n\t"
-                                 "v_mfma_f64_4x4x4_4b_f64 %1, %6, %7, %1\n\t"
-                                 "v_mfma_f64_4x4x4_4b_f64 %2, %8, %9, %2\n\t"
-                                 "v_mfma_f64_4x4x4_4b_f64 %3, %10, %11, %3\n\t"
-                                 "v_mfma_f64_4x4x4_4b_f64 %0, %12, %13, %0\n\t"
-                                 "v_mfma_f64_4x4x4_4b_f64 %1, %14, %15, %1\n\t"
-                                 "v_mfma_f64_4x4x4_4b_f64 %2, %16, %17, %2\n\t"
-                                 "v_mfma_f64_4x4x4_4b_f64 %3, %18, %19, %3"
-                                 : "+v"(macc[0]), "+v"(macc[1]), "+v"(macc[2]), "+v"(macc[3])
-                                 : "v"(mi.a0[4 * h]), "v"(kx[4 * h].x), "v"(mi.a1[4 * h]), "v"(kx[4 * h].y),
-                                   "v"(mi.a0[4 * h + 1]), "v"(kx[4 * h + 1].x), "v"(mi.a1[4 * h + 1]), "v"(kx[4 * h + 1].y),
-                                   "v"(mi.a0[4 * h + 2]), "v"(kx[4 * h + 2].x), "v"(mi.a1[4 * h + 2]), "v"(kx[4 * h + 2].y),
-                                   "v"(mi.a0[4 * h + 3]), "v"(kx[4 * h + 3].x), "v"(mi.a1[4 * h + 3]), "v"(kx[4 * h + 3].y));
-                // retired before any other reader (a register copy, the final sum)
-                asm volatile("s_nop 15\n\ts_nop 7" : "+v"(macc[0]), "+v"(macc[1]), "+v"(macc[2]), "+v"(macc[3]));
             };
             for (int ch = 0; ch < nchunks_head; ++ch) {
                 const bool with_mean = !(skip & 2);
-                MeanIn mi;
-                if (with_mean) {
-                    // alpha' is requested together with the inputs of the generation (one trip to L2)
-                    const int voff = (lk * dout + (low < dout ? low : 0)) * 8;
-#pragma unroll
-                    for (int s2 = 0; s2 < 8; ++s2) {
-                        mi.a0[s2] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(
-                            rs_alpha, voff, (64 * ch + 8 * s2) * dout * 8, 0));
-                        mi.a1[s2] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(
-                            rs_alpha, voff, (64 * ch + 8 * s2 + 4) * dout * 8, 0));
-                    }
-                }
+                gp4::MeanIn mi;
+                // alpha' is requested together with the inputs of the generation (one trip to L2)
+                if (with_mean) gp4::load_alpha(mi, rs_alpha, lk, low, dout, ch);
                 if (!(skip & 1)) generate(ch);
                 if (with_mean) {
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
-                    mean_run(mi);
+                    sl_d2 kx[8];
+                    gp4::load_own_kx<KXS2>(kx, kx_l + own);
+                    gp4::mean_mfma(kx, mi, macc);
                 }
             }
             // the means of the block where the chunk was (its last reads have fed their MFMAs)
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
-            if (lk < dout) cell_mean[(4 * blk + low) * SL_D + hd.col0 + lk] = (macc[0] + macc[1]) + (macc[2] + macc[3]);
+            if (lk < dout) cell_mean[(4 * blk + low) * SL_D + hd.col0 + lk] = gp4::mean_sum(macc);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
 
-            // decide_block(0) of sl_gp4.hip: err = 0 bounds the decrease from below, err = beta
-            // sqrt(variance) from above; a block whose valid cells all agree is finished
+            // the first decision (decide_block(0) of k_gp_sweep4: no panel yet, the whole prior
+            // variance): a block whose valid cells all agree is finished
             const int64_t idx = blk0 + lcol;
             const bool valid = lk == 0 && idx < hi;
-            bool neg_hi = false, open = false;
-            double v_x = 0.0;
-            if (valid) {
-                double x[SL_P], u[SL_M], prior[SL_D], mean[SL_D], err0[SL_D], err1[SL_D];
-                sl_cell_state(M, d, idx, points, x);
-                sl_policy_any<false>(M, nd, aux.tri, idx, x, u);
-                sl_append_action(nd, u, x);
-                sl_rows_dot<SL_D, SL_P>(M.m.dynamics.matrix, d, p, x, prior);
-                const double var = variance;
-                const double e = gp.beta * sqrt(var);
-#pragma unroll
-                for (int k = 0; k < SL_D; ++k) {
-                    if (k < d) {
-                        mean[k] = cell_mean[lcol * SL_D + k] + prior[k];
-                        err0[k] = 0.0;
-                        err1[k] = e;
-                    }
-                }
-                const SlCellCheck c0 = sl_cell_check<SL_FAST>(M, d, aux, x, mean, err0);
-                const SlCellCheck c1 = sl_cell_check<SL_FAST>(M, d, aux, x, mean, err1);
-                neg_hi = c1.negative;
-                // (a non-finite mean or err_hi leaves the cell, and so the block, undecided)
-                open = c0.negative != c1.negative || !(fabs(c0.decrease) < INFINITY) ||
-                       !(fabs(c1.decrease) < INFINITY);
-                v_x = values ? values[idx - lo] : c1.v_x;
-            }
+            gp4::CellBounds b{false, false, 0.0};
+            if (valid)
+                b = gp4::cell_bounds(M, nd, aux, gp.beta, idx, lo, points, values, cell_mean + lcol * SL_D, variance);
+            const bool neg_hi = b.neg_hi, open = b.open;
+            const double v_x = b.v_x;
             if (__ballot(open) == 0ull) {
                 const unsigned word = (unsigned)(__ballot(neg_hi) & 0xffffull);
                 const int64_t b16 = (blk0 - lo) >> 4;
