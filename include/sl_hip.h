@@ -216,11 +216,21 @@ SL_API int  sl_gp_set_head_kernel(sl_ctx* ctx, int head, int n, int p, int dout,
  * when the padded capacity of the head is exhausted (then call sl_gp_set_head again). */
 SL_API int  sl_gp_append_point(sl_ctx* ctx, int head, const double* h_x, const double* h_linv_row,
                         const double* h_alpha_new);
+/* The variance floor of k_gp_sweep4's early decision in use for `head`, read back from the device words
+ * the kernel reads: out[s], s = 0 .. n - 1 (n at most 32), is the constant c_s with  posterior variance of
+ * all points >= c_s x posterior variance of the first 256 s points,  which lets the lower bound of the
+ * decrease use err = beta sqrt(c_s var) instead of err = 0.  sl_gp_set_head certifies the constants on the
+ * host from h_Linv - O(n^3), 1.2 s at 1024 points - for the heads that can use them: RBF, more than 192 and
+ * at most 2048 points, in a context whose early decision is on (sl_gp4_early_configure) and whose
+ * configuration is not forced when the head is uploaded.  0 = no floor: every other head, boundaries at
+ * or behind the last point, any doubt.  sl_gp_append_point sets them all to 0 until the next
+ * sl_gp_set_head. */
+SL_API int  sl_gp_variance_floor(sl_ctx* ctx, int head, double* out, int n);
 SL_API int  sl_gp_configure(sl_ctx* ctx, int nheads, double beta);
 /* k_gp_sweep4 (one shared-kernel RBF head of more than 256 points, closed-form policy, quadratic V,
  * no record output) computes the posterior mean of a 64-cell tile first and stops adding variance
- * panels once bounds of the decrease - err = 0 from below, err = beta sqrt(variance - partial |a|^2)
- * from above - settle the mask bit of every cell: the same bits, fewer flops.  enable = 0 runs every
+ * panels once bounds of the decrease - err = beta sqrt(variance floor) from below (sl_gp_variance_floor;
+ * err = 0 without one), err = beta sqrt(variance - partial |a|^2) from above - settle the mask bit of every cell: the same bits, fewer flops.  enable = 0 runs every
  * panel of every tile (the A/B baseline and the other side of the bit-identity tests); the default
  * is 1.  Takes effect at the next sweep. */
 SL_API int  sl_gp4_early_configure(sl_ctx* ctx, int enable);

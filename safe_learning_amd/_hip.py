@@ -147,6 +147,7 @@ SIGNATURES = {
     "sl_gp_set_head_kernel": (_int, (_vp, _int, _int, _int, _int, _int, c_double_p, c_double_p, c_double_p,
                                      C.POINTER(GpKernel))),
     "sl_gp_append_point": (_int, (_vp, _int, c_double_p, c_double_p, c_double_p)),
+    "sl_gp_variance_floor": (_int, (_vp, _int, c_double_p, _int)),
     "sl_gp_configure": (_int, (_vp, _int, _dbl)),
     "sl_gp4_early_configure": (_int, (_vp, _int)),
     "sl_gp4_workgroups_configure": (_int, (_vp, _int)),
@@ -391,6 +392,15 @@ class Context(object):
             return False
         self.check(rc, "sl_gp_append_point")
         return True
+
+    def gp_variance_floor(self, head, stages):
+        """The variance-floor constants of an uploaded head, one per 256-row panel boundary, read back
+        from the device (``sl_gp_variance_floor``); all zero after ``gp_append_point``.  Raises
+        ``HipEngineError`` like every bound entry point (``_bind``): a head that is not set, more than
+        32 stages."""
+        out = np.zeros(stages, dtype=np.float64)
+        self.lib.sl_gp_variance_floor(self.handle, head, out.ctypes.data_as(c_double_p), stages)
+        return out
 
     def gp_inputs(self, head, n, p):
         """Scaled training inputs of an uploaded head as the kernels read them, ``[p, n]``."""

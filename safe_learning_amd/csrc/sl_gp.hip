@@ -21,6 +21,7 @@
 //  * the decrease check, the 64-lane ballot for the mask and the (V, index) lexmin of the
 //    failing cells run in the same kernel; HBM traffic is 8 B (V) + 1 bit per cell.
 #include "sl_common.h"
+#include "sl_gp_floor.h"
 
 typedef double sl_d4 __attribute__((ext_vector_type(4)));
 typedef double sl_d2 __attribute__((ext_vector_type(2)));
@@ -403,7 +404,8 @@ static int gp_set_head(sl_ctx* ctx, int head, int n, int p, int dout, int col0, 
     const int n_pad = ((n + rp - 1) / rp) * rp;
     const int nslab2 = n_pad / 8;
 
-    std::vector<double> xs((size_t)p * n_pad, 0.0), alphap((size_t)n_pad * dout, 0.0);
+    // (alpha' is followed by the variance floor of the head: see SlGpHeadDev)
+    std::vector<double> xs((size_t)p * n_pad, 0.0), alphap((size_t)n_pad * dout + SL_GP_FLOOR_WORDS, 0.0);
     std::vector<double> mpack((size_t)n_pad * n_pad, 0.0);
     for (int j = 0; j < n; ++j)
         for (int q = 0; q < p; ++q) xs[(size_t)q * n_pad + j] = h_X[(size_t)j * p + q] / h_lengthscales[q];
@@ -414,6 +416,21 @@ static int gp_set_head(sl_ctx* ctx, int head, int n, int p, int dout, int col0, 
             if (ai == 0.0) continue;
             for (int j = 0; j <= i; ++j) alphap[(size_t)j * dout + dd] += h_Linv[(size_t)i * n + j] * ai;
         }
+    }
+    // Variance floor of k_gp_sweep4's early decision: constants of the model and the 256-row panel
+    // boundaries, certified on the host (sl_gp_floor.h) and stored behind alpha'.  The cost is cubic
+    // in n (1.2 s at 1024 points, 130 MB of temporaries at 2048), so only heads that can reach the
+    // early decision pay it: an RBF head padded to that kernel's panels (n_pad a multiple of 256:
+    // more than 192 points), within its stage count and SL_GP_FLOOR_MAX_N, in a context whose
+    // early decision is on and whose configuration is not forced (SL_GP_CFG) at this upload.
+    // Everybody else keeps 0 = err = 0, also if the early decision is switched on later.
+    const int floor_stages = (n + SL_GP_FLOOR_RP - 1) / SL_GP_FLOOR_RP;
+    if (!h_kernel && ctx->gp4_early && ctx->env.gp_cfg < 0 && n_pad % SL_GP_FLOOR_RP == 0 &&
+        floor_stages <= SL_GP_FLOOR_STAGES && n <= SL_GP_FLOOR_MAX_N) {
+        double floor_c[SL_GP_FLOOR_STAGES] = {};
+        gpfloor::variance_floor(h_Linv, n, SL_GP_FLOOR_RP, floor_stages, variance, floor_c);
+        alphap[(size_t)n_pad * dout] = 2.0 * 64.0 * (double)n * 0x1p-53 * variance;   // 2 delta (gp4_early_ok)
+        for (int s = 0; s < floor_stages; ++s) alphap[(size_t)n_pad * dout + 1 + s] = floor_c[s];
     }
     // MFMA A fragments: [row block I][slab pair S2][lane][2]; A[i = lane & 15][k = lane >> 4]
     for (int I = 0; I < n_pad / 16; ++I) {
@@ -550,7 +567,25 @@ extern "C" int sl_gp_append_point(sl_ctx* ctx, int head, const double* h_x, cons
     SL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     hh.n = n + 1;
     dv.n = n + 1;
+    // a new row grows the Schur complements: the old constants are no bounds of the new model
+    SL_HIP_CHECK(ctx, hipMemset(hh.d_alpha + (size_t)hh.n_pad * hh.dout, 0, SL_GP_FLOOR_WORDS * sizeof(double)));
     SL_HIP_CHECK(ctx, hipMemcpy(ctx->d_gp, &ctx->h_gp, sizeof(SlGpDev), hipMemcpyHostToDevice));
+    return SL_OK;
+}
+
+extern "C" int sl_gp_variance_floor(sl_ctx* ctx, int head, double* out, int n) {
+    if (!ctx || !out) return sl_fail(ctx, SL_ERR_INVALID, "sl_gp_variance_floor: NULL argument");
+    if (head < 0 || head >= SL_MAX_GP_HEADS || !ctx->gp_heads[head].set)
+        return sl_fail(ctx, SL_ERR_INVALID, "sl_gp_variance_floor: head %d not set", head);
+    if (n < 0 || n > SL_GP_FLOOR_STAGES)
+        return sl_fail(ctx, SL_ERR_INVALID, "sl_gp_variance_floor: %d constants outside [0,%d]", n, SL_GP_FLOOR_STAGES);
+    // the words the kernel reads, behind alpha' ([0] is 2 delta)
+    const SlGpHeadHost& hh = ctx->gp_heads[head];
+    SL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    SL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    if (n > 0)
+        SL_HIP_CHECK(ctx, hipMemcpy(out, hh.d_alpha + (size_t)hh.n_pad * hh.dout + 1, sizeof(double) * n,
+                                    hipMemcpyDeviceToHost));
     return SL_OK;
 }
 

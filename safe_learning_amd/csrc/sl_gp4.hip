@@ -81,6 +81,8 @@ constexpr int RB = R * W;                  // row blocks per panel
 constexpr int KXS2 = CB * 128 + 4;
 constexpr int KXBUF = 8 * KXS2;
 static_assert(R == 4, "256-row panels (tools/audit_gp4.py is told the same number by the build)");
+static_assert(RP == SL_GP_FLOOR_RP && GP4Q_STAGES == SL_GP_FLOOR_STAGES,
+              "sl_gp_set_head computes the variance floor for these panel boundaries");
 
 // Block mode (EARLY): a pending record of an open 16-cell block in the workgroup's scratch -
 // [0] first cell (int64), [8 ..) 16 x SL_D means, then the four |a|^2 planes x 16 cells - and the
@@ -808,6 +810,9 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
             // from above (a cell that passes with it passes); every operation between |a|^2 and the
             // comparison rounds monotonically, so a bit both bounds agree on is the bit of the full
             // sum.  A 16-cell block whose cells are all decided needs no further panel.
+            // The lower bound tightens too: the variance of the full sum is at least c_s times the
+            // one left after s panels (the variance floor, sl_gp_floor.h / cell_bounds), so a cell
+            // that fails because of its uncertainty fails with err_lo = beta sqrt(c_s var - 2 delta).
             // decide_block: every wavefront for its own 16 cells (lanes 0 .. 15), `done` panels in
             // part_ss.  A block whose valid cells all agree (every decrease finite) is finished: its 16
             // mask bits go into the tile's word with a 2-byte store and the failing key is folded
@@ -827,7 +832,11 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
                         for (int k = 0; k < PSS; ++k) sumsq += part_ss[k * C + cl];
                         var = variance - sumsq;
                     }
-                    b = cell_bounds(M, nd, aux, gp.beta, idx, lo, points, values, cell_mean + cl * SL_D, var);
+                    // the variance floor of the boundary after `done` panels (none after the last)
+                    const double* fw = floor_words(hd);
+                    const double floor_c = last ? 0.0 : fw[1 + done], floor_2d = last ? 0.0 : fw[0];
+                    b = cell_bounds<true>(M, nd, aux, gp.beta, idx, lo, points, values, cell_mean + cl * SL_D, var,
+                                          floor_c, floor_2d);
                 }
                 const bool neg_hi = b.neg_hi, open = b.open;
                 const double v_x = b.v_x;

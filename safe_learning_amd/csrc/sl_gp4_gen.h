@@ -10,7 +10,9 @@
 //   MeanIn, load_alpha       the alpha' fragments of a chunk
 //   load_own_kx              the k_x fragments a wavefront has just written
 //   mean_mfma, mean_sum      the eight-MFMA mean group with its wait states, the final sum
-//   CellBounds, cell_bounds  the two sl_cell_check calls on a cell: lower and upper bound
+//   CellBounds, cell_bounds  the two sl_cell_check calls on a cell: lower bound (with the variance
+//                            floor of the stage) and upper bound
+//   floor_words              where the head's floor constants lie (behind alpha')
 // What differs between the kernels is an argument: where the block's inputs, run constants and
 // chunk lie in LDS, the stride KXS2 of the chunk's slab pairs, the variance left after the panels.
 // Only pieces both kernels use live here (the seed scratch of the plain path does not).  The
@@ -172,14 +174,27 @@ __device__ __forceinline__ double mean_sum(const double (&macc)[4]) {
     return (macc[0] + macc[1]) + (macc[2] + macc[3]);
 }
 
+// the head's variance floor in device memory: [0] = 2 delta, [1 + s] = c_s (SlGpHeadDev::alpha)
+__device__ __forceinline__ const double* floor_words(const SlGpHeadDev& hd) {
+    return hd.alpha + (size_t)hd.n_pad * hd.dout;
+}
+
 // Bounds of the decrease of cell idx with `var` of the prior variance left (the panels so far
-// taken off): err = 0 bounds it from below, err = beta sqrt(var) from above.  mean_row: the
-// cell's SL_D posterior means without the prior.  open: the bounds disagree, or one is not
-// finite (a non-finite mean or err_hi leaves the cell, and so its block, undecided).
+// taken off): err = beta sqrt(var) bounds it from above, and from below err = beta sqrt(var_lo)
+// with the variance floor var_lo = max(0, floor_c var - floor_2d): the variance of the full sum is
+// at least floor_c times the one left after these panels (floor_c = c_s of sl_gp_floor.h for the
+// panel boundary, a constant of the model), and floor_2d = 2 delta allows for the rounding of both
+// sums (fl(V_n) >= V_n - delta >= c (fl(V_m) - delta) - delta, delta = 64 n 2^-53 s^2).  Multiply,
+// subtract, max, sqrt and the product with beta round monotonically like the operations of the
+// upper bound, so a bit both bounds agree on is still the bit of the full sum.  floor_c = floor_2d
+// = 0 is err = 0 (FLOOR = false: the literal, for a caller without the constants).
+// mean_row: the cell's SL_D posterior means without the prior.  open: the bounds disagree, or one
+// is not finite (a non-finite mean or err_hi leaves the cell, and so its block, undecided).
 struct CellBounds { bool neg_hi, open; double v_x; };
+template <bool FLOOR>
 __device__ __forceinline__ CellBounds cell_bounds(const SlDevModel& M, const SlDims& nd, const SlAux& aux, double beta,
                                                   int64_t idx, int64_t lo, const double* points, const double* values,
-                                                  const double* mean_row, double var) {
+                                                  const double* mean_row, double var, double floor_c, double floor_2d) {
     const int d = nd.d, p = nd.p;
     double x[SL_P], u[SL_M], prior[SL_D], mean[SL_D], err0[SL_D], err1[SL_D];
     sl_cell_state(M, d, idx, points, x);
@@ -187,11 +202,12 @@ __device__ __forceinline__ CellBounds cell_bounds(const SlDevModel& M, const SlD
     sl_append_action(nd, u, x);
     sl_rows_dot<SL_D, SL_P>(M.m.dynamics.matrix, d, p, x, prior);
     const double e = beta * sqrt(var);
+    const double e_lo = FLOOR ? beta * sqrt(fmax(floor_c * var - floor_2d, 0.0)) : 0.0;
 #pragma unroll
     for (int k = 0; k < SL_D; ++k) {
         if (k < d) {
             mean[k] = mean_row[k] + prior[k];
-            err0[k] = 0.0;
+            err0[k] = e_lo;
             err1[k] = e;
         }
     }

@@ -280,8 +280,11 @@ __global__ __launch_bounds__(256, 4) void k_gp_mean_blocks(
             const int64_t idx = blk0 + lcol;
             const bool valid = lk == 0 && idx < hi;
             gp4::CellBounds b{false, false, 0.0};
+            // (No variance floor here: c_0, the constant of the whole factor, is 5e-7 on the headline
+            // model, and reading it cost this kernel registers and scratch - profiles/variance_floor.md.)
             if (valid)
-                b = gp4::cell_bounds(M, nd, aux, gp.beta, idx, lo, points, values, cell_mean + lcol * SL_D, variance);
+                b = gp4::cell_bounds<false>(M, nd, aux, gp.beta, idx, lo, points, values, cell_mean + lcol * SL_D, variance,
+                                            0.0, 0.0);
             const bool neg_hi = b.neg_hi, open = b.open;
             const double v_x = b.v_x;
             if (__ballot(open) == 0ull) {

@@ -1024,13 +1024,19 @@ SL_HD double sl_dact(int a, double pre, double post) {
 // ---------------------------------------------------------------------------------------------
 // the model as the kernels see it
 // ---------------------------------------------------------------------------------------------
+#define SL_GP_FLOOR_STAGES 32            // = GP4Q_STAGES (sl_gp4_queue.h): panel boundaries with a constant
+#define SL_GP_FLOOR_WORDS (1 + SL_GP_FLOOR_STAGES)
+#define SL_GP_FLOOR_RP 256               // = gp4::RP (sl_gp4.hip): rows per panel
+#define SL_GP_FLOOR_MAX_N 2048           // the constants cost O(n^3) on the host: larger heads keep 0
 struct SlGpHeadDev {
     int32_t n, n_pad, p, dout, col0, nslab2, reserved0, reserved1;
     double  variance;
     double  inv_ls[SL_P];
     const double* xs;        // [p][n_pad], inputs already divided by the lengthscales
     const double* mpack;     // MFMA A-fragments of Linv, see sl_gp.hip
-    const double* alpha;     // [n_pad][dout]  alpha' = Linv^T alpha
+    const double* alpha;     // [n_pad][dout]  alpha' = Linv^T alpha, then SL_GP_FLOOR_WORDS doubles: the
+                             // variance floor of the early decision (sl_gp_floor.h): [0] = 2 delta, the
+                             // rounding allowance, [1 + s] = c_s for the panel boundary s
     // sum-of-products kernel (sl_gp_set_head_kernel): device copy of the description, or null for
     // the RBF head of sl_gp_set_head.  xs then holds the inputs unscaled and inv_ls is all ones.
     const sl_gp_kernel* kernel;

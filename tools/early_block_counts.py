@@ -7,6 +7,15 @@ granules of 64 / 32 / 16 / 1 cells.  The kernel's granule is the 16-cell block (
 1-cell row the floor.
 
     python tools/early_block_counts.py [--variant informed|tight|survey] [--tiles 3000] [--seed 0]
+                                       [--variance-floor] [--headline-tau]
+
+--variance-floor: the lower bound of a cell before panel s is the decrease at err = beta sqrt(c_s
+(variance - partial |a|^2)) instead of err = 0, with c_s = sigma_n^2 sigma_min(Linv[256 s:, 256 s:])^2
+= sigma_n^2 / lambda_max of the Schur complement of the first 256 s rows (the
+posterior variance of all n points is at least c_s times the one of the first 256 s).  Before
+panel 0 the bound stays err = 0, as in k_gp_mean_blocks.
+--headline-tau: the variant's hyper-parameters on the headline's discretisation constant (the
+"little skipped" line of profiles/blocks_little_skipped.txt).
 
 Panel p of a tile multiplies (p + 1) 4 chunks against its 16 row blocks, the diagonal band a
 triangle: 40 / 104 / 168 / 232 (row block, chunk) products for p = 0 .. 3, 64 more per panel
@@ -31,10 +40,16 @@ def panel_weights(npan):
     return np.array([40 + 64 * p for p in range(npan)], dtype=float)
 
 
-def cell_stages(case, idx):
+def floor_constants(L, noise, npan):
+    """c_s = sigma_n^2 / lambda_max(L[256 s:, 256 s:] L[256 s:, 256 s:]^T) for s = 0 .. npan - 1."""
+    return np.array([noise / np.linalg.svd(L[RP * s:, RP * s:], compute_uv=False)[0] ** 2 for s in range(npan)])
+
+
+def cell_stages(case, idx, floor=False):
     """Per cell of ``idx``: the stage at which the bounds decide it (0 = from the mean alone, s =
     with s panels in |a|^2, npan = only the full sum does), its final mask bit, and whether its
     decrease is clear of the threshold (beyond the 1e-7 relative agreement of engine and oracle).
+    floor: the variance floor c_s (variance - partial |a|^2) in the lower bound instead of 0.
     Returns (stage, final, clear, npan)."""
     import cases
     ol = cases.oracle_lyapunov(case, compute_values=False)
@@ -56,12 +71,15 @@ def cell_stages(case, idx):
     dec = decrease(np.sum(a ** 2, 0))
     final = dec < thr
     clear = np.abs(dec - thr) > 1e-7 * (np.abs(dec) + np.abs(thr)) + 1e-12
-    sure_fail = ~(decrease(var0) < thr)                  # err = 0
+    c = floor_constants(L, case["dynamics"]["noise_variance"], npan) if floor else np.zeros(npan)
+    c[0] = 0.0        # the first decision of a large launch is k_gp_mean_blocks', which keeps err = 0
     stage = np.full(len(idx), npan)
     part = np.zeros_like(var0)
     for s in range(npan):
         if s:
             part = part + np.sum(a[(s - 1) * RP:s * RP] ** 2, 0)
+        sure_fail = ~(decrease(var0 - c[s] * (var0 - part)) < thr)       # err^2 = beta^2 c_s (var0 - part); c = 0: err = 0
+        assert not (sure_fail & final).any()
         done = sure_fail | (decrease(part) < thr)
         stage[(stage == npan) & done] = s
     return stage, final, clear, npan
@@ -91,14 +109,16 @@ def sample_tiles(case, tiles, seed):
     return (first[:, None] + np.arange(64)[None, :]).reshape(-1)
 
 
-def count(variant=None, tiles=3000, seed=0, batch=500):
+def count(variant=None, tiles=3000, seed=0, batch=500, floor=False, headline_tau=False):
     """{granule: (open fractions before each panel, panel work)} over random tiles."""
     from safe_learning_amd.benchmarks import headline_case
     case = headline_case(variant=variant)
+    if headline_tau:
+        case["tau"] = headline_case()["tau"]
     idx = sample_tiles(case, tiles, seed)
     stages = []
     for b in range(0, len(idx), batch * 64):             # (bounded memory: n x cells factors)
-        st, _, _, npan = cell_stages(case, idx[b:b + batch * 64])
+        st, _, _, npan = cell_stages(case, idx[b:b + batch * 64], floor)
         stages.append(st)
     stage = np.concatenate(stages)
     return {g: (open_fractions(granule_stages(stage, g), npan), panel_work(granule_stages(stage, g), npan))
@@ -110,9 +130,13 @@ if __name__ == "__main__":
     ap.add_argument("--variant", default=None)
     ap.add_argument("--tiles", type=int, default=3000)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--variance-floor", action="store_true")
+    ap.add_argument("--headline-tau", action="store_true")
     args = ap.parse_args()
-    result, npan = count(args.variant, args.tiles, args.seed)
-    print("# headline_case(variant=%r), %d random tiles, seed %d, %d panels" % (args.variant, args.tiles, args.seed, npan))
+    result, npan = count(args.variant, args.tiles, args.seed, floor=args.variance_floor, headline_tau=args.headline_tau)
+    print("# headline_case(variant=%r)%s, %d random tiles, seed %d, %d panels, lower bound: %s" % (
+        args.variant, " at the headline tau" if args.headline_tau else "", args.tiles, args.seed, npan,
+        "variance floor" if args.variance_floor else "err = 0"))
     print("# granule (cells) | open before panel 0 .. %d | panel work executed" % (npan - 1))
     for g in GRANULES:
         frac, work = result[g]

@@ -2,7 +2,7 @@
 measures it, ms, fraction of its roof, the counter / A-B files behind the number) and a list of what
 else is in profiles/.  Reads profiles/r06_configs.jsonl (tools/bench_configs.sh), the headline line
 profiles/r06_bench_driver_command.log, profiles/early_bench_headline.jsonl, profiles/blocks_ab_headline.jsonl and
-profiles/meanpass_ab_headline.jsonl, profiles/pmc_traffic.json and
+profiles/meanpass_ab_headline.jsonl, profiles/variance_floor_ab.jsonl, profiles/pmc_traffic.json and
 profiles/pmc_valu.json.
 
     python tools/profiles_index.py"""
@@ -14,7 +14,8 @@ P = os.path.join(ROOT, "profiles")
 
 # kernel -> (source, configuration that measures it, files with the evidence)
 KERNELS = [
-    ("k_gp_mean_blocks + k_gp_sweep4", "csrc/sl_gp4_mean.hip, csrc/sl_gp4.hip", "C4", "meanpass_ab_headline.jsonl (parent / mean kernel, alternating on one box), meanpass_before.md (the source pass of the parent split), "
+    ("k_gp_mean_blocks + k_gp_sweep4", "csrc/sl_gp4_mean.hip, csrc/sl_gp4.hip", "C4", "variance_floor.md (the variance floor in the lower bound: listings, CPU prediction floor_cpu_counts.txt, device stage counts, "
+     "A/B variance_floor_ab.jsonl, kernel trace, upload cost); shared_block_source.md (one source for both kernels' block arithmetic); meanpass_ab_headline.jsonl (parent / mean kernel, alternating on one box), meanpass_before.md (the source pass of the parent split), "
      "meanpass_kernel_stats.md (both kernels, matrix pipe, stage counts, flush cost), meanpass_other_lines.txt; packed 16-cell blocks before it: blocks_ab_headline.jsonl (parent / 16-cell blocks, alternating on one box), blocks_other_lines.txt, blocks_kernel_stats.md, "
      "blocks_stage_counts.txt, blocks_pmc_128.txt, blocks_little_skipped.txt, blocks_cpu_counts.txt (tools/early_block_counts.py); the 64-cell early decision before it: early_ab_headline.jsonl (parent / early / plain, interleaved on one box), early_kernel_stats.md, early_pmc_48.txt, early_pmc_128.txt, "
      "early_stage_counts.txt, early_ab_other_lines.jsonl, early_dump_outputs.txt, early_little_skipped.txt; the plain instantiation (every panel of every tile): r06_kernel_stats.md, r06_pmc_48.txt, r06_pmc_128.txt, r05_pmc_l2_64.txt, pmc_traffic.json; "
@@ -44,6 +45,10 @@ def load_lines(name):
                 line = line.strip()
                 if line.startswith("{"):
                     d = json.loads(line)
+                    if "result" in d:                      # an A/B file: {"line", "side", "run", "result"}
+                        if d["line"] != "headline" or d["side"] != "change":
+                            continue
+                        d = d["result"]
                     out[d["config"].get("name", "C4")] = d
     except OSError:
         pass
@@ -56,6 +61,7 @@ def main():
     lines.update(load_lines("early_bench_headline.jsonl"))      # the headline with the early tile decision
     lines.update(load_lines("blocks_ab_headline.jsonl"))        # ... on packed 16-cell blocks (the last line: this commit)
     lines.update(load_lines("meanpass_ab_headline.jsonl"))      # ... with the mean kernel in front (the last line: this commit)
+    lines.update(load_lines("variance_floor_ab.jsonl"))         # ... with the variance floor in the lower bound
     try:
         valu = json.load(open(os.path.join(P, "pmc_valu.json")))
     except (OSError, ValueError):
@@ -112,6 +118,8 @@ def main():
              "(DESIGN.md 4.1 \"Early tile decision\").",
              "* `meanpass_*`: the mean and the first decision of `k_gp_sweep4`'s block mode in `k_gp_mean_blocks` against the parent "
              "commit, one visit of one box (DESIGN.md 4.1).",
+             "* `variance_floor.md`, `variance_floor_ab.jsonl`, `floor_cpu_counts.txt`: the variance floor in the lower bound of "
+             "`k_gp_sweep4`'s early decision against the parent commit, one visit of one box (DESIGN.md 4.1).",
              "* `r06_shard_balance.md`: the N = 2 / 4 / 8 shards of C4 and C5 timed one by one on one GPU (`tools/shard_balance.py`).",
              "* `r06_parity_report.md`: what the parity claims rest on, what is a definition, what is unpinned.",
              "* `r06_box_variance_ab.txt`: the round-5 library and the tree alternating on ONE box (C3, C4-lin, C4-det): boxes of the pool "
