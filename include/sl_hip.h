@@ -246,6 +246,13 @@ SL_API int  sl_gp4_workgroups_configure(sl_ctx* ctx, int workgroups);
  * default: large launches only, the segment size from the scratch budget.  Belongs to the context,
  * takes effect at its next sweep. */
 SL_API int  sl_gp4_segment_configure(sl_ctx* ctx, int tiles);
+/* Block mode of k_gp_sweep4 decides and queues 8-cell HALVES of the 16-cell blocks: a half the
+ * bounds decide leaves at once, and the variance panels run on slots that hold one whole block or the
+ * low half of one block beside the high half of another.  enable = 0 goes back to whole blocks (A/B
+ * runs and tests; the results are the same bits either way).  sl_last_kernel reports, per launch, the
+ * paired composites and the slots of them that held one half only.  Belongs to the context, takes
+ * effect at its next sweep. */
+SL_API int  sl_gp4_halves_configure(sl_ctx* ctx, int enable);
 
 /* Auxiliary grid #slot with a per-vertex table (Triangulation: functions.py:1002-1032,
  * 1064-1101): slot 0 = value function, slot 1 = policy.  h_simplices [nsimplex][d+1] are the

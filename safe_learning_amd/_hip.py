@@ -152,6 +152,7 @@ SIGNATURES = {
     "sl_gp4_early_configure": (_int, (_vp, _int)),
     "sl_gp4_workgroups_configure": (_int, (_vp, _int)),
     "sl_gp4_segment_configure": (_int, (_vp, _int)),
+    "sl_gp4_halves_configure": (_int, (_vp, _int)),
     "sl_tri_set": (_int, (_vp, _int, C.POINTER(GridDesc), _int, _int32_p, c_double_p, c_double_p, _int, _int,
                           _vp)),
     "sl_tri_set_table": (_int, (_vp, _int, _vp)),
@@ -330,6 +331,10 @@ class Context(object):
         # first, in segments of N source tiles
         if hasattr(self.lib, "sl_gp4_segment_configure"):
             self.lib.sl_gp4_segment_configure(self.handle, int(os.environ.get("SL_GP4_SEGMENT_TILES") or 0))
+        # SL_GP4_HALVES=0 (A/B runs, tests): block mode decides and queues whole 16-cell blocks, not
+        # their 8-cell halves.  Same results bit for bit; last_kernel() names the granule.
+        if os.environ.get("SL_GP4_HALVES") == "0":
+            self.lib.sl_gp4_halves_configure(self.handle, 0)
 
     def close(self):
         if getattr(self, "handle", None):

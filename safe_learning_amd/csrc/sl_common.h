@@ -102,6 +102,7 @@ struct sl_ctx {
     int gp4_workgroup_cap = 0;         // at most this many workgroups per launch (sl_gp4_workgroups_configure)
     int gp4_segment_tiles = 0;         // source tiles per segment; the launch then always runs the mean kernel
                                        // (sl_gp4_segment_configure; off: large launches only, segments from the scratch budget)
+    bool gp4_halves = true;            // block mode decides and queues 8-cell halves (sl_gp4_halves_configure)
     size_t gp4_seed_bytes = 0;
     void* d_records = nullptr;         // GP posterior records of the two-pass network check
     size_t records_bytes = 0;
@@ -115,7 +116,10 @@ struct sl_ctx {
     void* comm = nullptr;              // RCCL communicator (sl_comm.hip), optional
     void* d_comm_records = nullptr;    // [world] gathered sl_sweep_result records
     int comm_rank = 0, comm_world = 1;
-    char last_kernel[160] = "";        // dominant kernel(s) of the last sweep call (sl_last_kernel)
+    char last_kernel[256] = "";        // dominant kernel(s) of the last sweep call (sl_last_kernel)
+    // block mode of k_gp_sweep4: the launch's two device counters (paired composites, lone-half
+    // slots), added to the note when it is read (sl_last_kernel); nullptr: nothing to add
+    const unsigned long long* gp4_pair_counts = nullptr;
     // sl_timing_configure: pairs of HIP events around the launches of an entry point, on the stream
     // they go to (channel 0: sl_lyap_sweep, 1: sl_lyap_finalize_dev, 2: sl_bellman_sweep)
     struct Timing {

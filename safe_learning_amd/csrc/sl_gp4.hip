@@ -40,6 +40,7 @@
 #include "sl_gp4_clobbers.h"
 #include "sl_gp4_gen.h"
 #include "sl_gp4_mean.h"
+#include "sl_gp4_halves.h"
 #include "sl_gp4_queue.h"
 
 #ifdef SL_NO_GP4
@@ -51,6 +52,7 @@ int sl_gp4_sweep_launch(sl_ctx* ctx, const SlDevModel&, const SlSweepArgs&, int*
 }
 extern "C" int sl_gp4_workgroups_configure(sl_ctx*, int) { return SL_OK; }
 extern "C" int sl_gp4_segment_configure(sl_ctx*, int) { return SL_OK; }
+extern "C" int sl_gp4_halves_configure(sl_ctx*, int) { return SL_OK; }
 #else
 
 namespace gp4 {
@@ -88,17 +90,31 @@ static_assert(RP == SL_GP_FLOOR_RP && GP4Q_STAGES == SL_GP_FLOOR_STAGES,
 // [0] first cell (int64), [8 ..) 16 x SL_D means, then the four |a|^2 planes x 16 cells - and the
 // workgroup's control block in LDS (thread 0 keeps the queues, sl_gp4_queue.h).
 constexpr int REC_MEAN = 8, REC_SS = REC_MEAN + 16 * SL_D, REC = REC_SS + W * 16;   // doubles
-struct BlockCtl {
-    Gp4Queues q;
+struct alignas(8) BlockCtl {
+    Gp4HalfQueues q;
     int action;            // panel of the composite tile to run; SOURCE: a source tile; DONE
-    int pos[GP4Q_SLOTS];   // ring positions of the composite's four slots (-1: empty)
-    int open[W];           // wavefront w pushes its block (to stage push_stage)
+    int pos[GP4Q_SLOTS];   // ring positions of the composite's four slots (-1: empty): full records, or
+    int posb[GP4Q_SLOTS];  // (paired) the low halves in pos, the high halves beside them in posb
+    int paired;            // the composite's slots are paired halves (sl_gp4_halves.h)
+    int open[GP4H_RINGS][W];   // wavefront w pushes a record onto this ring (of stage push_stage)
     int push_stage;
     int src_done;          // the source tiles are used up
     int nsrc;              // source tiles drawn (round-robin lists)
     int from_list;         // the composite's slots are records of the segment's list, not ring positions
     unsigned nlist;        // records of that list
+    unsigned npaired, nlone;   // paired composites run, slots of them that held one half only
+    // What wavefront w knows of its slot, kept HERE and read again where it is needed (generation of
+    // a chunk, decision) so that none of it lives in registers across the MFMA streams:
+    int slotw[W][4];       // [0]: SLOT_A | SLOT_B | SLOT_PAIRED; [1], [2]: the run mask of the first / second
+                           // record's block, its `direct` << 16
+    long long blk1[W];     // first cell of the second block
 };
+constexpr int SLOT_A = 1, SLOT_B = 2, SLOT_PAIRED = 4;
+static_assert(SLOT_A == GP4H_LOW && SLOT_B == GP4H_HIGH, "a paired slot's records ARE its live-half code");
+// (paired slots) the scaled inputs of the slot's SECOND block: CINB doubles a row, in the LDS that
+// holds cell_err on the plain path (block mode never forms it)
+constexpr int CINB = SL_D;
+static_assert(4 + 1 <= CINB, "k_gp_sweep4 is instantiated for up to four state dimensions and one action");
 constexpr int ACT_SOURCE = GP4Q_SOURCE, ACT_DONE = GP4Q_DONE;
 
 struct AFrag { sl_d2 v[R]; };
@@ -402,7 +418,7 @@ static __device__ unsigned long long sl_gp4_stage_count[8];
 // EARLY: 16-cell blocks may be decided from bounds of the decrease (see decide_block) and the
 // variance panels run on composite tiles of four blocks still open; its own instantiation, so
 // that the plain path (EARLY = false: records, several heads, switched off) stays the code it was.
-// `seeds` is then the workgroups' record scratch ([workgroup][stage][GP4Q_CAP][REC], seed_chunks
+// `seeds` is then the workgroups' record scratch ([workgroup][stage][GP4H_RECS][REC], seed_chunks
 // = stages) - a queued block regenerates its k_x from the exponentials.
 // `lst` (block mode of large launches: lst.cell != nullptr): the source pass has run in
 // k_gp_mean_blocks (sl_gp4_mean.hip), which decided what the mean decides and listed the blocks it
@@ -441,6 +457,9 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
     int64_t* next_tile = si + W;                                       // the tile the workgroup drew
     uint64_t* tile_decided = reinterpret_cast<uint64_t*>(next_tile + 1);   // (a spare word: the layout is the plain path's)
     BlockCtl* ctl = reinterpret_cast<BlockCtl*>(tile_decided + 1);        // block mode only
+    double* runcb = reinterpret_cast<double*>(ctl + 1);                   // [W][RUNS][RUNC]: second blocks of paired slots
+    double* cinb = cell_err;                       // [C][CINB] their scaled inputs (block mode has no cell_err)
+    static_assert(sizeof(BlockCtl) % 8 == 0 && CINB <= SL_D, "runcb is aligned, cinb fits cell_err");
 
     const SlDims nd = sl_dims<DT, MT>(M);
     const int d = nd.d, p = nd.p;
@@ -488,10 +507,13 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
     // wavefront w from the block's first cell.  Thread 0 chooses (sl_gp4_queue.h); queues, records
     // and the final flush are the workgroup's own, the tile counter stays the only shared object.
     const int nstages = early ? (gp.head[0].n + RP - 1) / RP : 0;
-    double* recs = seeds + (size_t)blockIdx.x * nstages * GP4Q_CAP * REC;
+    double* recs = seeds + (size_t)blockIdx.x * nstages * GP4H_RECS * REC;
     if (early && tid == 0) {
-        gp4q_init(ctl->q);
-        for (int w = 0; w < W; ++w) ctl->open[w] = 0;
+        gp4h_init(ctl->q);
+        for (int r = 0; r < GP4H_RINGS; ++r)
+            for (int w = 0; w < W; ++w) ctl->open[r][w] = 0;
+        ctl->paired = 0;
+        ctl->npaired = ctl->nlone = 0u;
         ctl->push_stage = 0;
         ctl->src_done = 0;
         ctl->nsrc = 0;
@@ -502,17 +524,23 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
         int stage = ACT_SOURCE;                    // block mode: the panel of a composite tile
         if constexpr (early) {
             if (tid == 0) {
-                int n = 0;                         // the blocks the pass before left open are queued
-                for (int w = 0; w < W; ++w) { n += ctl->open[w]; ctl->open[w] = 0; }
-                if (n) gp4q_push(ctl->q, ctl->push_stage, n);
+                for (int r = 0; r < GP4H_RINGS; ++r) {    // what the pass before left open is queued
+                    int n = 0;
+                    for (int w = 0; w < W; ++w) { n += ctl->open[r][w]; ctl->open[r][w] = 0; }
+                    if (n) gp4h_push(ctl->q, ctl->push_stage, r, n);
+                }
                 const int64_t nsource = lst.cell ? (int64_t)gp4l_draws(ctl->nlist) : ntiles;
-                int st = gp4q_schedule(ctl->q, nstages, ctl->src_done, ctl->pos, [&]() {
+                int st = gp4h_schedule(ctl->q, nstages, ctl->src_done, ctl->pos, ctl->posb, ctl->paired, [&]() {
                     const int64_t t = ticket ? (int64_t)atomicAdd(ticket, 1ull)
                                              : (int64_t)blockIdx.x + (int64_t)ctl->nsrc * gridDim.x;
                     ctl->nsrc += 1;
                     if (t < nsource) *next_tile = t;
                     return t < nsource;
                 });
+                if (st >= 0 && ctl->paired) {
+                    ctl->npaired += 1u;
+                    for (int w = 0; w < GP4Q_SLOTS; ++w) ctl->nlone += (ctl->pos[w] >= 0) != (ctl->posb[w] >= 0);
+                }
                 ctl->from_list = 0;
                 if (lst.cell && st == ACT_SOURCE) {    // draw *next_tile of the list: panel 0 on its records
                     for (int w = 0; w < GP4Q_SLOTS; ++w) ctl->pos[w] = (int)gp4l_slot(*next_tile, w, ctl->nlist);
@@ -538,20 +566,39 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
         }
         // block mode: the first cell of this wavefront's block (an empty slot of a partly filled
         // composite generates nothing and writes nothing)
+        // A PAIRED slot holds the low half (cells 0 .. 7) of block blk0 in its columns 0 .. 7 and the
+        // high half (cells 8 .. 15) of another block, blk1, in its columns 8 .. 15; `live` has bit h
+        // set when the slot's half h is a cell range somebody still waits for.  Everywhere else blk1
+        // = blk0 and both halves are live.
         bool have_blk = true;
         int64_t blk0 = tile_base + 16 * wave;
         const double* rec_in = nullptr;
         const double* list_mean = nullptr;             // the block's record in the segment's list: [16][d] means
+        [[maybe_unused]] int64_t blk1 = blk0;
+        [[maybe_unused]] const double* rec_b = nullptr;
+        [[maybe_unused]] bool paired = false, have_a = true, have_b = false;
         if (early && stage >= 0) {
             const int pos = __builtin_amdgcn_readfirstlane(ctl->pos[wave]);
-            have_blk = pos >= 0;
+            paired = __builtin_amdgcn_readfirstlane(ctl->paired) != 0;
+            const int posb = paired ? __builtin_amdgcn_readfirstlane(ctl->posb[wave]) : -1;
+            have_a = pos >= 0;
+            have_b = posb >= 0;
+            have_blk = have_a || have_b;
             const bool listed = __builtin_amdgcn_readfirstlane(ctl->from_list) != 0;
-            rec_in = recs + (size_t)(stage * GP4Q_CAP + (have_blk && !listed ? pos : 0)) * REC;
-            if (listed) list_mean = lst.mean + (size_t)(have_blk ? pos : 0) * 16 * d;
+            const int ring_a = gp4h_base(paired ? GP4H_RING_LOW : GP4H_RING_FULL);
+            rec_in = recs + (size_t)(stage * GP4H_RECS + ring_a + (have_a && !listed ? pos : 0)) * REC;
+            rec_b = recs + (size_t)(stage * GP4H_RECS + gp4h_base(GP4H_RING_HIGH) + (have_b ? posb : 0)) * REC;
+            if (listed) list_mean = lst.mean + (size_t)(have_a ? pos : 0) * 16 * d;
             blk0 = hi - 1;
-            if (have_blk) {
+            if (have_a) {
                 const int64_t b = listed ? (int64_t)lst.cell[pos] : *reinterpret_cast<const int64_t*>(rec_in);
                 blk0 = ((int64_t)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) |
+                       (int64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)b);
+            }
+            blk1 = paired ? hi - 1 : blk0;
+            if (have_b) {
+                const int64_t b = *reinterpret_cast<const int64_t*>(rec_b);
+                blk1 = ((int64_t)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) |
                        (int64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)b);
             }
         }
@@ -581,9 +628,10 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
             __amdgpu_buffer_rsrc_t rs_alpha =
                 __builtin_amdgcn_make_buffer_rsrc((void*)hd.alpha, 0, 0x7fffffff, 0x27000);
             // scaled GP input [x, policy(x)] / lengthscales of the 64 cells (lane = cell of block `wave`)
-            if (lk == 0) {
+            // (a paired slot: the next 16 lanes form the inputs of its second block, through the same code)
+            if (lk == 0 || (early && have_b && lk == 1)) {
                 double xg[SL_P], u[SL_M];
-                int64_t gidx = (early ? blk0 : tile_base + 16 * wave) + lcol;
+                int64_t gidx = (early ? (lk == 1 ? blk1 : blk0) : tile_base + 16 * wave) + lcol;
                 gidx = gidx < hi ? gidx : hi - 1;
                 // (opaque: the decode of the index stays here - hoisted out of the loop over the
                 // heads its results were spilled to scratch at every tile)
@@ -591,20 +639,31 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
                 sl_cell_state(M, d, gidx, points, xg);
                 sl_policy_any<false>(M, nd, aux.tri, gidx, xg, u);
                 sl_append_action(nd, u, xg);
+                if constexpr (early) {
+                    double* row = lk == 1 ? cinb + (16 * wave + lcol) * CINB : cin + (16 * wave + lcol) * SL_P;
+#pragma unroll
+                    for (int q = 0; q < SL_P; ++q)
+                        if (q < CINB || lk == 0) row[q] = (q < p) ? xg[q] * hd.inv_ls[q] : 0.0;
+                } else {
 #pragma unroll
                 for (int q = 0; q < SL_P; ++q)
                     cin[(16 * wave + lcol) * SL_P + q] = (q < p) ? xg[q] * hd.inv_ls[q] : 0.0;
+                }
             }
             if (early && stage >= 0 && have_blk) {
                 // slot `wave` of a composite tile: the block's means and the |a|^2 of the panels
-                // before this one (the plane update then starts from them, from 0 at panel 0)
+                // before this one (the plane update then starts from them, from 0 at panel 0); a
+                // paired slot takes its columns 8 .. 15 from its second record, an absent half zeros
                 if (list_mean) {
                     for (int i = lane; i < 16 * d; i += 64)
                         cell_mean[(16 * wave + i / d) * SL_D + i % d] = list_mean[i];
                 } else {
-                    for (int i = lane; i < 16 * SL_D; i += 64) cell_mean[16 * wave * SL_D + i] = rec_in[REC_MEAN + i];
+                    for (int i = lane; i < 16 * SL_D; i += 64)
+                        cell_mean[16 * wave * SL_D + i] = (paired && i >= 8 * SL_D ? rec_b : rec_in)[REC_MEAN + i];
                 }
-                part_ss[lk * C + 16 * wave + lcol] = stage > 0 ? rec_in[REC_SS + lane] : 0.0;
+                const bool mine = paired ? (lcol < 8 ? have_a : have_b) : true;
+                part_ss[lk * C + 16 * wave + lcol] =
+                    stage > 0 && mine ? (paired && lcol >= 8 ? rec_b : rec_in)[REC_SS + lane] : 0.0;
             }
             __syncthreads();
             // Where the input is affine in the cell index, z_j(c) = |X_j - x(c)|^2 is quadratic in
@@ -614,7 +673,7 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
             // (curved policies, explicit points): one exponential per (point, cell) instead.
             unsigned runs = 1u;
             bool wide = false;
-            {
+            if constexpr (!early) {                 // (block mode: block_runs, below, for both records of a slot)
                 bool bend = false;
                 if (lcol >= 1) {                    // |step|^2 of the scaled input between neighbours
                     double st2 = 0.0;
@@ -669,7 +728,9 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
             run0[SL_P + 1] = uniform(sl_exp_nonpos(-run0[SL_P]));
             // a tile with a kink: the step, |step|^2 and Q of every run once per tile (lane r
             // for run r), not once per training point and chunk
-            if (runs != 1u && !direct) {
+            // (block mode: also of a block that is one run - its generation reads row 0 from here,
+            // the values of run0, and keeps nothing of the block in registers across the MFMA streams)
+            if (!early && runs != 1u && !direct) {
                 if (lane < RUNS) {
                     unsigned m = runs;
                     for (int r = 0; r < lane; ++r) m &= m - 1;
@@ -693,6 +754,27 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
                 }
                 __builtin_amdgcn_wave_barrier();
             }
+            // Block mode: the same for the records of the slot (sl_gp4_gen.h has the statements once
+            // more), through one piece of code; the run constants go to LDS also for a block that is one
+            // run, the run masks into the slot's words.
+            if constexpr (early) {
+#pragma nounroll
+                for (int sub = 0; sub < 2; ++sub) {
+                    if (!(sub ? have_b : have_a)) continue;
+                    unsigned runs_h;
+                    bool direct_h;
+                    block_runs(sub ? cinb + 16 * wave * CINB : cin + 16 * wave * SL_P, sub ? CINB : SL_P,
+                               (sub ? runcb : runc) + wave * RUNS * RUNC, p, lane, runs_h, direct_h);
+                    if (lane == 0) ctl->slotw[wave][1 + sub] = (int)runs_h | (direct_h ? 1 << 16 : 0);
+                }
+                if (lane == 0) {                   // (a source tile: one whole block per wavefront)
+                    ctl->slotw[wave][0] = (have_a ? SLOT_A : 0) | (have_b ? SLOT_B : 0) | (paired ? SLOT_PAIRED : 0);
+                    ctl->blk1[wave] = blk1;
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+            }
+            auto slot_word = [&](int k) -> int { return __builtin_amdgcn_readfirstlane(ctl->slotw[wave][k]); };
             double macc[4] = {0.0, 0.0, 0.0, 0.0};   // posterior-mean accumulators (see mean_pass)
 
             // k_x chunk `ch` -> LDS buffer `buf` (lane = training point 64 ch + lane)
@@ -767,6 +849,37 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
                     direct_run(kxw, wswz, xv, cin, 16 * wave, variance, p);
                 }
             };
+            // Block mode: the generation of record `sub` of the slot (0: the whole block, or the low half
+            // of a paired slot; 1: the high half of its second block) - always the generation of the
+            // record's WHOLE block from that block's first cell, of which the columns [c_lo, c_hi) are
+            // stored.  Inputs, run constants and run mask come from LDS (sw: the slot's two words).
+            [[maybe_unused]] auto generate_half = [&](int ch, int buf, int sub, int sw0) {
+                const int rw = slot_word(1 + sub);
+                const unsigned runs_h = (unsigned)rw & 0xffffu;
+                const bool direct_h = (rw >> 16) & 1;
+                const int cs = sub ? CINB : SL_P;
+                const double* cw = sub ? cinb + 16 * wave * CINB : cin + 16 * wave * SL_P;
+                const double* rc = (sub ? runcb : runc) + wave * RUNS * RUNC;
+                const int c_lo = sub ? 8 : 0, c_hi = !sub && (sw0 & SLOT_PAIRED) ? 8 : 16;
+                double* kxw = kx_l + buf * KXBUF + wbase;
+                double xv[SL_P];
+#pragma unroll
+                for (int q = 0; q < SL_P; ++q)
+                    if (q < p)
+                        xv[q] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(
+                            rs_xs, lane * 8, (q * n_pad + 64 * ch) * 8, 0));
+                if (runs_h == 1u) {
+                    double e, rho;
+                    run_seed(xv, cw, rc, variance, p, e, rho);
+                    if (c_lo) store_run16<8, 16>(kxw, wswz, rho, e, rc[SL_P + 1]);
+                    else if (c_hi == 8) store_run16<0, 8>(kxw, wswz, rho, e, rc[SL_P + 1]);
+                    else store_run16(kxw, wswz, rho, e, rc[SL_P + 1]);
+                } else if (!direct_h) {
+                    store_runs_window(kxw, wswz, xv, cw, cs, rc, runs_h, variance, p, c_lo, c_hi);
+                } else {
+                    direct_run_window(kxw, wswz, xv, cw, cs, variance, p, c_lo, c_hi);
+                }
+            };
             // Posterior mean k_x . alpha' on the matrix cores as well: for the wavefront's own 16
             // cells, mean[dd][cell] = sum_j alpha'[j][dd] k_x[j][cell] is a 4 x 16 x 64 product per
             // chunk - A = alpha'^T (row dd = lane & 3, the same for the four blocks), B = the
@@ -789,7 +902,15 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
                 const bool with_mean = ch >= first_new && !(skip & 2);
                 MeanIn mi;
                 if (with_mean) load_alpha(mi, rs_alpha, lk, low, dout, ch);
-                if (!(skip & 1)) generate(ch, buf, first_new, keep);
+                if (!(skip & 1)) {
+                    if constexpr (early) {
+                        const int sw0 = slot_word(0);
+#pragma nounroll
+                        for (int sub = 0; sub < 2; ++sub)
+                            if (sw0 & (SLOT_A << sub)) generate_half(ch, buf, sub, sw0);
+                    } else
+                    generate(ch, buf, first_new, keep);
+                }
                 if (with_mean) {
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
@@ -819,10 +940,18 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
             // with the block's 16 initial-set bits; cells >= hi write zeros.  After the last panel
             // the upper bound IS the decrease of the full sum (the arithmetic of the plain
             // epilogue: sum of the planes k = 0 .. 3, variance - sum, beta sqrt, sl_cell_check).
-            auto decide_block = [&](int done) -> bool {
+            // Two verdicts, one per HALF of eight cells (lst.halves; without it one per block): a half
+            // whose valid cells all agree writes its 8 mask bits with a 1-byte store and folds its key
+            // with its 8 initial-set bits, whatever its sibling does - a cell's bit never depended on
+            // its neighbours.  Returns the live-half code of what stays open (0: nothing).  In a paired
+            // slot the halves belong to two blocks (blk0, blk1) and only the live ones are looked at.
+            auto decide_block = [&](int done, int sw, int64_t blk1) -> int {
+                const int live = sw & SLOT_PAIRED ? sw & (SLOT_A | SLOT_B) : (sw & SLOT_A ? GP4H_BOTH : 0);
                 const bool last = done == npanels;
-                const int64_t idx = blk0 + lcol;
-                const bool valid = lk == 0 && idx < hi;
+                const int half = lcol >> 3;
+                const int64_t blkh = half ? blk1 : blk0;
+                const int64_t idx = blkh + lcol;
+                const bool valid = lk == 0 && idx < hi && ((live >> half) & 1);
                 const int cl = 16 * wave + lcol;
                 CellBounds b{false, false, 0.0};
                 if (valid) {
@@ -840,20 +969,26 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
                 }
                 const bool neg_hi = b.neg_hi, open = b.open;
                 const double v_x = b.v_x;
-                const bool all = last || __ballot(open) == 0ull;
-                if (all) {
+                const unsigned openw = (unsigned)(__ballot(open) & 0xffffull);
+                int still = last ? 0 : ((openw & 0xffu) ? GP4H_LOW : 0) | ((openw & 0xff00u) ? GP4H_HIGH : 0);
+                if (!lst.halves && still) still = GP4H_BOTH;
+                still &= live;
+                const int decided = live & ~still;
+                if (decided) {
                     const unsigned word = (unsigned)(__ballot(neg_hi) & 0xffffull);
-                    const int64_t b16 = (blk0 - lo) >> 4;
+                    const bool mine = lk == 0 && ((decided >> half) & 1);
+                    const int64_t b8 = ((blkh - lo) >> 3) + half;
                     unsigned init = 0u;
-                    if (init_bits) init = reinterpret_cast<const unsigned short*>(init_bits)[b16];
-                    if (lane == 0) reinterpret_cast<unsigned short*>(neg_bits)[b16] = (unsigned short)word;
-                    const bool okc = neg_hi || ((init >> lcol) & 1u);
-                    if (valid && !okc) sl_key_min(best_v, best_i, sl_vbits(v_x), idx);
+                    if (init_bits && mine) init = reinterpret_cast<const unsigned char*>(init_bits)[b8];
+                    if (mine && (lcol & 7) == 0)
+                        reinterpret_cast<unsigned char*>(neg_bits)[b8] = (unsigned char)(word >> (8 * half));
+                    const bool okc = neg_hi || ((init >> (lcol & 7)) & 1u);
+                    if (valid && mine && !okc) sl_key_min(best_v, best_i, sl_vbits(v_x), idx);
 #ifdef SL_DIAG
-                    if (lane == 0 && !last && done < 4) atomicAdd(&sl_gp4_stage_count[done], 1ull);
+                    if (lane == 0 && !last && done < 4 && !still) atomicAdd(&sl_gp4_stage_count[done], 1ull);
 #endif
                 }
-                return all;
+                return still;
             };
             if (early && stage == ACT_SOURCE) {
                 // The mean first: every chunk once, without the factor (a wavefront's mean_run reads
@@ -935,15 +1070,38 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
                 // the top of the next pass, when every wavefront has asked for its position).
                 __syncthreads();                   // part_ss of every wavefront
                 const int done = stage + 1;
-                bool open_blk = false;
-                if (have_blk) open_blk = !decide_block(done);
-                if (open_blk && lane == 0) ctl->open[wave] = 1;
+                // What stays open: a whole block (full ring), or a low half of blk0 and / or a high
+                // half of blk1 (the half rings) - a record names its block's first cell and keeps all
+                // 16 columns of means and planes, of which the ring it sits in says which are live.
+                int still = 0;
+                const int sw = slot_word(0);
+                const bool paired = (sw & SLOT_PAIRED) != 0;
+                int64_t blk1 = blk0;
+                if (paired) {
+                    const int64_t b = ctl->blk1[wave];
+                    blk1 = ((int64_t)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) |
+                           (int64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)b);
+                }
+                if (have_blk) still = decide_block(done, sw, blk1);
+                const bool whole = !paired && still == GP4H_BOTH;
+                if (still && lane == 0) {
+                    if (whole) ctl->open[GP4H_RING_FULL][wave] = 1;
+                    else {
+                        if (still & GP4H_LOW) ctl->open[GP4H_RING_LOW][wave] = 1;
+                        if (still & GP4H_HIGH) ctl->open[GP4H_RING_HIGH][wave] = 1;
+                    }
+                }
                 __syncthreads();
-                if (open_blk) {
+#pragma nounroll
+                for (int ring = 0; ring < GP4H_RINGS; ++ring) {
+                    const bool push = ring == GP4H_RING_FULL ? whole
+                                                             : !whole && (still & (ring == GP4H_RING_LOW ? GP4H_LOW : GP4H_HIGH));
+                    if (!push) continue;
                     int rank = 0;
-                    for (int w = 0; w < wave; ++w) rank += ctl->open[w];
-                    double* rec_out = recs + (size_t)(done * GP4Q_CAP + gp4q_push_pos(ctl->q, done, rank)) * REC;
-                    if (lane == 0) *reinterpret_cast<int64_t*>(rec_out) = blk0;
+                    for (int w = 0; w < wave; ++w) rank += ctl->open[ring][w];
+                    double* rec_out = recs + (size_t)(done * GP4H_RECS + gp4h_base(ring) +
+                                                      gp4h_push_pos(ctl->q, done, ring, rank)) * REC;
+                    if (lane == 0) *reinterpret_cast<int64_t*>(rec_out) = ring == GP4H_RING_HIGH ? blk1 : blk0;
                     for (int i = lane; i < 16 * SL_D; i += 64) rec_out[REC_MEAN + i] = cell_mean[16 * wave * SL_D + i];
                     if (done > 0) rec_out[REC_SS + lane] = part_ss[lk * C + 16 * wave + lcol];
                 }
@@ -1002,6 +1160,11 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
     sl_block_reduce_key<true>(best_v, best_i, sv, si);
     if (tid == 0) {
         if (early && lst.fold) sl_key_min(best_v, best_i, partials[blockIdx.x].vbits, partials[blockIdx.x].index);
+        if constexpr (early) {                     // the launch's counts: two words of the scratch's head
+            unsigned long long* counts = reinterpret_cast<unsigned long long*>(seeds) - 4;
+            if (ctl->npaired) atomicAdd(counts, (unsigned long long)ctl->npaired);
+            if (ctl->nlone) atomicAdd(counts + 1, (unsigned long long)ctl->nlone);
+        }
         partials[blockIdx.x].vbits = best_v;
         partials[blockIdx.x].index = best_i;
     }
@@ -1013,7 +1176,8 @@ __global__ __launch_bounds__(256, 2) void k_gp_sweep4(
 static size_t gp4_fixed_lds() {
     return sizeof(double) * (2 * gp4::KXBUF + gp4::W * gp4::C +
                              2 * gp4::C * SL_D + gp4::C * SL_P + gp4::W * gp4::RUNS * gp4::RUNC) +
-           (2 * gp4::W + 4) * sizeof(uint64_t) + sizeof(gp4::BlockCtl);
+           (2 * gp4::W + 4) * sizeof(uint64_t) + sizeof(gp4::BlockCtl) +
+           sizeof(double) * gp4::W * gp4::RUNS * gp4::RUNC;       // runcb
 }
 
 // May blocks be decided from bounds of the decrease (the kernel's decide_block)?  Conditions, not
@@ -1058,7 +1222,7 @@ static int launch4(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, i
     }
     const size_t lds = gp4_fixed_lds();                       // two workgroups per CU: < 80 KB each
     static_assert(sizeof(double) * (2 * gp4::KXBUF + gp4::W * gp4::C + 2 * gp4::C * SL_D + gp4::C * SL_P +
-                                    gp4::W * gp4::RUNS * gp4::RUNC) + (2 * gp4::W + 4) * sizeof(uint64_t) +
+                                    2 * gp4::W * gp4::RUNS * gp4::RUNC) + (2 * gp4::W + 4) * sizeof(uint64_t) +
                           sizeof(gp4::BlockCtl)
                       <= 80 * 1024, "two workgroups of k_gp_sweep4 per CU");
     // (block mode queues one stage per panel: larger training sets than GP4Q_STAGES panels stay plain)
@@ -1080,8 +1244,10 @@ static int launch4(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, i
         seed_chunks = c > seed_chunks ? c : seed_chunks;
     }
     const size_t head_bytes = 64;       // the tile counter; block mode: [1] tiles the mean kernel drew, [2] its list length
-    // block mode: the same scratch holds the pending records instead, [workgroup][stage][GP4Q_CAP][REC]
-    // (1344 B a record, 10.5 KiB per stage and workgroup: 42 KiB at 1024 points, 21 MiB for 512 workgroups)
+    // block mode: the same scratch holds the pending records instead, [workgroup][stage][GP4H_RECS][REC]
+    // (1344 B a record, 42 KiB per stage and workgroup - a ring of full records and two of halves -
+    // 168 KiB at 1024 points, 84 MiB for 512 workgroups); head words [4], [5]: the launch's counts of
+    // paired composites and lone-half slots
     const int stages = early ? (ctx->gp_heads[0].n + gp4::RP - 1) / gp4::RP : 0;
     const bool counter = ntiles >= 4 * blocks;
     // Block mode of a large launch (the condition of the tile counter; sl_gp4_segment_configure forces
@@ -1100,7 +1266,7 @@ static int launch4(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, i
         nseg = gp4l_segments(ntiles, seg);
     }
     const size_t list_cap = (size_t)GP4Q_SLOTS * (size_t)seg;
-    const size_t rec_bytes = early ? (size_t)blocks * stages * GP4Q_CAP * gp4::REC * sizeof(double) : 0;
+    const size_t rec_bytes = early ? (size_t)blocks * stages * GP4H_RECS * gp4::REC * sizeof(double) : 0;
     const size_t seed_bytes = head_bytes +
         (early ? rec_bytes + list_cap * (sizeof(long long) + 16 * DT * sizeof(double))
                : (size_t)gp4::RUNS * blocks * seed_chunks * gp4::W * 128 * sizeof(double));
@@ -1111,14 +1277,20 @@ static int launch4(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, i
     // SL_GP4_SEEDS=0: every generation from scratch (same k_x bit for bit: the test of that)
     double* seeds = (ctx->env.gp4_seeds == 0 && !early) ? nullptr : ctx->d_gp4_seeds + head_bytes / sizeof(double);
     unsigned long long* ticket = reinterpret_cast<unsigned long long*>(ctx->d_gp4_seeds);
+    unsigned long long* const head = ticket;
+    // Halves only where a workgroup meets enough blocks to pair them: the launches that draw from the
+    // mean kernel's lists.  A small launch hands a workgroup one to three source tiles; its halves
+    // would mostly run alone, in more partly filled composites than its blocks (C2: 0.309 -> 0.399 ms).
+    const int halves = ctx->gp4_halves && split ? 1 : 0;
+    if (early) SL_HIP_CHECK(ctx, hipMemsetAsync(head, 0, head_bytes, ctx->stream));     // counters and counts
     if (!split) {
-        if (counter) SL_HIP_CHECK(ctx, hipMemsetAsync(ticket, 0, head_bytes, ctx->stream));
-        else ticket = nullptr;
+        if (!counter) ticket = nullptr;
+        else if (!early) SL_HIP_CHECK(ctx, hipMemsetAsync(ticket, 0, head_bytes, ctx->stream));
         const int rc = sl_with_dim<1, 0>(early, [&](auto e) {
             SL_HIP_CHECK(ctx, sl_launch_lds(k_gp_sweep4<DT, MT, e != 0>, dim3((unsigned)blocks), dim3(gp4::W * 64), lds,
                                             ctx->stream, model, ctx->h_gp, aux, lo, hi, ntiles, a.init_bits, a.values,
                                             a.neg_bits, ctx->d_partials, a.dbg, a.points, skip, seeds, seed_chunks,
-                                            ticket, Gp4ListArgs{nullptr, nullptr, nullptr, 0}));
+                                            ticket, Gp4ListArgs{nullptr, nullptr, nullptr, 0, halves}));
             return SL_OK;
         });
         if (rc) return rc;
@@ -1133,7 +1305,7 @@ static int launch4(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, i
             const long long t0 = gp4l_segment_first(seg, k), nt = gp4l_segment_count(ntiles, seg, k);
             if ((size_t)GP4Q_SLOTS * (size_t)nt > list_cap)
                 return sl_fail(ctx, SL_ERR_INVALID, "k_gp_sweep4: a segment larger than its list");
-            SL_HIP_CHECK(ctx, hipMemsetAsync(ticket, 0, head_bytes, ctx->stream));
+            SL_HIP_CHECK(ctx, hipMemsetAsync(ticket, 0, head_bytes / 2, ctx->stream));   // (the counts stay)
             const Gp4MeanLaunch ml{mean_wg, t0, t0 + nt, ctx->d_partials + blocks, k > 0, ticket + 1, list_count,
                                    list_cell, list_mean, (unsigned)list_cap};
             const int rc = sl_gp4_mean_launch_dim<DT>(ctx, model, a, ml);
@@ -1142,7 +1314,7 @@ static int launch4(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, i
             SL_HIP_CHECK(ctx, sl_launch_lds(k_gp_sweep4<DT, MT, true>, dim3((unsigned)blocks), dim3(gp4::W * 64), lds,
                                             ctx->stream, model, ctx->h_gp, aux, lo, hi, ntiles, a.init_bits, a.values,
                                             a.neg_bits, ctx->d_partials, a.dbg, a.points, skip, seeds, seed_chunks,
-                                            ticket, Gp4ListArgs{list_cell, list_mean, list_count, k > 0}));
+                                            ticket, Gp4ListArgs{list_cell, list_mean, list_count, k > 0, halves}));
         }
         *nblocks = (int)blocks + 4 * mean_wg;
     }
@@ -1161,10 +1333,13 @@ static int launch4(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, i
 #endif
     if (split)
         sl_note_kernel(ctx, false, "k_gp_sweep4<d=%d, m=%d> (%d-row panels, %d workgroup(s) per CU, early decision, 16-cell "
-                                   "blocks) after k_gp_mean_blocks, %lld segment(s)", DT, MT, gp4::RP, 2, nseg);
+                                   "blocks%s) after k_gp_mean_blocks, %lld segment(s)", DT, MT, gp4::RP, 2,
+                       halves ? " in 8-cell halves" : "", nseg);
     else
-    sl_note_kernel(ctx, false, "k_gp_sweep4<d=%d, m=%d> (%d-row panels, %d workgroup(s) per CU%s)",
-                   DT, MT, gp4::RP, 2, early ? ", early decision, 16-cell blocks" : "");
+    sl_note_kernel(ctx, false, "k_gp_sweep4<d=%d, m=%d> (%d-row panels, %d workgroup(s) per CU%s%s)",
+                   DT, MT, gp4::RP, 2, early ? ", early decision, 16-cell blocks" : "",
+                   early && halves ? " in 8-cell halves" : "");
+    if (early) ctx->gp4_pair_counts = head + 4;        // read when the note is (sl_last_kernel)
     return SL_OK;
 }
 
@@ -1196,6 +1371,11 @@ SL_GP4_DIM_ENTRY(4)
 extern "C" int sl_gp4_segment_configure(sl_ctx* ctx, int tiles) {
     if (!ctx) return sl_fail(nullptr, SL_ERR_INVALID, "sl_gp4_segment_configure: NULL context");
     ctx->gp4_segment_tiles = tiles > 0 ? tiles : 0;
+    return SL_OK;
+}
+extern "C" int sl_gp4_halves_configure(sl_ctx* ctx, int enable) {
+    if (!ctx) return sl_fail(nullptr, SL_ERR_INVALID, "sl_gp4_halves_configure: NULL context");
+    ctx->gp4_halves = enable != 0;
     return SL_OK;
 }
 extern "C" int sl_gp4_workgroups_configure(sl_ctx* ctx, int workgroups) {

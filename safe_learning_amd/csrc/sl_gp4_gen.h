@@ -93,12 +93,16 @@ __device__ __forceinline__ void run_seed(const double (&xv)[SL_P], const double*
 // MIND THE ORDER: rho comes BEFORE e here, unlike run_seed's outputs, and all three are doubles - a
 // swapped call compiles.  (The compiler orders the operands of the products after the arguments;
 // with e in front every product of the plain kernel's recurrence comes out commuted, 26 lines for 2.)
+// The column window [C0, C1) (a half-record of the block mode: 0 .. 8 or 8 .. 16) selects the cells
+// that are STORED; the recurrence itself always starts at cell 0 of the block, so a stored value is
+// the bits the whole block's generation gives it.
+template <int C0 = 0, int C1 = 16>
 __device__ __forceinline__ void store_run16(double* kxw, int wswz, double rho, double e, double q) {
     double* w_lo = kxw + 2 * wswz;               // cells 0..11
     double* w_hi = w_lo - 8 * wswz;              // cells 12..15 wrap for wswz = 4
 #pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        (c < 12 ? w_lo : w_hi)[2 * c] = e;
+    for (int c = 0; c < C1; ++c) {
+        if (c >= C0) (c < 12 ? w_lo : w_hi)[2 * c] = e;
         e *= rho;
         rho *= q;
     }
@@ -117,6 +121,115 @@ __device__ __forceinline__ void direct_run(double* kxw, int wswz, const double (
             }
         }
         kxw[2 * ((c + wswz) & 15)] = variance * sl_exp_nonpos(-0.5 * z);
+    }
+}
+// the same for the cells [c_lo, c_hi) of a block whose 16 input rows lie at cw, cs doubles a row
+// (every cell on its own: a window changes no stored value)
+__device__ __forceinline__ void direct_run_window(double* kxw, int wswz, const double (&xv)[SL_P], const double* cw,
+                                                  int cs, double variance, int p, int c_lo, int c_hi) {
+    for (int c = c_lo; c < c_hi; ++c) {
+        double z = 0.0;
+#pragma unroll
+        for (int q = 0; q < SL_P; ++q) {
+            if (q < p) {
+                const double dq = xv[q] - cw[c * cs + q];
+                z = fma(dq, dq, z);
+            }
+        }
+        kxw[2 * ((c + wswz) & 15)] = variance * sl_exp_nonpos(-0.5 * z);
+    }
+}
+// The recurrence of a block with a few runs, restarted at each (`runs`: bit c = cell c starts a
+// run; rcw: the rows of run constants, cw: the block's 16 input rows of cs doubles); the cells
+// [c_lo, c_hi) are stored.  The statements of k_gp_sweep4's own loop (sl_gp4.hip, generate).
+__device__ __forceinline__ void store_runs_window(double* kxw, int wswz, const double (&xv)[SL_P], const double* cw,
+                                                  int cs, const double* rcw, unsigned runs, double variance, int p,
+                                                  int c_lo, int c_hi) {
+    unsigned m = runs;
+    for (int r = 0; m; ++r) {
+        const int c0 = __builtin_ctz(m);
+        m &= m - 1;
+        const int c1 = m ? __builtin_ctz(m) : 16;
+        if (c0 >= c_hi) break;
+        if (c1 <= c_lo) continue;
+        const double* rc = rcw + r * RUNC;
+        double e, rho;
+        run_seed(xv, cw + c0 * cs, rc, variance, p, e, rho);
+        const double qr = rc[SL_P + 1];
+        const int cend = c1 < c_hi ? c1 : c_hi;
+        for (int c = c0; c < cend; ++c) {
+            if (c >= c_lo) kxw[2 * ((c + wswz) & 15)] = e;
+            e *= rho;
+            rho *= qr;
+        }
+    }
+}
+
+// Run detection and run constants of a block whose 16 input rows lie at cw (cs doubles a row): the
+// statements the plain path of k_gp_sweep4 and k_gp_mean_blocks apply to their own block (see there
+// for the reasoning), for the records of a block-mode slot.  runs: bit c = cell c starts an affine run; direct: one
+// exponential per (point, cell); rcw: [RUNS][RUNC] constants of every run - also of a block that is
+// one run: its row 0 holds the values the first record keeps in scalar registers (the same
+// subtraction, the same sum of squares with zeros behind p, the same exponential), read back from LDS
+// so that nothing of the second record lives in registers across the MFMA streams.
+__device__ __forceinline__ void block_runs(const double* cw, int cs, double* rcw, int p, int lane, unsigned& runs,
+                                           bool& direct) {
+    const int lcol = lane & 15;
+    runs = 1u;
+    bool wide = false, bend = false;
+    if (lcol >= 1) {
+        double st2 = 0.0;
+#pragma unroll
+        for (int q = 0; q < SL_P; ++q) {
+            if (q < p) {
+                const double st = cw[lcol * cs + q] - cw[(lcol - 1) * cs + q];
+                st2 = fma(st, st, st2);
+            }
+        }
+        wide = !(st2 <= 1.0);
+    }
+    if (lcol >= 2) {
+#pragma unroll
+        for (int q = 0; q < SL_P; ++q) {
+            if (q < p) {
+                const double c0 = cw[lcol * cs + q];
+                const double c1 = cw[(lcol - 1) * cs + q];
+                const double c2 = cw[(lcol - 2) * cs + q];
+                bend = bend || fabs((c0 - c1) - (c1 - c2)) > 2e-14 * fmax(1.0, fabs(c0));
+            }
+        }
+    }
+    unsigned bends = (unsigned)(__ballot(bend) & 0xffffull);
+    while (bends) {
+        const int c = __builtin_ctz(bends);
+        runs |= 1u << c;
+        bends &= ~(3u << c);
+    }
+    runs = (unsigned)__builtin_amdgcn_readfirstlane((int)runs);
+    direct = __builtin_popcount(runs) > 4 || (__ballot(wide) & 0xffffull) != 0ull;
+    if (!direct) {
+        if (lane < RUNS) {
+            unsigned m = runs;
+            for (int r = 0; r < lane; ++r) m &= m - 1;
+            if (m) {
+                const int c0 = __builtin_ctz(m);
+                m &= m - 1;
+                const int c1 = m ? __builtin_ctz(m) : 16;
+                const double* at = cw + c0 * cs;
+                const bool single = c1 - c0 < 2;
+                double a2r = 0.0;
+                double* rc = rcw + lane * RUNC;
+#pragma unroll
+                for (int q = 0; q < SL_P; ++q) {
+                    const double step = (q < p && !single) ? at[cs + q] - at[q] : 0.0;
+                    rc[q] = step;
+                    a2r = fma(step, step, a2r);
+                }
+                rc[SL_P] = a2r;
+                rc[SL_P + 1] = sl_exp_nonpos(-a2r);
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
     }
 }
 

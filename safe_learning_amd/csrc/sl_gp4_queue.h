@@ -89,6 +89,7 @@ struct Gp4ListArgs {
     const double* mean;          // [record][16][d] posterior means
     const unsigned* count;       // records the mean kernel appended
     int fold;                    // a later segment: fold the key already in the workgroup's partial
+    int halves;                  // decide and queue 8-cell halves (sl_gp4_halves.h); 0: whole blocks
 };
 
 SL_HD long long gp4l_draws(long long n) { return (n + GP4Q_SLOTS - 1) / GP4Q_SLOTS; }

@@ -15,7 +15,8 @@
 thread_local std::string g_sl_last_error;
 
 void sl_note_kernel(sl_ctx* ctx, bool append, const char* fmt, ...) {
-    char buf[160];
+    char buf[200];
+    if (!append) ctx->gp4_pair_counts = nullptr;
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(buf, sizeof(buf), fmt, ap);
@@ -28,7 +29,23 @@ void sl_note_kernel(sl_ctx* ctx, bool append, const char* fmt, ...) {
     }
 }
 
-extern "C" const char* sl_last_kernel(const sl_ctx* ctx) { return ctx ? ctx->last_kernel : ""; }
+extern "C" const char* sl_last_kernel(const sl_ctx* ctx) {
+    if (!ctx) return "";
+    if (ctx->gp4_pair_counts) {
+        // the counts of the block-mode launch the note names: read once, when somebody asks
+        sl_ctx* c = const_cast<sl_ctx*>(ctx);
+        unsigned long long n[2] = {0, 0};
+        const unsigned long long* from = c->gp4_pair_counts;
+        c->gp4_pair_counts = nullptr;
+        if (hipStreamSynchronize(c->stream) == hipSuccess &&
+            hipMemcpy(n, from, sizeof(n), hipMemcpyDeviceToHost) == hipSuccess) {
+            const size_t used = strlen(c->last_kernel);
+            snprintf(c->last_kernel + used, sizeof(c->last_kernel) - used,
+                     ", %llu paired composite(s), %llu lone half slot(s)", n[0], n[1]);
+        }
+    }
+    return ctx->last_kernel;
+}
 
 int sl_fail(sl_ctx* ctx, int code, const char* fmt, ...) {
     char buf[512];

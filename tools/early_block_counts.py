@@ -7,7 +7,7 @@ granules of 64 / 32 / 16 / 1 cells.  The kernel's granule is the 16-cell block (
 1-cell row the floor.
 
     python tools/early_block_counts.py [--variant informed|tight|survey] [--tiles 3000] [--seed 0]
-                                       [--variance-floor] [--headline-tau]
+                                       [--variance-floor] [--headline-tau] [--halves]
 
 --variance-floor: the lower bound of a cell before panel s is the decrease at err = beta sqrt(c_s
 (variance - partial |a|^2)) instead of err = 0, with c_s = sigma_n^2 sigma_min(Linv[256 s:, 256 s:])^2
@@ -16,6 +16,15 @@ posterior variance of all n points is at least c_s times the one of the first 25
 panel 0 the bound stays err = 0, as in k_gp_mean_blocks.
 --headline-tau: the variant's hyper-parameters on the headline's discretisation constant (the
 "little skipped" line of profiles/blocks_little_skipped.txt).
+
+--halves: the kernel decides the two 8-cell halves of a block separately and packs the low half of
+one block beside the high half of another into one slot of a composite tile (DESIGN.md 4.1 "Half
+blocks").  Adds the 8- and 4-cell granules to the table and prints, per panel, of all blocks: the
+full slots (both halves open), the paired slots (a low-only half beside a high-only half, as many
+as the rarer kind allows), the lone halves (the surplus of the other kind, a slot each), the share of
+open halves whose sibling is open too, the slots over the blocks open at the 16-cell granule - and
+the panel work at that packing.  (The first decision of a large launch is per block: the line
+"halves from panel 1 on" keeps the 16-cell count for panel 0.)
 
 Panel p of a tile multiplies (p + 1) 4 chunks against its 16 row blocks, the diagonal band a
 triangle: 40 / 104 / 168 / 232 (row block, chunk) products for p = 0 .. 3, 64 more per panel
@@ -101,6 +110,27 @@ def panel_work(gstage, npan):
     return float(open_fractions(gstage, npan).dot(w) / w.sum())
 
 
+def half_packing(stage, npan):
+    """Per panel, as fractions of all 16-cell blocks: (full slots, paired slots, lone halves, share of
+    open halves whose sibling is open, slots / blocks open at the 16-cell granule), and the panel work
+    with every panel packed in halves / with panel 0 on whole blocks."""
+    h = granule_stages(stage, 8).reshape(-1, 2)
+    rows, slots, blocks = [], [], []
+    for p in range(npan):
+        lo, hi = h[:, 0] > p, h[:, 1] > p
+        full, lo_only, hi_only = (lo & hi).mean(), (lo & ~hi).mean(), (~lo & hi).mean()
+        paired, lone = min(lo_only, hi_only), abs(lo_only - hi_only)
+        open_blocks, open_halves = (lo | hi).mean(), lo.mean() + hi.mean()
+        slots.append(full + paired + lone)
+        blocks.append(open_blocks)
+        rows.append((full, paired, lone, 2 * full / open_halves if open_halves else 1.0,
+                     slots[-1] / open_blocks if open_blocks else 1.0, 0.5 * open_halves / open_blocks if open_blocks else 1.0))
+    w = panel_weights(npan)
+    work = float(np.dot(slots, w) / w.sum())
+    work_from_1 = float((blocks[0] * w[0] + np.dot(slots[1:], w[1:])) / w.sum())
+    return rows, work, work_from_1
+
+
 def sample_tiles(case, tiles, seed):
     """Cell indices of ``tiles`` random 64-cell tiles of the case's grid (tile-aligned)."""
     n = int(np.prod(case["num_points"]))
@@ -109,8 +139,10 @@ def sample_tiles(case, tiles, seed):
     return (first[:, None] + np.arange(64)[None, :]).reshape(-1)
 
 
-def count(variant=None, tiles=3000, seed=0, batch=500, floor=False, headline_tau=False):
-    """{granule: (open fractions before each panel, panel work)} over random tiles."""
+def count(variant=None, tiles=3000, seed=0, batch=500, floor=False, headline_tau=False, granules=GRANULES,
+          halves=False):
+    """{granule: (open fractions before each panel, panel work)} over random tiles; halves: also
+    half_packing() of the same cells, under the key "halves"."""
     from safe_learning_amd.benchmarks import headline_case
     case = headline_case(variant=variant)
     if headline_tau:
@@ -121,8 +153,11 @@ def count(variant=None, tiles=3000, seed=0, batch=500, floor=False, headline_tau
         st, _, _, npan = cell_stages(case, idx[b:b + batch * 64], floor)
         stages.append(st)
     stage = np.concatenate(stages)
-    return {g: (open_fractions(granule_stages(stage, g), npan), panel_work(granule_stages(stage, g), npan))
-            for g in GRANULES}, npan
+    result = {g: (open_fractions(granule_stages(stage, g), npan), panel_work(granule_stages(stage, g), npan))
+              for g in granules}
+    if halves:
+        result["halves"] = half_packing(stage, npan)
+    return result, npan
 
 
 if __name__ == "__main__":
@@ -132,12 +167,23 @@ if __name__ == "__main__":
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--variance-floor", action="store_true")
     ap.add_argument("--headline-tau", action="store_true")
+    ap.add_argument("--halves", action="store_true")
     args = ap.parse_args()
-    result, npan = count(args.variant, args.tiles, args.seed, floor=args.variance_floor, headline_tau=args.headline_tau)
+    granules = (64, 32, 16, 8, 4, 1) if args.halves else GRANULES
+    result, npan = count(args.variant, args.tiles, args.seed, floor=args.variance_floor, headline_tau=args.headline_tau,
+                         granules=granules, halves=args.halves)
     print("# headline_case(variant=%r)%s, %d random tiles, seed %d, %d panels, lower bound: %s" % (
         args.variant, " at the headline tau" if args.headline_tau else "", args.tiles, args.seed, npan,
         "variance floor" if args.variance_floor else "err = 0"))
     print("# granule (cells) | open before panel 0 .. %d | panel work executed" % (npan - 1))
-    for g in GRANULES:
+    for g in granules:
         frac, work = result[g]
-        print("%5d | %s | %.3f" % (g, " / ".join("%.3f" % f for f in frac), work))
+        print(("%5d | %s | %.4f" if args.halves else "%5d | %s | %.3f") % (g, " / ".join("%.3f" % f for f in frac), work))
+    if args.halves:
+        rows, work, work_from_1 = result["halves"]
+        print("# packed halves, per panel, of all blocks: full slots | paired slots | lone halves | open halves with an "
+              "open sibling | slots / open blocks | halves / 2 / open blocks")
+        for p, row in enumerate(rows):
+            print("panel %d | %.4f | %.4f | %.4f | %.3f | %.3f | %.3f" % ((p,) + row))
+        print("panel work at that packing: %.4f (16-cell blocks: %.4f); halves from panel 1 on: %.4f"
+              % (work, result[16][1], work_from_1))
