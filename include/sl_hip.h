@@ -644,6 +644,43 @@ SL_API int  sl_nn_loss(sl_ctx* ctx, int kind, int64_t m, int d, const double* d_
                     const double* d_labels_or_targets, const double* d_class_weights, double safe_level,
                     double lagrange, double eps, double* d_losses, double* d_coeff, double* d_points);
 
+/* ---- policy gradients of future_values (reinforcement_learning.py:65-114; the
+ * optimizer.minimize(-reduce(rl.future_values(states)), var_list=rl.policy.parameters) of
+ * examples/inverted_pendulum.ipynb cells 9/12 and safe_learning/tests/test_rl.py:29-77), without the
+ * Lyapunov penalty.  The chain rule is cut at the action: Q(x, u) = r([x, u]) + gamma V(mu([x, u])),
+ *   d sum_i w_i Q(x_i, pi(x_i)) / d theta = sum_i sum_a (w_i dQ/du_a(x_i)) d pi_a(x_i) / d theta.
+ * sl_action_gradient: under the model of sl_model_set (policy, dynamics, quadratic reward, value table
+ *   in slot 0, gamma) d_grad [n][m] = dQ/du at the points d_points [n][d] (NULL: the first n grid points
+ *   of the model, as the Bellman sweeps generate them) and the actions d_actions [n][m] (NULL: u =
+ *   policy(x); a network policy goes through a per-point action table as in the sweeps); d_q [n] (may
+ *   be NULL) = Q, d_next [n][d] (may be NULL) = the successor mu.
+ *     dQ/du_a = [(P + P^T) z]_{d+a} + gamma sum_k c_k dmu_k/du_a
+ *   c = gradient of the value table's simplex at the successor, the simplex located as the table's
+ *   evaluation locates it; with `project` coordinate k of c counts only while lo_k <= mu_k <= hi_k (the
+ *   gradient of tf.minimum(tf.maximum(x, lo), hi), functions.py:1485).  SL_DYN_LINEAR: the action columns of
+ *   the matrix; SL_DYN_GP: the prior-mean columns plus sum_j alpha'_jk dk(x_j, z)/du_a of the head that
+ *   owns column k, for RBF heads and every sum-of-products description.  The Euler dynamics
+ *   (SL_DYN_PENDULUM, SL_DYN_CARTPOLE): SL_ERR_UNSUPPORTED.  One thread per point.
+ * sl_policy_param_grad: for the network of sl_policy_network_set (no sl_model_set needed; d = its input
+ *   width, at most SL_MAX_STATE_DIM) d_grad = sum_i sum_o d_coeff[i][o] d pi_o(p_i)/d theta for every
+ *   kernel and bias, concatenated in the order W_0, b_0, W_1, b_1, ..., W_out (W_l [in][out] row-major;
+ *   only the layers that have a bias contribute one) - the order sl_policy_network_set stores them in.
+ *   pi = output_scale h_L; activation derivatives as TensorFlow's (relu: 1 for a pre-activation > 0, else
+ *   0).  The outer products run on the matrix cores with the points as the reduction dimension, every
+ *   workgroup adds into its own slice of context scratch and a second kernel adds the slices in ascending
+ *   order: no atomics, the same bits at every call.
+ * sl_tri_param_grad: for the table of slot `slot` (sl_tri_set; its grid, simplices and `project`, not
+ *   its values) d_grad [nindex][cols] (vertex v) = sum of d_coeff[i][:] w_ik over all (i, k) with
+ *   simplex_k(p_i) = v, weights and simplices as the table's evaluation computes them; vertices that no
+ *   point touches get 0.  The (vertex, contribution) pairs are ordered with sl_sort_pairs and every run is
+ *   added in point order: no atomics, the same bits at every call.  n (d + 1) < 2^31. */
+SL_API int  sl_action_gradient(sl_ctx* ctx, int64_t n, const double* d_points, const double* d_actions,
+                    double* d_grad, double* d_q, double* d_next);
+SL_API int  sl_policy_param_grad(sl_ctx* ctx, int64_t n, int d, const double* d_points, const double* d_coeff,
+                    double* d_grad);
+SL_API int  sl_tri_param_grad(sl_ctx* ctx, int slot, int64_t n, const double* d_points, const double* d_coeff,
+                    double* d_grad);
+
 /* ---- multi-GPU collectives directly on RCCL ----------------------------- *
  * For callers without torch.distributed (the Python package issues the same exchanges through
  * torch.distributed, backend "nccl" = RCCL).  One communicator per context, one rank per GPU; every

@@ -11,5 +11,6 @@ from .lyapunov import *           # noqa: F401,F403
 from .reinforcement_learning import *   # noqa: F401,F403
 from . import utilities, distributed, kernels, training
 from .utilities import compute_roa, compute_trajectory, reward_rollout
-from .training import balanced_class_weights, pretraining_step, roa_classification_step
+from .training import (balanced_class_weights, policy_improvement_step, pretraining_step,
+                       roa_classification_step)
 from ._hip import HipEngineError

@@ -210,6 +210,10 @@ SIGNATURES = {
     # training a LyapunovNetwork
     "sl_nn_param_grad": (_int, (_vp, _i64, _int, _vp, _vp, _vp)),
     "sl_nn_loss": (_int, (_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _vp, _vp, _vp)),
+    # policy gradients of future_values
+    "sl_action_gradient": (_int, (_vp, _i64, _vp, _vp, _vp, _vp, _vp)),
+    "sl_policy_param_grad": (_int, (_vp, _i64, _int, _vp, _vp, _vp)),
+    "sl_tri_param_grad": (_int, (_vp, _int, _i64, _vp, _vp, _vp)),
     # RCCL collectives
     "sl_comm_unique_id": (_int, (C.c_char_p,)),
     "sl_comm_init": (_int, (_vp, C.c_char_p, _int, _int)),
@@ -657,6 +661,21 @@ class Context(object):
         self.lib.sl_nn_loss(self.handle, int(kind), int(m), int(d), _ptr(d_states), _ptr(d_next),
                             _ptr(d_labels_or_targets), _ptr(d_class_weights), float(safe_level), float(lagrange),
                             float(eps), _ptr(d_losses), _ptr(d_coeff), _ptr(d_points))
+
+    def action_gradient(self, n, d_points, d_actions, d_grad, d_q=None, d_next=None):
+        """``sl_action_gradient``: ``dQ/du`` of ``Q = r + gamma V(mean f)`` at ``n`` points under the
+        uploaded model (``d_points=None``: the grid points, ``d_actions=None``: the policy's actions)."""
+        self.lib.sl_action_gradient(self.handle, int(n), _ptr(d_points), _ptr(d_actions), _ptr(d_grad), _ptr(d_q),
+                                    _ptr(d_next))
+
+    def policy_param_grad(self, n, d, d_points, d_coeff, d_grad):
+        """``sl_policy_param_grad``: ``sum_i sum_o coeff[i][o] d pi_o(p_i)/d theta`` of the uploaded network
+        policy, flat in the order ``W_0, b_0, W_1, b_1, ..., W_out``."""
+        self.lib.sl_policy_param_grad(self.handle, int(n), int(d), _ptr(d_points), _ptr(d_coeff), _ptr(d_grad))
+
+    def tri_param_grad(self, slot, n, d_points, d_coeff, d_grad):
+        """``sl_tri_param_grad``: the same sum for the vertex table of slot ``slot`` -> ``[nindex, cols]``."""
+        self.lib.sl_tri_param_grad(self.handle, int(slot), int(n), _ptr(d_points), _ptr(d_coeff), _ptr(d_grad))
 
     def nn_train_scratch(self):
         """``sl_debug_nn_train_scratch`` -> (bytes of the scratch area, its guard zones are intact)."""

@@ -749,6 +749,36 @@ class Triangulation(DeterministicFunction):
                     self.discretization.discrete_points, self.project,
                     self._device(ctx).shape[1], self._device(ctx))
 
+    def parameter_gradient(self, points, coefficients):
+        """``sum_i coefficients[i, :] * d table(points[i]) / d parameters`` -> ``[nindex, k]``: vertex
+        ``v`` receives ``coefficients[i] * w_ik`` from every point whose simplex has ``v`` as its corner
+        ``k`` (weights and simplices as the evaluation computes them, ``project`` included) - what
+        ``tf.gradients(sum(coefficients * table(points)), parameters)`` returns for the reference's
+        table.  ``points`` ``[n, d]`` and ``coefficients`` ``[n, k]`` are NumPy arrays or device
+        tensors; the sums run on the GPU (``sl_tri_param_grad``) in a fixed order, the same bits at
+        every call."""
+        import torch
+        from . import _evaluate
+        if self.output_dim is None:
+            raise ValueError('the table has no parameters yet')
+        ctx, builder = _evaluate._builder(self.input_dim)
+        d_points = _evaluate._to_device(ctx, points)
+        n, d = d_points.shape
+        if d != self.input_dim:
+            raise ValueError('the table expects %d inputs, the points have %d columns' % (self.input_dim, d))
+        if not isinstance(coefficients, torch.Tensor):
+            coefficients = np.asarray(coefficients, dtype=np.float64)
+            coefficients = coefficients.reshape(max(len(np.atleast_1d(coefficients)), 1), -1)
+        d_coeff = _evaluate._to_device(ctx, coefficients)
+        if tuple(d_coeff.shape) != (n, self.output_dim):
+            raise ValueError('coefficients of shape %s for %d points and %d columns'
+                             % (tuple(d_coeff.shape), n, self.output_dim))
+        builder._upload_tri(1, self)
+        out = torch.empty((self.nindex, self.output_dim), dtype=torch.float64, device=ctx.torch_device)
+        ctx.tri_param_grad(1, n, d_points, d_coeff, out)
+        gradient = out.cpu().numpy()
+        return -gradient if self.negate else gradient
+
 
 # ----------------------------------------------------------------------------------------------
 # analytic dynamics of the examples
@@ -878,12 +908,15 @@ class NeuralNetwork(DeterministicFunction):
     callables; the names of the ones it uses are accepted here) -, ``output_scale`` multiplies the
     output (``:1727-1728``); with ``use_bias`` every layer but the last has a bias (``:1712, 1722``).
 
-    The reference's parameters are TensorFlow variables (Xavier initialisation, trained by SGD -
-    outside this package's scope): here they are given, ``parameters = [W_0, b_0, W_1, b_1, ...,
-    W_out]`` in the reference's variable order (``_parameter_iter``, ``:1731-1740``; ``W_l`` is
-    ``[in, units]``; without biases just the ``W_l``), or drawn Xavier-uniform from ``seed`` once
-    ``input_dim`` is known.  Assigning ``parameters`` again (or calling :meth:`touch` after editing the
-    arrays in place) makes the engine upload them again."""
+    The reference's parameters are TensorFlow variables (Xavier initialisation, trained by SGD): here
+    they are NumPy arrays on the host, ``parameters = [W_0, b_0, W_1, b_1, ..., W_out]`` in the
+    reference's variable order (``_parameter_iter``, ``:1731-1740``; ``W_l`` is ``[in, units]``;
+    without biases just the ``W_l``), given or drawn Xavier-uniform from ``seed`` once ``input_dim`` is
+    known.  Assigning ``parameters`` again (or calling :meth:`touch` after editing the arrays in place)
+    makes the engine upload them again.  Training: :meth:`parameter_gradient` sums ``coefficients *
+    d policy / d parameters`` over a batch on the GPU; ``PolicyIteration.policy_gradient`` and
+    ``training.policy_improvement_step`` build the notebook's policy-improvement step
+    (``optimizer.minimize(-reduce(rl.future_values(states)), var_list=rl.policy.parameters)``) on it."""
 
     _role = 'policy'
     _ACTIVATIONS = {None: 0, 'linear': 0, 'tanh': 1, 'relu': 2, 'sigmoid': 3}
@@ -962,6 +995,59 @@ class NeuralNetwork(DeterministicFunction):
             biases.append(next(it) if (self.use_bias and l < len(self.layers) - 1) else None)
         return ([self.input_dim] + self.layers, [self._ACTIVATIONS[a] for a in self.nonlinearities],
                 kernels, biases)
+
+    def _on_engine(self):
+        """The point-evaluation context with this network's current parameters on it (uploaded again
+        only when they changed: ``ModelBuilder._write_policy``)."""
+        from . import _evaluate
+        if self.input_dim is None:
+            raise ValueError('the network has no parameters yet: give input_dim or parameters')
+        ctx, builder = _evaluate._builder(self.input_dim)
+        builder._write_policy(_hip.ModelDesc(), self)
+        return ctx
+
+    def parameter_gradient(self, points, coefficients):
+        """``sum_i sum_o coefficients[i, o] * d policy_o(points[i]) / d theta`` for every array
+        ``theta`` of ``parameters`` (a list shaped like ``parameters``): what
+        ``tf.gradients(sum(coefficients * policy(points)), parameters)`` returns for the reference's
+        network, ``output_scale`` included.  ``points`` ``[n, d]`` and ``coefficients`` ``[n, m]`` are
+        NumPy arrays or device tensors; the sum over the points runs on the GPU
+        (``sl_policy_param_grad``) and is the same bit for bit at every call."""
+        import torch
+        from . import _evaluate
+        if self.negate:
+            raise ValueError('differentiate the network itself, not its negation')
+        ctx = self._on_engine()
+        d_points = _evaluate._to_device(ctx, points)
+        n, d = d_points.shape
+        if d != self.input_dim:
+            raise ValueError('the network expects %d inputs, the points have %d columns' % (self.input_dim, d))
+        if not isinstance(coefficients, torch.Tensor):
+            coefficients = np.asarray(coefficients, dtype=np.float64)
+            coefficients = coefficients.reshape(max(len(np.atleast_1d(coefficients)), 1), -1)
+        d_coeff = _evaluate._to_device(ctx, coefficients)
+        if tuple(d_coeff.shape) != (n, self.output_dim):
+            raise ValueError('coefficients of shape %s for %d points and %d outputs'
+                             % (tuple(d_coeff.shape), n, self.output_dim))
+        shapes = self._shapes()
+        sizes = [int(np.prod(shape)) for shape in shapes]
+        out = torch.empty(sum(sizes), dtype=torch.float64, device=ctx.torch_device)
+        ctx.policy_param_grad(n, d, d_points, d_coeff, out)
+        flat = out.cpu().numpy()
+        offsets = np.concatenate(([0], np.cumsum(sizes)))
+        return [flat[offsets[k]:offsets[k + 1]].reshape(shape).copy() for k, shape in enumerate(shapes)]
+
+    def lipschitz(self):
+        """``|output_scale| * prod_l sigma_max(W_l)``: a Lipschitz constant of the network for
+        contractive nonlinearities (relu, tanh, sigmoid), by SVD of the host copy of the kernels
+        (``functions.py:1744-1786``, whose product leaves the output scale to the caller)."""
+        if self._parameters is None:
+            raise ValueError('the network has no parameters yet: give input_dim or parameters')
+        constant = abs(self.output_scale)
+        for w in self._parameters:
+            if w.ndim == 2:
+                constant *= float(np.linalg.svd(w, compute_uv=False).max())
+        return constant
 
 
 class LyapunovNetwork(DeterministicFunction):

@@ -14,7 +14,7 @@ import numpy as np
 from . import _hip
 from . import distributed as dist_utils
 from ._model import ModelBuilder
-from .functions import ConstantFunction, Triangulation
+from .functions import CartPole, ConstantFunction, InvertedPendulum, NeuralNetwork, Triangulation
 
 __all__ = ['PolicyIteration', 'OptimizationError']
 
@@ -167,6 +167,98 @@ class PolicyIteration(object):
             constraint = lyapunov.v_decrease_bound(states, next_states) - lyapunov.threshold(states)
             updated = updated - lagrange_multiplier * constraint
         return updated
+
+    # ---- policy gradients (the policy-improvement half of policy iteration) ---------------------
+    def _action_gradient_device(self, states, policy, actions):
+        """One ``sl_action_gradient`` call -> device tensors (states [n, d], dQ/du [n, m], Q [n])."""
+        import torch
+        from . import _evaluate
+        if isinstance(self.dynamics, (InvertedPendulum, CartPole)):
+            raise TypeError('the action gradient is implemented for LinearSystem and GP dynamics '
+                            '(GaussianProcess, FunctionStack), not for the Euler dynamics %s'
+                            % type(self.dynamics).__name__)
+        ctx = self._ctx
+        dev = ctx.torch_device
+        if states is None or states is self.state_space:
+            if getattr(self, '_state_space_dev', None) is None or self._state_space_dev.device != dev:
+                self._state_space_dev = torch.from_numpy(np.ascontiguousarray(self.state_space)).to(dev)
+            d_states = self._state_space_dev
+        else:
+            d_states = _evaluate._to_device(ctx, states)
+        n, d = d_states.shape
+        if d != self.discretization.ndim:
+            raise ValueError('states of %d columns, the state space has %d dimensions'
+                             % (d, self.discretization.ndim))
+        d_actions = None
+        if actions is not None:
+            if not isinstance(actions, torch.Tensor):
+                actions = np.atleast_2d(np.asarray(actions, dtype=np.float64))
+            d_actions = _evaluate._to_device(ctx, actions)
+            if d_actions.shape[0] not in (1, n):
+                raise ValueError('actions must be one row or one row per state (%d), got %d'
+                                 % (n, d_actions.shape[0]))
+            d_actions = d_actions.expand(n, d_actions.shape[1]).contiguous()
+            # explicit actions never evaluate the policy: a constant of their width stands in its slot
+            policy = ConstantFunction(np.zeros(d_actions.shape[1]))
+        elif policy is None:
+            policy = self.policy
+        if isinstance(policy, (np.ndarray, torch.Tensor)):
+            raise TypeError('a per-vertex action table is not a policy of the states: pass it as `actions`')
+        self._upload(policy)
+        m = int(self._builder._desc.policy.m)
+        grad = torch.empty((n, m), dtype=torch.float64, device=dev)
+        q = torch.empty(n, dtype=torch.float64, device=dev)
+        ctx.action_gradient(n, d_states, d_actions, grad, q)
+        return d_states, grad, q
+
+    def action_gradient(self, states=None, policy=None, actions=None, lyapunov=None):
+        """``d future_values / d action`` -> ``[n, m]``: the derivative of ``r(x, u) + gamma V(f(x, u))``
+        (``:65-104``, the dynamics mean for a GP) with respect to ``u`` at ``u = policy(states)``
+        (default: ``self.policy``) or at the given ``actions`` (one row, or one per state), on the GPU
+        (``sl_action_gradient``).  ``states=None``: the grid's vertices.  Device tensors in, a device
+        tensor out; NumPy otherwise.  The value table's simplex gradient is taken at the successor,
+        and with ``project=True`` only the coordinates inside the table's limits count (TensorFlow's
+        gradient of the clip, ``functions.py:1485``).  LinearSystem and GP dynamics; the Lyapunov
+        penalty (``lyapunov=``) is not differentiated yet."""
+        import torch
+        if lyapunov is not None:
+            raise NotImplementedError('the gradient of the Lyapunov penalty (the derivative of beta sqrt(var) '
+                                      'and of L_v) is not implemented: differentiate without lyapunov=')
+        keep = isinstance(states, torch.Tensor)
+        _, grad, _ = self._action_gradient_device(states, policy, actions)
+        return grad if keep else grad.cpu().numpy()
+
+    def policy_gradient(self, states=None, reduction='mean', lyapunov=None):
+        """``(objective, gradient)`` of ``J(theta) = reduce_i future_values(x_i)`` under
+        ``self.policy`` with respect to its parameters: ``objective`` is ``J`` at the current
+        parameters, ``gradient`` is shaped like ``policy.parameters`` - the gradient
+        ``optimizer.minimize(-reduce(rl.future_values(states)), var_list=rl.policy.parameters)``
+        descends along, negated (``examples/inverted_pendulum.ipynb`` cells 9/12, ``reduction='mean'``;
+        ``tests/test_rl.py:59``, ``'sum'``).  One ``sl_action_gradient`` call, its result scaled by
+        ``1/n`` for ``'mean'``, then the policy's ``parameter_gradient`` on the device tensors: the
+        batch never visits the host.  ``policy`` must be a bare ``NeuralNetwork`` or
+        ``Triangulation``.  Single process only."""
+        if lyapunov is not None:
+            raise NotImplementedError('the gradient of the Lyapunov penalty (the derivative of beta sqrt(var) '
+                                      'and of L_v) is not implemented: differentiate without lyapunov=')
+        if reduction not in ('mean', 'sum'):
+            raise ValueError("reduction must be 'mean' or 'sum', got %r" % (reduction,))
+        if self._world > 1:
+            raise NotImplementedError('policy_gradient runs on one GPU: call it on one rank and broadcast '
+                                      'policy.parameters')
+        policy = self.policy
+        if type(policy) not in (NeuralNetwork, Triangulation) or policy.negate:
+            raise TypeError('policy_gradient differentiates a bare NeuralNetwork or Triangulation policy, '
+                            'not %s' % (('a negated ' if getattr(policy, 'negate', False) else '')
+                                        + type(policy).__name__))
+        d_states, grad, q = self._action_gradient_device(states, None, None)
+        if reduction == 'mean':
+            n = d_states.shape[0]
+            grad = grad * (1.0 / n)
+            objective = float(q.sum()) / n
+        else:
+            objective = float(q.sum())
+        return objective, policy.parameter_gradient(d_states, grad)
 
     def value_iteration(self, action_space=None):
         """One Jacobi sweep (``:135-140``); returns ``max |dV|``.

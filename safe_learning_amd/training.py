@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _hip
 
-__all__ = ['balanced_class_weights', 'pretraining_step', 'roa_classification_step']
+__all__ = ['balanced_class_weights', 'pretraining_step', 'roa_classification_step', 'policy_improvement_step']
 
 
 def _check_single_process():
@@ -122,3 +122,27 @@ def roa_classification_step(lyapunov, states, roa_labels, class_weights, safe_le
         _descend(network, ctx, points, coeff, float(learning_rate))
     objective, classifier, decrease = losses.tolist()
     return dict(objective=objective, classifier_loss=classifier, decrease_loss=decrease)
+
+
+def policy_improvement_step(rl, states, learning_rate, reduction='mean'):
+    """One gradient step of the policy-improvement half of policy iteration on ``rl.policy`` (a bare
+    ``NeuralNetwork`` or ``Triangulation``): ``theta <- theta + learning_rate * dJ/dtheta`` with
+    ``J = reduce_i rl.future_values(states_i)`` - plain gradient descent on ``-J``, the
+    ``optimizer.minimize(-reduce(rl.future_values(states)), var_list=rl.policy.parameters)`` of
+    ``examples/inverted_pendulum.ipynb`` cells 9/12 (``reduction='mean'``) and of
+    ``tests/test_rl.py:59`` (``'sum'``).  Returns the objective ``J`` BEFORE the step;
+    ``learning_rate=None`` evaluates it only.  ``states=None``: the grid's vertices.
+
+    The gradient comes from ``rl.policy_gradient`` (``sl_action_gradient`` and the policy's
+    ``parameter_gradient`` on the GPU); the update is assigned to ``policy.parameters`` on the host,
+    where the master copy lives: sweeps, ``value_iteration``, the successor cache and ``Lyapunov``
+    objects that share the policy notice the edit through its version token."""
+    _check_single_process()
+    objective, gradient = rl.policy_gradient(states, reduction)
+    if learning_rate is not None:
+        policy, rate = rl.policy, float(learning_rate)
+        if isinstance(gradient, list):
+            policy.parameters = [w + rate * g for w, g in zip(policy.parameters, gradient)]
+        else:
+            policy.parameters = policy.parameters + rate * gradient
+    return objective

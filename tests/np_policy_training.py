@@ -1,0 +1,665 @@
+"""NumPy reference of the policy-gradient path (``PolicyIteration.action_gradient`` / ``policy_gradient``,
+``NeuralNetwork.parameter_gradient``, ``Triangulation.parameter_gradient``,
+``training.policy_improvement_step``), built from the oracle's classes.
+
+    Q(x, u) = r([x, u]) + gamma V(mu([x, u]))        reinforcement_learning.py:65-104
+    dQ/du_a = [(P + P^T) z]_{d+a} + gamma sum_k c_k dmu_k/du_a
+
+``c`` is ``oracle.Triangulation.gradient`` at the successor (masked where ``project`` clips it: TensorFlow's
+gradient of ``tf.minimum(tf.maximum(x, lo), hi)`` is 1 inside the limits and on them, 0 outside), ``mu`` the
+oracle's LinearSystem or the mean of its ``GPRCached`` (``alpha' = L^-T alpha``, ``mean = sum_j k_j alpha'_j``),
+the kernels' values the kernel classes' ``K`` (asserted equal by the host test), their derivatives written
+out here per class.
+
+Every gradient comes with its error companion ``A``: the same sum with every term replaced by its absolute
+value.  ``A`` bounds what a rounding error of the evaluation can grow to, so results are compared as
+``|g - g_ref| <= tol * A`` (a tolerance relative to ``|g|`` fails on entries that cancel).  Every function
+runs in the precision of ``dtype``: ``np.float64`` is the reference, ``np.longdouble`` measures the
+reference's own error, and ``tolerance(key, n)`` is 32 times that measured error - the rule and the margin
+of tests/np_lyapunov_training.py.
+"""
+
+import numpy as np
+import scipy.linalg
+
+import oracle
+from oracle import np_functions as onp
+
+LONG = np.longdouble
+
+
+# ---- kernels: value and derivative with respect to the query's action columns ------------------------------
+def kernel_terms(kern, X, Z, cols, dtype=np.float64):
+    """-> (K, dK, KA, dKA): ``K[j, i] = k(X_j, Z_i)``, ``dK[j, i, a] = dk/dZ_{i, cols[a]}`` and the
+    companions (sums of absolute values of the product-rule / sum terms)."""
+    X, Z = np.asarray(X, dtype=dtype), np.asarray(Z, dtype=dtype)
+    n, q, m = len(X), len(Z), len(cols)
+    if isinstance(kern, onp.Prod):
+        K, dK = np.ones((n, q), dtype=dtype), np.zeros((n, q, m), dtype=dtype)
+        KA, dKA = np.ones((n, q), dtype=dtype), np.zeros((n, q, m), dtype=dtype)
+        for member in kern.kern_list:
+            k, dk, ka, dka = kernel_terms(member, X, Z, cols, dtype)
+            dK, dKA = dK * k[:, :, None] + K[:, :, None] * dk, dKA * ka[:, :, None] + KA[:, :, None] * dka
+            K, KA = K * k, KA * ka
+        return K, dK, KA, dKA
+    if isinstance(kern, onp.Add):
+        parts = [kernel_terms(member, X, Z, cols, dtype) for member in kern.kern_list]
+        return tuple(sum(p[i] for p in parts) for i in range(4))
+    active = np.arange(kern.input_dim) if isinstance(kern, onp.RBF) else kern.active_dims
+    Xa, Za = X[:, active], Z[:, active]
+    where = [list(active).index(c) if c in active else None for c in cols]
+    dK = np.zeros((n, q, m), dtype=dtype)
+    if isinstance(kern, onp.Linear):
+        var = np.asarray(kern.variance, dtype=dtype)
+        K = (Xa * var).dot(Za.T)
+        KA = (np.abs(Xa) * var).dot(np.abs(Za).T)
+        for a, pos in enumerate(where):
+            if pos is not None:
+                dK[:, :, a] = (Xa[:, pos] * var[pos])[:, None]
+        return K, dK, KA, np.abs(dK)
+    ls = np.asarray(kern.lengthscales, dtype=dtype)
+    diff = (Xa[:, None, :] - Za[None, :, :]) / ls                   # (a_q - z_q) / l_q
+    r2 = np.sum(np.square(diff), axis=2)
+    var = dtype(kern.variance)
+    if isinstance(kern, onp.Matern32):
+        s = np.sqrt(dtype(3)) * np.sqrt(r2 + dtype(1e-12))
+        e = np.exp(-s)
+        K = var * (1 + s) * e
+        factor = 3 * var * e
+    else:                                                            # RBF / SlicedRBF
+        K = var * np.exp(-r2 / 2)
+        factor = K
+    for a, pos in enumerate(where):
+        if pos is not None:
+            dK[:, :, a] = factor * diff[:, :, pos] / ls[pos]
+    return K, dK, np.abs(K), np.abs(dK)
+
+
+# ---- dynamics: mean and its action Jacobian ------------------------------
+def _gp_members(dynamics):
+    """[(GPRCached, first output column)] of an oracle GaussianProcess / FunctionStack."""
+    heads = dynamics.functions if isinstance(dynamics, onp.FunctionStack) else [dynamics]
+    out, col = [], 0
+    for head in heads:
+        out.append((head.gaussian_process, col))
+        col += head.gaussian_process.Y.shape[1]
+    return out
+
+
+def dynamics_terms(dynamics, z, d, dtype=np.float64):
+    """-> (mean [n, d], J [n, d, m], JA): ``J[i, k, a] = d mu_k / d u_a`` at ``z = [x, u]``."""
+    z = np.asarray(z, dtype=dtype)
+    n, p = z.shape
+    m = p - d
+    cols = list(range(d, p))
+    if isinstance(dynamics, onp.LinearSystem):
+        M = np.asarray(dynamics.matrix, dtype=dtype)
+        J = np.broadcast_to(M[:, d:], (n, d, m)).copy()
+        return z.dot(M.T), J, np.abs(J)
+    mean, J, JA = (np.zeros((n, d), dtype=dtype), np.zeros((n, d, m), dtype=dtype), np.zeros((n, d, m), dtype=dtype))
+    for gp, col0 in _gp_members(dynamics):
+        assert gp._scale == 1.0
+        alpha = scipy.linalg.solve_triangular(gp.cholesky.T, gp.alpha, lower=False).astype(dtype)   # L^-T alpha
+        K, dK, _, dKA = kernel_terms(gp.kern, gp.X, z, cols, dtype)
+        prior = np.asarray(gp.mean_function.matrix, dtype=dtype)
+        out = slice(col0, col0 + alpha.shape[1])
+        mean[:, out] = K.T.dot(alpha) + z.dot(prior.T)
+        J[:, out, :] = np.einsum("jia,jk->ika", dK, alpha) + prior[None, :, d:]
+        JA[:, out, :] = np.einsum("jia,jk->ika", dKA, np.abs(alpha)) + np.abs(prior)[None, :, d:]
+    return mean, J, JA
+
+
+# ---- the value table's simplex gradient and its clip mask ------------------------------
+def table_gradient(tri, points, dtype=np.float64):
+    """-> (c [n, d], cA): the gradient of the simplex ``oracle.Triangulation`` finds for the (float64)
+    points, ``c_k = sum_j H[k, j] (p_j - p_0)``, times the mask of ``project``."""
+    pts64 = np.asarray(points, dtype=np.float64)
+    ids = tri.find_simplex(pts64)
+    simplices = tri.simplices(ids)
+    H = tri.hyperplanes[ids % tri.triangulation.nsimplex].astype(dtype)        # [n, d(k), d(j)]
+    params = np.asarray(tri.parameters, dtype=dtype)[:, 0][simplices]          # [n, d + 1]
+    delta = params[:, 1:] - params[:, :1]
+    c = np.einsum("nkj,nj->nk", H, delta)
+    cA = np.einsum("nkj,nj->nk", np.abs(H), np.abs(params[:, 1:]) + np.abs(params[:, :1]))
+    if tri.project:
+        lim = tri.discretization.limits
+        inside = (pts64 >= lim[:, 0]) & (pts64 <= lim[:, 1])
+        c, cA = c * inside, cA * inside
+    return c, cA
+
+
+def table_value(tri, points, dtype=np.float64):
+    w, simplices, _ = table_weights(tri, points, dtype)
+    return np.sum(w * np.asarray(tri.parameters, dtype=dtype)[:, 0][simplices], axis=1)
+
+
+def table_weights(tri, points, dtype=np.float64):
+    """``Triangulation._get_weights`` in ``dtype`` (simplices located in float64) -> (w, simplices, wA)."""
+    pts64 = np.atleast_2d(np.asarray(points, dtype=np.float64))
+    disc = tri.discretization
+    ids = tri.find_simplex(pts64)
+    simplices = tri.simplices(ids)
+    origins = disc.index_to_state(simplices[:, 0]).astype(dtype)
+    H = tri.hyperplanes[ids % tri.triangulation.nsimplex].astype(dtype)
+    pts = np.asarray(points, dtype=dtype).reshape(pts64.shape)
+    if tri.project:
+        pts = np.clip(pts, disc.limits[:, 0].astype(dtype), disc.limits[:, 1].astype(dtype))
+    offset = pts - origins
+    w1 = np.sum(offset[:, :, None] * H, axis=1)
+    w1A = np.sum(np.abs(offset)[:, :, None] * np.abs(H), axis=1)
+    w = np.concatenate((1 - np.sum(w1, axis=1, keepdims=True), w1), axis=1)
+    wA = np.concatenate((1 + np.sum(w1A, axis=1, keepdims=True), w1A), axis=1)
+    return w, simplices, wA
+
+
+# ---- the action gradient ------------------------------
+def action_gradient(rl, states, actions, dtype=np.float64):
+    """``rl``: an oracle PolicyIteration.  -> dict(grad [n, m], A, q [n], next [n, d])."""
+    x = np.atleast_2d(np.asarray(states, dtype=dtype))
+    u = np.atleast_2d(np.asarray(actions, dtype=dtype))
+    n, d = x.shape
+    m = u.shape[1]
+    z = np.hstack((x, u))
+    mean, J, JA = dynamics_terms(rl.dynamics, z, d, dtype)
+    c, cA = table_gradient(rl.value_function, mean, dtype)
+    P = np.asarray(rl.reward_function.matrix, dtype=dtype)
+    S = P + P.T
+    dr, drA = z.dot(S)[:, d:], np.abs(z).dot(np.abs(S))[:, d:]
+    gamma = dtype(rl.gamma)
+    grad = dr + gamma * np.einsum("nk,nka->na", c, J)
+    A = drA + gamma * np.einsum("nk,nka->na", cA, JA)
+    q = np.einsum("ni,ij,nj->n", z, P, z) + gamma * table_value(rl.value_function, mean, dtype)
+    return dict(grad=grad, A=A, q=q, next=mean)
+
+
+def policy_actions(policy, states, dtype=np.float64):
+    """A NeuralNetwork or Triangulation policy (oracle objects) at the states, in ``dtype``."""
+    if isinstance(policy, onp.NeuralNetwork):
+        return network_forward(policy, states, dtype)[-1][2] * dtype(policy.output_scale)
+    w, simplices, _ = table_weights(policy, states, dtype)
+    return np.sum(w[:, :, None] * np.asarray(policy.parameters, dtype=dtype)[simplices], axis=1)
+
+
+# ---- NeuralNetwork policy ------------------------------
+def _act(name, x):
+    if name == 'tanh':
+        return np.tanh(x)
+    if name == 'relu':
+        return np.maximum(x, 0)
+    if name == 'sigmoid':
+        return 1 / (1 + np.exp(-x))
+    return x
+
+
+def _dact(name, pre, post):
+    if name == 'tanh':
+        return 1 - post * post
+    if name == 'relu':
+        return (pre > 0).astype(post.dtype)
+    if name == 'sigmoid':
+        return post * (1 - post)
+    return np.ones_like(post)
+
+
+def _layers(net, dtype):
+    it, out = iter(net.parameters), []
+    for l in range(len(net.layers)):
+        W = np.asarray(next(it), dtype=dtype)
+        b = np.asarray(next(it), dtype=dtype) if (net.use_bias and l < len(net.layers) - 1) else None
+        out.append((W, b))
+    return out
+
+
+def network_forward(net, points, dtype=np.float64):
+    """-> [(input, pre, post)] per layer."""
+    h = np.atleast_2d(np.asarray(points, dtype=dtype))
+    cache = []
+    for (W, b), name in zip(_layers(net, dtype), net.nonlinearities):
+        pre = h.dot(W) if b is None else h.dot(W) + b
+        post = _act(name, pre)
+        cache.append((h, pre, post))
+        h = post
+    return cache
+
+
+def network_parameter_gradient(net, points, coefficients, dtype=np.float64, order=None):
+    """``sum_i sum_o c[i, o] d pi_o(p_i)/d theta`` -> (gradients, companions), lists shaped like
+    ``net.parameters``; ``order``: a permutation of the points (another summation order)."""
+    points = np.atleast_2d(np.asarray(points, dtype=dtype))
+    c = np.asarray(coefficients, dtype=dtype).reshape(len(points), -1)
+    if order is not None:
+        points, c = points[order], c[order]
+    layers = _layers(net, dtype)
+    cache = network_forward(net, points, dtype)
+    grads, comps = [], []
+    delta = deltaA = None
+    for l in reversed(range(len(layers))):
+        h_in, pre, post = cache[l]
+        dact = _dact(net.nonlinearities[l], pre, post)
+        if l == len(layers) - 1:
+            delta = c * dtype(net.output_scale) * dact
+            deltaA = np.abs(c) * abs(dtype(net.output_scale)) * np.abs(dact)
+        else:
+            W_next = layers[l + 1][0]
+            delta = delta.dot(W_next.T) * dact
+            deltaA = deltaA.dot(np.abs(W_next).T) * np.abs(dact)
+        entry, entryA = [h_in.T.dot(delta)], [np.abs(h_in).T.dot(deltaA)]
+        if layers[l][1] is not None:
+            entry.append(delta.sum(axis=0))
+            entryA.append(deltaA.sum(axis=0))
+        grads[:0], comps[:0] = entry, entryA
+    return grads, comps
+
+
+def relu_margin(net, points):
+    """Smallest |pre-activation| of any relu unit, per point (inf without relu layers)."""
+    worst = np.full(len(np.atleast_2d(points)), np.inf)
+    for (_, pre, _), name in zip(network_forward(net, points), net.nonlinearities):
+        if name == 'relu':
+            worst = np.minimum(worst, np.abs(pre).min(axis=1))
+    return worst
+
+
+# ---- Triangulation policy ------------------------------
+def table_parameter_gradient(tri, points, coefficients, dtype=np.float64):
+    """Vertex v receives ``sum coeff[i, :] w_ik`` over all (i, k) with ``simplex_k(p_i) = v``, in point
+    order -> (gradient [nindex, cols], companion)."""
+    points = np.atleast_2d(np.asarray(points, dtype=dtype))
+    c = np.asarray(coefficients, dtype=dtype).reshape(len(points), -1)
+    w, simplices, wA = table_weights(tri, points, dtype)
+    grad = np.zeros((tri.nindex, c.shape[1]), dtype=dtype)
+    comp = np.zeros((tri.nindex, c.shape[1]), dtype=dtype)
+    for i in range(len(points)):
+        for k in range(simplices.shape[1]):
+            grad[simplices[i, k]] += c[i] * w[i, k]
+            comp[simplices[i, k]] += np.abs(c[i]) * wA[i, k]
+    return grad, comp
+
+
+# ---- the step ------------------------------
+def policy_gradient(rl, states, reduction='mean', dtype=np.float64):
+    """-> (objective, gradient, companion) of ``J = reduce_i Q(x_i, pi(x_i))`` with respect to
+    ``rl.policy.parameters`` (a list for a network, an array for a table)."""
+    states = rl.state_space if states is None else np.atleast_2d(states)
+    u = policy_actions(rl.policy, states, dtype)
+    terms = action_gradient(rl, states, u, dtype)
+    scale = dtype(1) / len(states) if reduction == 'mean' else dtype(1)
+    coeff = terms['grad'] * scale
+    objective = np.sum(terms['q']) * scale
+    if isinstance(rl.policy, onp.NeuralNetwork):
+        grad, comp = network_parameter_gradient(rl.policy, states, coeff, dtype)
+        # the companion of the chain: |coeff| is bounded by A of the action gradient
+        _, comp = network_parameter_gradient(rl.policy, states, terms['A'] * scale, dtype)
+    else:
+        grad, _ = table_parameter_gradient(rl.policy, states, coeff, dtype)
+        _, comp = table_parameter_gradient(rl.policy, states, terms['A'] * scale, dtype)
+    return objective, grad, comp
+
+
+def policy_improvement_step(rl, states, learning_rate, reduction='mean'):
+    """``theta <- theta + learning_rate dJ/dtheta`` -> (objective before the step, gradient, companion)."""
+    objective, grad, comp = policy_gradient(rl, states, reduction)
+    if learning_rate is not None:
+        if isinstance(grad, list):
+            rl.policy.parameters = [w + learning_rate * g for w, g in zip(rl.policy.parameters, grad)]
+        else:
+            rl.policy.parameters = rl.policy.parameters + learning_rate * grad
+    return float(objective), grad, comp
+
+
+# ---- comparing ------------------------------
+def _as_list(x):
+    return list(x) if isinstance(x, (list, tuple)) else [x]
+
+
+def ratio_to_companion(got, ref, comp, rows=None):
+    """max |got - ref| / A in units of 2^-53 (entries with A = 0 must agree exactly); ``rows``: a mask of the
+    leading axis (points that are compared)."""
+    worst = 0.0
+    for g, r, a in zip(_as_list(got), _as_list(ref), _as_list(comp)):
+        g, r, a = (np.asarray(v, dtype=LONG) for v in (g, r, a))
+        if rows is not None:
+            g, r, a = g[rows], r[rows], a[rows]
+        diff = np.abs(g - r)
+        assert np.all(diff[a == 0] == 0)
+        if (a > 0).any():
+            worst = max(worst, float((diff[a > 0] / a[a > 0]).max()))
+    return worst * 2.0 ** 53
+
+
+# ---- the cases of the tests ------------------------------
+def lqr_case():
+    """The 1-D system of safe_learning/tests/test_rl.py:29-77 (tests/golden/reference_known_answers.json)."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_known_answers.json")) as f:
+        g = json.load(f)["policy_iteration_integration"]
+    a, b, q, r = (np.array(g[k], dtype=float) for k in "abqr")
+    k, p = oracle.dlqr(a, b, q, r)
+    return dict(g=g, a=a, b=b, q=q, r=r, k=k, p=p)
+
+
+def lqr_pair(sl=None, value_sweeps=3):
+    """-> (oracle PolicyIteration, product PolicyIteration or None) of lqr_case from the policy -k/2 x, the
+    value table after ``value_sweeps`` oracle sweeps (not zero: the simplex gradients differ)."""
+    c = lqr_case()
+    g = c["g"]
+    reward = -scipy.linalg.block_diag(c["q"], c["r"])
+    vgrid = oracle.GridWorld(g["value_grid"]["limits"], g["value_grid"]["num_points"])
+    pgrid = oracle.GridWorld(g["policy_grid"]["limits"], g["policy_grid"]["num_points"])
+    ovf = oracle.Triangulation(vgrid, 0. * vgrid.all_points, project=True)
+    opolicy = oracle.Triangulation(pgrid, -c["k"] / 2 * pgrid.all_points)
+    orl = oracle.PolicyIteration(opolicy, oracle.LinearSystem((c["a"], c["b"])), oracle.QuadraticFunction(reward), ovf)
+    for _ in range(value_sweeps):
+        orl.value_iteration()
+    rl = None
+    if sl is not None:
+        svgrid = sl.GridWorld(g["value_grid"]["limits"], g["value_grid"]["num_points"])
+        spgrid = sl.GridWorld(g["policy_grid"]["limits"], g["policy_grid"]["num_points"])
+        vf = sl.Triangulation(svgrid, ovf.parameters.copy(), project=True)
+        policy = sl.Triangulation(spgrid, opolicy.parameters.copy())
+        rl = sl.PolicyIteration(policy, sl.LinearSystem((c["a"], c["b"])), sl.QuadraticFunction(reward), vf)
+    return orl, rl
+
+
+NETWORKS = {
+    # key: (input width, layers, nonlinearities, use_bias, output_scale)
+    "notebook": (2, [32, 32, 1], ['relu', 'relu', 'tanh'], True, 0.7),
+    "wide": (2, [64, 64, 2], ['tanh', 'sigmoid', None], False, 1.0),
+    "one": (1, [1], ['tanh'], True, 1.0),
+    "ragged": (4, [17, 5, 1], ['tanh', 'relu', 'tanh'], True, 1.3),
+}
+WEIGHT_SCALE = 0.8
+
+
+def network_parameters(key, seed=0):
+    d, layers, _, use_bias, _ = NETWORKS[key]
+    rng = np.random.default_rng(seed + 17)
+    widths, params = [d] + layers, []
+    for l in range(len(layers)):
+        shape = (widths[l], widths[l + 1])
+        params.append(WEIGHT_SCALE * rng.uniform(-1, 1, shape) * np.sqrt(6. / sum(shape)))
+        if use_bias and l < len(layers) - 1:
+            params.append(0.1 * rng.uniform(-1, 1, widths[l + 1]))
+    return params
+
+
+def make_network(key, sl=None, seed=0):
+    """-> (oracle NeuralNetwork, product NeuralNetwork or None) with the same parameters."""
+    d, layers, acts, use_bias, scale = NETWORKS[key]
+    params = network_parameters(key, seed)
+    onet = onp.NeuralNetwork(layers, acts, output_scale=scale, use_bias=use_bias, parameters=params)
+    net = None
+    if sl is not None:
+        net = sl.NeuralNetwork(layers, acts, output_scale=scale, use_bias=use_bias,
+                               parameters=[p.copy() for p in params])
+    return onet, net
+
+
+def make_batch(key, n, seed=1):
+    """Points in [-1, 1]^d and coefficients [n, m] with both signs and exact zeros."""
+    d, layers = NETWORKS[key][0], NETWORKS[key][1]
+    rng = np.random.default_rng(seed + n)
+    points = rng.uniform(-1, 1, (n, d))
+    coeff = rng.normal(size=(n, layers[-1]))
+    coeff[rng.uniform(size=n) < 0.2] = 0.0
+    if n > 2:
+        coeff[n // 2] = 0.0
+    coeff[0] = 0.75
+    coeff[-1] = -1.25 if n > 1 else 0.75
+    return points, coeff
+
+
+def smooth_table(grid, P, sign=-1.0):
+    """A value table that is not a plane anywhere: -(x^T P x) (1 + bump)."""
+    pts = grid.all_points
+    vals = np.einsum('ij,jk,ik->i', pts, P, pts)
+    bump = 1.0 + 0.05 * np.sin(3.0 * pts[:, 0]) * np.cos(2.0 * pts[:, -1])
+    return (sign * vals * bump)[:, None]
+
+
+SYSTEMS = ("lqr", "pendulum", "cartpole", "linear22")
+POLICY_OF = {"pendulum": "notebook", "cartpole": "ragged", "linear22": "wide"}
+
+
+def system_case(name):
+    """Parameters of one action-gradient system: dict(case, value_points, reward, gamma, policy key)."""
+    import cases
+    from safe_learning_amd.benchmarks import notebook_kernels
+    if name == "pendulum":
+        case = cases.make_case("pendulum", n_gp=70, stack=True)
+        case["dynamics"]["kernels"] = notebook_kernels(case)
+        nv = 17
+    elif name == "cartpole":
+        case = cases.make_case("cartpole", n_gp=90)
+        nv = 5
+    else:
+        A = np.array([[1.0, 0.1], [-0.05, 0.95]])
+        B = np.array([[0.02, 0.1], [0.1, -0.03]])
+        case = dict(name="linear22", stack=False, d=2, m=2, limits=[[-1., 1.]] * 2, saturate=None,
+                    dynamics={"kind": "linear", "matrix": np.hstack((A, B))}, P=np.array([[1.0, 0.2], [0.2, 0.7]]),
+                    K=np.zeros((2, 2)), lv=("const", 1.0))
+        nv = 9
+    d, m = case["d"], case["m"]
+    rng = np.random.default_rng(3)
+    R = rng.uniform(-0.2, 0.2, (d + m, d + m))                      # not symmetric: P + P^T matters
+    reward = -(scipy.linalg.block_diag(np.eye(d), 0.1 * np.eye(m)) + R * 0.1)
+    return dict(case=case, nv=nv, reward=reward, gamma=0.95, policy=POLICY_OF[name])
+
+
+def system_pair(name, sl=None):
+    """-> (oracle PolicyIteration, product PolicyIteration or None) for one of SYSTEMS, the policy a
+    NeuralNetwork (a 5-vertex table for 'lqr')."""
+    import cases
+    if name == "lqr":
+        return lqr_pair(sl)
+    spec = system_case(name)
+    case = spec["case"]
+    _, odynamics, _, _ = cases.oracle_specs(dict(case, K=np.zeros((case["m"], case["d"])), saturate=None))
+    ovgrid = oracle.GridWorld(case["limits"], spec["nv"])
+    ovf = oracle.Triangulation(ovgrid, smooth_table(ovgrid, case["P"]), project=True)
+    onet, net = make_network(spec["policy"], sl)
+    orl = oracle.PolicyIteration(onet, odynamics, oracle.QuadraticFunction(spec["reward"]), ovf, gamma=spec["gamma"])
+    rl = None
+    if sl is not None:
+        from safe_learning_amd.benchmarks import build_specs
+        _, dynamics, _, _ = build_specs(dict(case, K=np.zeros((case["m"], case["d"])), saturate=None))
+        vgrid = sl.GridWorld(case["limits"], spec["nv"])
+        vf = sl.Triangulation(vgrid, ovf.parameters.copy(), project=True)
+        rl = sl.PolicyIteration(net, dynamics, sl.QuadraticFunction(spec["reward"]), vf, gamma=spec["gamma"])
+    return orl, rl
+
+
+def system_states(name, n, seed=2):
+    """States in [-1.15, 1.15]^d ([-1.6, 1.6] for 'lqr', whose closed loop contracts by a third): some
+    states, and some successors under the policy as under the explicit actions, lie outside the table's
+    limits, so the clip mask of ``project`` is exercised; explicit actions in [-1, 1]^m beside them."""
+    orl, _ = system_pair(name)
+    d = orl.value_function.input_dim
+    m = orl.policy.output_dim if hasattr(orl.policy, "output_dim") else 1
+    rng = np.random.default_rng(seed + n)
+    reach = 1.6 if name == "lqr" else 1.15
+    return rng.uniform(-reach, reach, (n, d)), rng.uniform(-1, 1, (n, m))
+
+
+def comparable(orl, states, actions, margin=1e-9, through_policy=False):
+    """Mask of the points whose derivative does not jump nearby: the successor is not an ambiguous point of
+    the value table (tests/exclusions.py), no successor coordinate lies within ``margin`` of a limit, and
+    (``through_policy``: the chain goes on into a network policy) no relu pre-activation within ``margin`` of 0."""
+    import exclusions
+    nxt = orl.dynamics(states, actions)
+    nxt = nxt[0] if isinstance(nxt, tuple) else nxt
+    tri = orl.value_function
+    ok = ~exclusions.ambiguous_points(tri, nxt)
+    lim = tri.discretization.limits
+    ok &= (np.abs(nxt - lim[:, 0]) > margin).all(axis=1) & (np.abs(nxt - lim[:, 1]) > margin).all(axis=1)
+    if through_policy and isinstance(orl.policy, onp.NeuralNetwork):
+        ok &= relu_margin(orl.policy, states) > margin
+    return ok
+
+
+MAX_EXCLUDED = 0.02
+
+
+# ---- the tolerance ------------------------------
+# max |g_float64 - g_longdouble| / A of this reference, in units of 2^-53, measured by measure_reference_ratio
+# below and rounded up (tests/test_policy_training_host.py asserts that a re-measurement stays below these
+# figures).  ("action", system, explicit actions?, n), ("network", key, n), ("table", key), ("steps-lqr", k),
+# ("steps-notebook", k).  A key without a figure (batch sizes that depend on the device's CU count) is measured
+# on the spot, once.
+#
+# The action gradient is a function of ONE point: its error at a point does not depend on how many points a
+# call evaluates, and the ratio of a small batch is the luck of its draw (0.007 for one point of the pendulum,
+# 1.9 over a thousand).  Its figure is therefore the maximum over the ACTION_RATIO_POINTS states of
+# system_states(name, ACTION_RATIO_POINTS), for every batch size of that system; the parameter gradients are
+# sums over the batch (A grows like n, the error like sqrt(n)) and have one figure per batch.
+ACTION_RATIO_POINTS = 1000
+REFERENCE_RATIO = {
+    ("action", "lqr", True): 1.12, ("action", "lqr", False): 2.07, ("action", "pendulum", True): 0.568,
+    ("action", "pendulum", False): 1.89,
+    ("action", "cartpole", True): 0.687, ("action", "cartpole", False): 1.58, ("action", "linear22", True): 1.09,
+    ("action", "linear22", False): 3.31,
+    ("network", "notebook", 1): 47.5, ("network", "notebook", 15): 114, ("network", "notebook", 16): 16.7,
+    ("network", "notebook", 17): 37.2, ("network", "notebook", 1000): 134,
+    ("network", "wide", 1): 8.42, ("network", "wide", 15): 3.3, ("network", "wide", 16): 2.33,
+    ("network", "wide", 17): 3.2, ("network", "wide", 1000): 1.16,
+    ("network", "one", 1): 1.75, ("network", "one", 15): 0.296, ("network", "one", 16): 0.0806,
+    ("network", "one", 17): 0.58, ("network", "one", 1000): 0.13,
+    ("network", "ragged", 1): 2.81, ("network", "ragged", 15): 4.31, ("network", "ragged", 16): 2.23,
+    ("network", "ragged", 17): 2.37, ("network", "ragged", 1000): 1.23,
+    # 2 x 256 CUs x 256 + 77 points (the batch above the grid-stride bound on an MI355X)
+    ("network", "notebook", 131149): 36.0, ("network", "wide", 131149): 0.105, ("network", "one", 131149): 0.0136,
+    ("network", "ragged", 131149): 0.62,
+    ("table", "1d"): 0.317, ("table", "1d-project"): 0.319, ("table", "1d-two"): 0.554, ("table", "2d"): 1.14,
+    ("table", "2d-project"): 0.74, ("table", "2d-two"): 1.03,
+    ("steps-notebook", 0): 2.95, ("steps-notebook", 1): 1.1, ("steps-notebook", 2): 0.639,
+    ("steps-notebook", 3): 0.285, ("steps-notebook", 4): 3.73}
+# one figure per gradient step of the 10 x 5 loop of tests/test_rl.py:29-77
+LQR_STEP_RATIOS = [
+    0.296, 0.117, 0.483, 0.168, 0.134, 0.37, 0.15, 0.158, 0.21, 0.349, 0.14, 0.296, 0.255, 0.32, 0.143, 0.152,
+    0.202, 0.333, 0.248, 0.145, 0.526, 0.241, 0.173, 0.2, 0.359, 0.272, 0.353, 0.203, 0.327, 0.259, 0.132, 0.176,
+    0.179, 0.205, 0.322, 0.508, 0.402, 0.539, 0.512, 0.569, 0.562, 0.522, 0.705, 0.61, 0.571, 0.186, 0.129, 0.204,
+    0.24, 0.213]
+REFERENCE_RATIO.update({("steps-lqr", k): v for k, v in enumerate(LQR_STEP_RATIOS)})
+
+
+def measure_reference_ratio(key):
+    kind = key[0]
+    if kind == "action":
+        _, name, explicit = key
+        orl, _ = system_pair(name)
+        states, actions = system_states(name, ACTION_RATIO_POINTS)
+        u64 = actions if explicit else policy_actions(orl.policy, states)
+        ok = comparable(orl, states, u64)
+        t64 = action_gradient(orl, states, u64)
+        u80 = actions if explicit else policy_actions(orl.policy, states, LONG)
+        t80 = action_gradient(orl, states, u80, LONG)
+        return ratio_to_companion(t64["grad"], t80["grad"], t64["A"], ok)
+    if kind == "network":
+        _, name, n = key
+        onet, _ = make_network(name)
+        points, coeff = make_batch(name, n)
+        g64, comp = network_parameter_gradient(onet, points, coeff)
+        g80, _ = network_parameter_gradient(onet, points, coeff, LONG)
+        return ratio_to_companion(g64, g80, comp)
+    if kind == "table":
+        tri, points, coeff = table_case(key[1])
+        g64, comp = table_parameter_gradient(tri, points, coeff)
+        g80, _ = table_parameter_gradient(tri, points, coeff, LONG)
+        return ratio_to_companion(g64, g80, comp)
+    if kind in ("steps-lqr", "steps-notebook"):
+        return measure_step_ratios(kind)[key[1]]
+    raise KeyError(key)
+
+
+def reference_ratio(key):
+    if key not in REFERENCE_RATIO:
+        REFERENCE_RATIO[key] = measure_reference_ratio(key)
+    return REFERENCE_RATIO[key]
+
+
+def tolerance(*key):
+    """32 times the reference's own measured error on that batch: room for another summation order, the
+    device's exp and tanh a few ulp off where libm is within one, and fused operations in the kernel values."""
+    return 32.0 * reference_ratio(tuple(key)) * 2.0 ** -53
+
+
+TABLES = {
+    # key: (limits, num_points, columns, project)
+    "1d": ([[-1., 1.]], 5, 1, False), "1d-project": ([[-1., 1.]], 5, 1, True),
+    "1d-two": ([[-1., 1.]], 5, 2, True),
+    "2d": ([[-1., 1.], [-0.5, 2.0]], [7, 6], 1, False), "2d-project": ([[-1., 1.], [-0.5, 2.0]], [7, 6], 1, True),
+    "2d-two": ([[-1., 1.], [-0.5, 2.0]], [7, 6], 2, True),
+}
+
+
+def table_case(key, sl=None, n=200):
+    """-> (oracle Triangulation or (oracle, product), points, coefficients): points inside, on vertices and
+    outside the grid."""
+    limits, num, cols, project = TABLES[key]
+    grid = oracle.GridWorld(limits, num)
+    rng = np.random.default_rng(len(key) + 5)
+    values = rng.normal(size=(grid.nindex, cols))
+    tri = oracle.Triangulation(grid, values, project=project)
+    lim = np.asarray(limits)
+    span = lim[:, 1] - lim[:, 0]
+    import exclusions
+    unit = rng.uniform(-0.15, 1.15, (n, len(limits)))
+    # outside the grid in one coordinate at a time: beyond a corner of the grid the clipped unit-cell
+    # coordinates sit on a shared face and the simplices there extrapolate differently (tests/exclusions.py)
+    outside = (unit < 0) | (unit > 1)
+    for k in range(1, len(limits)):
+        redo = outside[:, :k].any(axis=1) & outside[:, k]
+        unit[redo, k] = rng.uniform(0.05, 0.95, int(redo.sum()))
+    points = lim[:, 0] + span * unit
+    # the vertices themselves - those the reference locates unambiguously (a vertex whose coordinate is not
+    # a whole multiple of the spacing in floating point wraps into the wrong corner of the unit cell)
+    vertices = grid.all_points
+    vertices = vertices[~exclusions.ambiguous_points(tri, vertices)]
+    points[:len(vertices)] = vertices
+    coeff = rng.normal(size=(n, cols))
+    coeff[::7] = 0.0
+    keep = ~exclusions.ambiguous_points(tri, points)
+    assert 1.0 - keep.mean() <= MAX_EXCLUDED
+    points, coeff = points[keep], coeff[keep]
+    if sl is None:
+        return tri, points, coeff
+    sgrid = sl.GridWorld(limits, num)
+    return (tri, sl.Triangulation(sgrid, values.copy(), project=project)), points, coeff
+
+
+# ---- the two step loops of the tests ------------------------------
+LQR_LOOP = dict(outer=10, inner=5, learning_rate=0.01, reduction='sum')          # tests/test_rl.py:29-77
+NOTEBOOK_LOOP = dict(steps=5, learning_rate=0.1, reduction='mean', states=1000)   # inverted_pendulum.ipynb cells 9/12
+
+
+def notebook_states(orl):
+    """The sampled states of the notebook-shape test: system_states('pendulum', 1000) without the points whose
+    derivative jumps nearby at the initial parameters (at most MAX_EXCLUDED of them)."""
+    states, _ = system_states("pendulum", NOTEBOOK_LOOP["states"])
+    ok = comparable(orl, states, policy_actions(orl.policy, states), through_policy=True)
+    assert 1.0 - ok.mean() <= MAX_EXCLUDED
+    return states[ok]
+
+
+def measure_step_ratios(kind):
+    """float64 against long double on the gradient of every step of the reference's own run."""
+    ratios = []
+    if kind == "steps-lqr":
+        orl, _ = lqr_pair(value_sweeps=0)
+        for _ in range(LQR_LOOP["outer"]):
+            orl.value_iteration()
+            for _ in range(LQR_LOOP["inner"]):
+                _, g64, comp = policy_gradient(orl, None, LQR_LOOP["reduction"])
+                _, g80, _ = policy_gradient(orl, None, LQR_LOOP["reduction"], LONG)
+                ratios.append(ratio_to_companion(g64, g80, comp))
+                policy_improvement_step(orl, None, LQR_LOOP["learning_rate"], LQR_LOOP["reduction"])
+    else:
+        orl, _ = system_pair("pendulum")
+        states = notebook_states(orl)
+        for _ in range(NOTEBOOK_LOOP["steps"]):
+            _, g64, comp = policy_gradient(orl, states, NOTEBOOK_LOOP["reduction"])
+            _, g80, _ = policy_gradient(orl, states, NOTEBOOK_LOOP["reduction"], LONG)
+            ratios.append(ratio_to_companion(g64, g80, comp))
+            policy_improvement_step(orl, states, NOTEBOOK_LOOP["learning_rate"], NOTEBOOK_LOOP["reduction"])
+    return ratios

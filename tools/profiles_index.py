@@ -132,6 +132,10 @@ def main():
              "* `lyapunov_training.md`: training a LyapunovNetwork (`k_nn_loss`, `k_nn_param_grad`, csrc/sl_nn.hip): registers / LDS, "
              "the tolerance of the gradient comparisons and what it was measured from, one gradient against torch autograd "
              "(`tools/lyapunov_training_probe.py`).",
+             "* `policy_training.md`: policy gradients of `future_values` (`k_action_gradient`, `k_policy_param_grad`, `k_tri_pg_*`, "
+             "csrc/sl_policy_grad.hip): registers / LDS, the measured ratios of the GPU tests against their tolerances, a "
+             "policy-improvement step at the notebook's shape and `sl_action_gradient` on a 64^4 grid beside an uncached "
+             "policy-evaluation sweep (`tools/policy_training_probe.py`).",
              "* `gp_posterior_truth.md`: the GP posterior of `k_gp_sweep4`, `k_gp_sweep` and `k_gp_small` against the posterior in "
              "extended precision (`tests/np_gp_truth.py`): per case cond(K), the oracle's own error, a NumPy restatement of the "
              "engine's formula and the engine's measured error (`tests/test_gpu_gp_truth.py`; DESIGN.md 6 (iv)).",
