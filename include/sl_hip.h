@@ -681,6 +681,24 @@ SL_API int  sl_policy_param_grad(sl_ctx* ctx, int64_t n, int d, const double* d_
 SL_API int  sl_tri_param_grad(sl_ctx* ctx, int slot, int64_t n, const double* d_points, const double* d_coeff,
                     double* d_grad);
 
+/* ---- the Lyapunov penalty of future_values, differentiated (reinforcement_learning.py:107-112; the
+ * rl.future_values(tf_states, lyapunov=lyapunov) of examples/inverted_pendulum.ipynb cell 17).  Under the model
+ * of sl_model_set of a LYAPUNOV context (policy, GP dynamics, Lyapunov function, L_v, L_f, tau), with z = [x, u]:
+ *   C(x, u) = V_L(mu) - V_L(x) + sum_k L_k(mu) e_k + |L(x)|_1 (1 + L_f(x)) tau,   e_k = beta sqrt(var_h(z))
+ *   dC/du_a = sum_j [g_j(mu) + sum_k dL_k/dmu_j(mu) e_k] dmu_j/du_a + sum_k L_k(mu) beta dvar_h/du_a / (2 sqrt(var_h))
+ *   dvar_h/du_a = dk(z, z)/du_a - 2 a^T b_a,   a = L^-1 k_x,  b_a = L^-1 dk_x/du_a
+ * d_grad [n][m] = dC/du at the points d_points [n][d] (NULL: the first n grid points) and the actions d_actions
+ * [n][m] (NULL: u = policy(x), evaluated once); d_constraint [n] (may be NULL) = C; d_terms [n][2 + 2 d] (may be
+ * NULL) = the record of SL_EVAL_DECREASE: decrease bound, threshold (-|L(x)|_1 (1 + L_f) tau), mean, error.
+ * g = grad V_L: (P + P^T) mu for a quadratic, the simplex gradient for a table (negated with it, masked per
+ * coordinate where the table projects); dL/dmu: sign(.) G for the two linear kinds (sign(0) = 0), 0 for a
+ * constant and for the gradient kinds over a table.  sqrt(var) is not clamped.  The triangular products run on
+ * the matrix cores from the A fragments the heads hold, in batches through context scratch; no atomics, the
+ * same bits at every call and for every split of the points over calls.
+ * SL_DYN_GP only: the Euler and the linear dynamics, and SL_V_NETWORK, return SL_ERR_UNSUPPORTED. */
+SL_API int  sl_decrease_gradient(sl_ctx* ctx, int64_t n, const double* d_points, const double* d_actions,
+                    double* d_grad, double* d_constraint, double* d_terms);
+
 /* ---- multi-GPU collectives directly on RCCL ----------------------------- *
  * For callers without torch.distributed (the Python package issues the same exchanges through
  * torch.distributed, backend "nccl" = RCCL).  One communicator per context, one rank per GPU; every

@@ -214,6 +214,8 @@ SIGNATURES = {
     "sl_action_gradient": (_int, (_vp, _i64, _vp, _vp, _vp, _vp, _vp)),
     "sl_policy_param_grad": (_int, (_vp, _i64, _int, _vp, _vp, _vp)),
     "sl_tri_param_grad": (_int, (_vp, _int, _i64, _vp, _vp, _vp)),
+    # the Lyapunov penalty of future_values, differentiated
+    "sl_decrease_gradient": (_int, (_vp, _i64, _vp, _vp, _vp, _vp, _vp)),
     # RCCL collectives
     "sl_comm_unique_id": (_int, (C.c_char_p,)),
     "sl_comm_init": (_int, (_vp, C.c_char_p, _int, _int)),
@@ -676,6 +678,12 @@ class Context(object):
     def tri_param_grad(self, slot, n, d_points, d_coeff, d_grad):
         """``sl_tri_param_grad``: the same sum for the vertex table of slot ``slot`` -> ``[nindex, cols]``."""
         self.lib.sl_tri_param_grad(self.handle, int(slot), int(n), _ptr(d_points), _ptr(d_coeff), _ptr(d_grad))
+
+    def decrease_gradient(self, n, d_points, d_actions, d_grad, d_constraint=None, d_terms=None):
+        """``sl_decrease_gradient``: ``dC/du`` of the Lyapunov constraint ``C = decrease bound - threshold``
+        at ``n`` points under the uploaded model (``d_actions=None``: the policy's actions)."""
+        self.lib.sl_decrease_gradient(self.handle, int(n), _ptr(d_points), _ptr(d_actions), _ptr(d_grad),
+                                      _ptr(d_constraint), _ptr(d_terms))
 
     def nn_train_scratch(self):
         """``sl_debug_nn_train_scratch`` -> (bytes of the scratch area, its guard zones are intact)."""

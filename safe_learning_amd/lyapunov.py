@@ -330,6 +330,50 @@ class Lyapunov(object):
         v_dot, v_dot_error = self.v_decrease_confidence(states, next_states)
         return v_dot + v_dot_error
 
+    def decrease_gradient(self, states, actions=None):
+        """``(dC/du [n, m], C [n, 1])`` of the constraint ``C = v_decrease_bound - threshold`` that
+        ``PolicyIteration.future_values(..., lyapunov=self)`` penalises (``reinforcement_learning.py:107-112``),
+        at ``states`` and ``actions`` (one row, or one per state; ``None``: ``self.policy(states)``), on the
+        GPU (``sl_decrease_gradient``): the derivative runs through the posterior mean (``grad V_L`` and
+        the derivative of ``L_v``) and through the error bound ``beta sqrt(var)``.  Device tensors in,
+        device tensors out; NumPy otherwise.  GP dynamics (``GaussianProcess`` / ``FunctionStack``), a
+        quadratic or table Lyapunov function; the threshold depends on the states only.  A
+        ``LyapunovNetwork`` is not differentiated."""
+        import torch
+        from . import _evaluate
+        from .functions import CartPole, InvertedPendulum, LyapunovNetwork, UncertainFunction
+        if isinstance(self.lyapunov_function, LyapunovNetwork):
+            raise TypeError('the gradient of the Lyapunov penalty is implemented for a quadratic or table '
+                            'Lyapunov function, not for a LyapunovNetwork')
+        if isinstance(self.dynamics, (InvertedPendulum, CartPole)) or not isinstance(self.dynamics, UncertainFunction):
+            raise TypeError('the gradient of the Lyapunov penalty needs uncertain GP dynamics (mean, error), '
+                            'not %s' % type(self.dynamics).__name__)
+        keep = isinstance(states, torch.Tensor)
+        ctx = self._ctx
+        d_states = _evaluate._to_device(ctx, states)
+        n, d = d_states.shape
+        if d != self.discretization.ndim:
+            raise ValueError('states of %d columns, the state space has %d dimensions'
+                             % (d, self.discretization.ndim))
+        if isinstance(self.policy, (np.ndarray, torch.Tensor)):        # a per-vertex action table
+            m = int(self.policy.reshape(self.discretization.nindex, -1).shape[1])
+        else:
+            m = _evaluate._policy_output_dim(self.policy)
+        d_actions = None
+        if actions is not None:
+            if not isinstance(actions, torch.Tensor):
+                actions = np.atleast_2d(np.asarray(actions, dtype=np.float64))
+            d_actions = _evaluate._to_device(ctx, actions)
+            if d_actions.shape[0] not in (1, n) or d_actions.shape[1] != m:
+                raise ValueError('actions must be [1, %d] or [%d, %d], got %s'
+                                 % (m, n, m, tuple(d_actions.shape)))
+            d_actions = d_actions.expand(n, m).contiguous()
+        self._upload_model()
+        grad = torch.empty((n, m), dtype=torch.float64, device=ctx.torch_device)
+        constraint = torch.empty((n, 1), dtype=torch.float64, device=ctx.torch_device)
+        ctx.decrease_gradient(n, d_states, d_actions, grad, constraint)
+        return (grad, constraint) if keep else (grad.cpu().numpy(), constraint.cpu().numpy())
+
     @property
     def values(self):
         """V at every grid point, ``float64[nindex]`` (``lyapunov.py:305-322``).

@@ -211,24 +211,80 @@ class PolicyIteration(object):
         ctx.action_gradient(n, d_states, d_actions, grad, q)
         return d_states, grad, q
 
-    def action_gradient(self, states=None, policy=None, actions=None, lyapunov=None):
+    def _penalised_gradient_device(self, states, policy, actions, lyapunov, lagrange_multiplier):
+        """The safe objective ``Q - lambda C`` and its action derivative -> device tensors (states [n, d],
+        ``dQ/du - lambda dC/du`` [n, m], ``Q - lambda C`` [n]).  The actions are evaluated ONCE and go as
+        explicit actions to ``sl_action_gradient`` and to ``lyapunov.decrease_gradient``; the two
+        results are combined on the device.  ``lagrange_multiplier = 0``: the penalty is evaluated and
+        left out (the unpenalised numbers bit for bit)."""
+        import torch
+        from . import _evaluate
+        from .functions import UncertainFunction
+        from .lyapunov import Lyapunov
+        if not isinstance(lyapunov, Lyapunov):
+            raise NotImplementedError('the gradient of the Lyapunov penalty is implemented for a Lyapunov '
+                                      'instance of this package, not for %s' % type(lyapunov).__name__)
+        if lyapunov.dynamics is not self.dynamics:
+            raise ValueError('the Lyapunov penalty is differentiated under ONE dynamics model: '
+                             'lyapunov.dynamics must be the dynamics object of this PolicyIteration')
+        if not isinstance(self.dynamics, UncertainFunction):
+            raise TypeError('the Lyapunov penalty needs uncertain dynamics (mean, error): the '
+                            'reference reads the error bound of the GP (:97-108)')
+        ctx = self._ctx
+        if states is None or states is self.state_space:
+            dev = ctx.torch_device
+            if getattr(self, '_state_space_dev', None) is None or self._state_space_dev.device != dev:
+                self._state_space_dev = torch.from_numpy(np.ascontiguousarray(self.state_space)).to(dev)
+            d_states = self._state_space_dev
+        else:
+            d_states = _evaluate._to_device(ctx, states)
+        n = d_states.shape[0]
+        if actions is None:
+            chosen = self.policy if policy is None else policy
+            if isinstance(chosen, (np.ndarray, torch.Tensor)):
+                raise TypeError('a per-vertex action table is not a policy of the states: pass it as `actions`')
+            d_actions = _evaluate.policy(chosen, d_states)
+        else:
+            if not isinstance(actions, torch.Tensor):
+                actions = np.atleast_2d(np.asarray(actions, dtype=np.float64))
+            d_actions = _evaluate._to_device(ctx, actions)
+            if d_actions.shape[0] not in (1, n):
+                raise ValueError('actions must be one row or one row per state (%d), got %d'
+                                 % (n, d_actions.shape[0]))
+        d_actions = d_actions.expand(n, d_actions.shape[1]).contiguous()
+        d_states, grad, q = self._action_gradient_device(d_states, None, d_actions)
+        d_grad_c, d_c = lyapunov.decrease_gradient(d_states, d_actions)
+        rate = float(lagrange_multiplier)
+        if rate != 0.0:
+            grad = grad - rate * d_grad_c
+            q = q - rate * d_c.reshape(-1)
+        return d_states, grad, q
+
+    def action_gradient(self, states=None, policy=None, actions=None, lyapunov=None, lagrange_multiplier=1.):
         """``d future_values / d action`` -> ``[n, m]``: the derivative of ``r(x, u) + gamma V(f(x, u))``
         (``:65-104``, the dynamics mean for a GP) with respect to ``u`` at ``u = policy(states)``
         (default: ``self.policy``) or at the given ``actions`` (one row, or one per state), on the GPU
         (``sl_action_gradient``).  ``states=None``: the grid's vertices.  Device tensors in, a device
         tensor out; NumPy otherwise.  The value table's simplex gradient is taken at the successor,
         and with ``project=True`` only the coordinates inside the table's limits count (TensorFlow's
-        gradient of the clip, ``functions.py:1485``).  LinearSystem and GP dynamics; the Lyapunov
-        penalty (``lyapunov=``) is not differentiated yet."""
+        gradient of the clip, ``functions.py:1485``).  LinearSystem and GP dynamics.
+
+        With ``lyapunov=`` (a ``Lyapunov`` whose ``dynamics`` is this object's, a GP model) the
+        Lyapunov decrease enters as a soft constraint (``:107-112``): the result is ``dQ/du - lambda
+        dC/du`` with ``C = v_decrease_bound - threshold`` and ``lambda = lagrange_multiplier``
+        (``Lyapunov.decrease_gradient``, ``sl_decrease_gradient``).  Not differentiated: a
+        ``LyapunovNetwork`` as the Lyapunov function, and the dependence of the threshold on the policy's
+        parameters through a ``lipschitz_dynamics`` callable that reads ``policy.lipschitz()`` (here
+        ``L_f`` is a number or ``c + ||M x||_1``)."""
         import torch
-        if lyapunov is not None:
-            raise NotImplementedError('the gradient of the Lyapunov penalty (the derivative of beta sqrt(var) '
-                                      'and of L_v) is not implemented: differentiate without lyapunov=')
         keep = isinstance(states, torch.Tensor)
+        if lyapunov is not None:
+            _, grad, _ = self._penalised_gradient_device(states, policy, actions, lyapunov, lagrange_multiplier)
+            return grad if keep else grad.cpu().numpy()
         _, grad, _ = self._action_gradient_device(states, policy, actions)
         return grad if keep else grad.cpu().numpy()
 
-    def policy_gradient(self, states=None, reduction='mean', lyapunov=None):
+    def policy_gradient(self, states=None, reduction='mean', lyapunov=None, lagrange_multiplier=1.):
         """``(objective, gradient)`` of ``J(theta) = reduce_i future_values(x_i)`` under
         ``self.policy`` with respect to its parameters: ``objective`` is ``J`` at the current
         parameters, ``gradient`` is shaped like ``policy.parameters`` - the gradient
@@ -237,10 +293,16 @@ class PolicyIteration(object):
         ``tests/test_rl.py:59``, ``'sum'``).  One ``sl_action_gradient`` call, its result scaled by
         ``1/n`` for ``'mean'``, then the policy's ``parameter_gradient`` on the device tensors: the
         batch never visits the host.  ``policy`` must be a bare ``NeuralNetwork`` or
-        ``Triangulation``.  Single process only."""
+        ``Triangulation``.  Single process only.
+
+        With ``lyapunov=`` the objective is ``reduce_i future_values(x_i, lyapunov=lyapunov,
+        lagrange_multiplier=...)`` - the safe policy update of ``examples/inverted_pendulum.ipynb``
+        cell 17 - see ``action_gradient`` for what is differentiated and what is not."""
         if lyapunov is not None:
-            raise NotImplementedError('the gradient of the Lyapunov penalty (the derivative of beta sqrt(var) '
-                                      'and of L_v) is not implemented: differentiate without lyapunov=')
+            from .lyapunov import Lyapunov
+            if not isinstance(lyapunov, Lyapunov):
+                raise NotImplementedError('the gradient of the Lyapunov penalty is implemented for a Lyapunov '
+                                          'instance of this package, not for %s' % type(lyapunov).__name__)
         if reduction not in ('mean', 'sum'):
             raise ValueError("reduction must be 'mean' or 'sum', got %r" % (reduction,))
         if self._world > 1:
@@ -251,7 +313,10 @@ class PolicyIteration(object):
             raise TypeError('policy_gradient differentiates a bare NeuralNetwork or Triangulation policy, '
                             'not %s' % (('a negated ' if getattr(policy, 'negate', False) else '')
                                         + type(policy).__name__))
-        d_states, grad, q = self._action_gradient_device(states, None, None)
+        if lyapunov is not None:
+            d_states, grad, q = self._penalised_gradient_device(states, None, None, lyapunov, lagrange_multiplier)
+        else:
+            d_states, grad, q = self._action_gradient_device(states, None, None)
         if reduction == 'mean':
             n = d_states.shape[0]
             grad = grad * (1.0 / n)

@@ -124,7 +124,7 @@ def roa_classification_step(lyapunov, states, roa_labels, class_weights, safe_le
     return dict(objective=objective, classifier_loss=classifier, decrease_loss=decrease)
 
 
-def policy_improvement_step(rl, states, learning_rate, reduction='mean'):
+def policy_improvement_step(rl, states, learning_rate, reduction='mean', lyapunov=None, lagrange_multiplier=1.):
     """One gradient step of the policy-improvement half of policy iteration on ``rl.policy`` (a bare
     ``NeuralNetwork`` or ``Triangulation``): ``theta <- theta + learning_rate * dJ/dtheta`` with
     ``J = reduce_i rl.future_values(states_i)`` - plain gradient descent on ``-J``, the
@@ -133,12 +133,24 @@ def policy_improvement_step(rl, states, learning_rate, reduction='mean'):
     ``tests/test_rl.py:59`` (``'sum'``).  Returns the objective ``J`` BEFORE the step;
     ``learning_rate=None`` evaluates it only.  ``states=None``: the grid's vertices.
 
-    The gradient comes from ``rl.policy_gradient`` (``sl_action_gradient`` and the policy's
-    ``parameter_gradient`` on the GPU); the update is assigned to ``policy.parameters`` on the host,
+    With ``lyapunov=`` the step is the SAFE policy update of the notebook's cell 17, run 200 at a time by
+    its cells 21/22: ``J = reduce_i rl.future_values(states_i, lyapunov=lyapunov,
+    lagrange_multiplier=lagrange_multiplier)``, the Lyapunov decrease as a soft constraint.  Out of
+    scope: a ``LyapunovNetwork`` as the Lyapunov function, the dependence of the threshold on the
+    policy's parameters through ``policy.lipschitz()`` inside a ``lipschitz_dynamics`` callable (the
+    notebook's TensorFlow graph differentiates it; here ``L_f`` is a number or ``c + ||M x||_1``),
+    optimisers other than plain gradient descent, and more than one rank.
+
+    The gradient comes from ``rl.policy_gradient`` (``sl_action_gradient``, ``sl_decrease_gradient`` and the
+    policy's ``parameter_gradient`` on the GPU); the update is assigned to ``policy.parameters`` on the host,
     where the master copy lives: sweeps, ``value_iteration``, the successor cache and ``Lyapunov``
     objects that share the policy notice the edit through its version token."""
     _check_single_process()
-    objective, gradient = rl.policy_gradient(states, reduction)
+    if lyapunov is None:
+        objective, gradient = rl.policy_gradient(states, reduction)
+    else:
+        objective, gradient = rl.policy_gradient(states, reduction, lyapunov=lyapunov,
+                                                 lagrange_multiplier=lagrange_multiplier)
     if learning_rate is not None:
         policy, rate = rl.policy, float(learning_rate)
         if isinstance(gradient, list):

@@ -136,6 +136,11 @@ def main():
              "csrc/sl_policy_grad.hip): registers / LDS, the measured ratios of the GPU tests against their tolerances, a "
              "policy-improvement step at the notebook's shape and `sl_action_gradient` on a 64^4 grid beside an uncached "
              "policy-evaluation sweep (`tools/policy_training_probe.py`).",
+             "* `safe_policy_training.md`: the Lyapunov penalty of `future_values`, differentiated (`k_sg_generate`, `k_sg_gemm`, "
+             "`k_sg_epilogue`, csrc/sl_safe_grad.hip): registers / LDS / scratch, the measured ratios of the GPU tests against "
+             "their tolerances, a safe policy-improvement step at the notebook's shape beside the unpenalised one and "
+             "`sl_decrease_gradient` under a 1024-point RBF head against the FP64 matrix peak (`tools/safe_policy_probe.py`; "
+             "DESIGN.md 4.5c).",
              "* `gp_posterior_truth.md`: the GP posterior of `k_gp_sweep4`, `k_gp_sweep` and `k_gp_small` against the posterior in "
              "extended precision (`tests/np_gp_truth.py`): per case cond(K), the oracle's own error, a NumPy restatement of the "
              "engine's formula and the engine's measured error (`tests/test_gpu_gp_truth.py`; DESIGN.md 6 (iv)).",
