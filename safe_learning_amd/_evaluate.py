@@ -36,6 +36,30 @@ def _to_device(ctx, array):
     return torch.from_numpy(np.ascontiguousarray(array)).to(ctx.torch_device)
 
 
+def _points_and_coefficients(ctx, points, coefficients, input_dim, what):
+    """The arguments of a ``parameter_gradient`` as device tensors: ``points`` ``[n, input_dim]`` (``what`` names
+    the function in the refusal), ``coefficients`` with a row per entry of their first axis (the caller checks it)."""
+    import torch
+    d_points = _to_device(ctx, points)
+    if d_points.shape[1] != input_dim:
+        raise ValueError('the %s expects %d inputs, the points have %d columns' % (what, input_dim, d_points.shape[1]))
+    if not isinstance(coefficients, torch.Tensor):
+        coefficients = np.asarray(coefficients, dtype=np.float64)
+        coefficients = coefficients.reshape(max(len(np.atleast_1d(coefficients)), 1), -1)
+    return d_points, _to_device(ctx, coefficients)
+
+
+def _action_rows(ctx, actions, n):
+    """Explicit actions (one row, or one per state) as a contiguous ``[n, m]`` device tensor;
+    ``None`` (evaluate the policy) stays ``None``."""
+    if actions is None:
+        return None
+    d_actions = _to_device(ctx, actions)
+    if d_actions.shape[0] not in (1, n):
+        raise ValueError('actions must be one row or one row per state (%d), got %d' % (n, d_actions.shape[0]))
+    return d_actions.expand(n, d_actions.shape[1]).contiguous()
+
+
 def _on_device(x):
     """Inputs given as device tensors keep the results on the device (no host round trip)."""
     import torch

@@ -5,7 +5,7 @@
 // error) of GP dynamics comes from a first pass of k_gp_sweep that only emits its per-cell
 // records; deterministic dynamics are evaluated here.  Below them: the training step of
 // examples/lyapunov_function_learning.ipynb (k_nn_loss, k_nn_param_grad).
-#include "sl_common.h"
+#include "sl_grad_host.h"
 #include "sl_nn_train.h"
 
 __device__ __forceinline__ void nn_lv_from_grad(int kind, int d, const double* g, double* lv) {
@@ -298,7 +298,7 @@ int sl_nn_check_launch(sl_ctx* ctx, const SlSweepArgs& a, const double* d_record
 // instead of standing 4 x 16 tiles beside each wavefront's activations, and one staging tile
 // (33 KB) rather than two keeps the largest network (four layers of 64: 108 KB of weights) inside
 // the 160 KB of a CU.  No atomics: a workgroup writes its G to its own slice of the context's
-// scratch buffer and k_nn_grad_reduce adds the slices in ascending order.
+// scratch buffer and sl_sum_slices adds the slices in ascending order.
 // (The two chains are written out again here and not shared with nn_mfma_eval as helpers: with helpers
 // the register allocation of the sweeps' kernels changes - k_nn_values_mfma<2..4> go from 121 - 125
 // VGPRs without scratch to 256 with it; profiles/lyapunov_training.md.)
@@ -470,16 +470,6 @@ __global__ __launch_bounds__(64 * SL_NNG_WAVES) void k_nn_param_grad(SlAux aux, 
             }
         }
     }
-}
-
-// out[e] = partials[0][e] + partials[1][e] + ... in that order: the same bits at every call
-__global__ __launch_bounds__(SL_BLOCK) void k_nn_grad_reduce(const double* __restrict__ partials, int nblocks,
-                                                             int total, double* __restrict__ out) {
-    const int e = blockIdx.x * SL_BLOCK + threadIdx.x;
-    if (e >= total) return;
-    double s = 0.0;
-    for (int b = 0; b < nblocks; ++b) s = s + partials[(size_t)b * total + e];
-    out[e] = s;
 }
 
 // The losses: V(x) (and V(x+)) of 16 samples per wavefront on the matrix cores, the per-sample terms
@@ -655,10 +645,7 @@ extern "C" int sl_nn_param_grad(sl_ctx* ctx, int64_t m, int d, const double* d_p
         return SL_OK;
     });
     if (rc) return rc;
-    hipLaunchKernelGGL(k_nn_grad_reduce, dim3((total + SL_BLOCK - 1) / SL_BLOCK), dim3(SL_BLOCK), 0, ctx->stream,
-                       partials, (int)blocks, total, d_grad_kernels);
-    SL_HIP_CHECK(ctx, hipGetLastError());
-    return SL_OK;
+    return sl_sum_slices(ctx, partials, (int)blocks, total, d_grad_kernels);
 }
 
 extern "C" int sl_nn_loss(sl_ctx* ctx, int kind, int64_t m, int d, const double* d_states, const double* d_next,

@@ -8,7 +8,7 @@
 //   sl_tri_param_grad      the same sum for the vertex table of a Triangulation policy
 //
 // Nothing here uses floating-point atomics: two calls with the same inputs return the same bits.
-#include "sl_common.h"
+#include "sl_grad_host.h"
 #include "sl_policy_grad.h"
 
 // =============================================================================================
@@ -82,9 +82,8 @@ __global__ __launch_bounds__(SL_BLOCK) void k_action_gradient(const SlDevModel M
 
 extern "C" int sl_action_gradient(sl_ctx* ctx, int64_t n, const double* d_points, const double* d_actions,
                                   double* d_grad, double* d_q, double* d_next) {
-    if (!ctx) return sl_fail(nullptr, SL_ERR_INVALID, "sl_action_gradient: NULL context");
-    if (!ctx->model_set) return sl_fail(ctx, SL_ERR_INVALID, "sl_action_gradient: call sl_model_set first");
-    if (n < 0 || !d_grad) return sl_fail(ctx, SL_ERR_INVALID, "sl_action_gradient: bad argument");
+    const char* who = "sl_action_gradient";
+    if (const int rc = sl_point_grad_arguments(ctx, who, n, d_grad)) return rc;
     const sl_model_desc& md = ctx->h_model.m;
     if (md.dynamics.kind != SL_DYN_LINEAR && md.dynamics.kind != SL_DYN_GP)
         return sl_fail(ctx, SL_ERR_UNSUPPORTED, "sl_action_gradient: dynamics kind %d; the action gradient is "
@@ -96,24 +95,13 @@ extern "C" int sl_action_gradient(sl_ctx* ctx, int64_t n, const double* d_points
     if (ctx->h_tri[0].grid.d != md.grid.d)
         return sl_fail(ctx, SL_ERR_INVALID, "sl_action_gradient: value table of %d dimensions, states of %d",
                        ctx->h_tri[0].grid.d, md.grid.d);
-    if (md.dynamics.kind == SL_DYN_GP && ctx->h_gp.nheads < 1)
-        return sl_fail(ctx, SL_ERR_INVALID, "sl_action_gradient: GP dynamics without heads (sl_gp_configure)");
-    if (!d_points && n > ctx->h_model.gf.nindex)
-        return sl_fail(ctx, SL_ERR_INVALID, "sl_action_gradient: %lld points on a grid of %lld", (long long)n,
-                       (long long)ctx->h_model.gf.nindex);
+    if (const int rc = sl_point_grad_gp_heads(ctx, who)) return rc;
+    if (const int rc = sl_point_grad_on_grid(ctx, who, n, d_points)) return rc;
     if (n == 0) return SL_OK;
     SL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     // a network policy: one action per point first, as everywhere else
     SlPolicyTableScope network_policy(ctx, 0, d_actions ? 0 : n, d_points);
-    if (network_policy.rc) return network_policy.rc;
-    if (!d_actions) {
-        const int kind = ctx->h_model.m.policy.kind;
-        if (kind == SL_POLICY_TRI && !ctx->h_tri[1].set)
-            return sl_fail(ctx, SL_ERR_INVALID, "sl_action_gradient: policy table not set");
-        if (kind == SL_POLICY_TABLE && d_points && !network_policy.swapped)
-            return sl_fail(ctx, SL_ERR_UNSUPPORTED, "sl_action_gradient: a per-vertex policy table cannot be "
-                                                    "evaluated at arbitrary points");
-    }
+    if (const int rc = sl_point_grad_policy(ctx, who, d_points, d_actions, network_policy)) return rc;
     int64_t blocks = (n + SL_BLOCK - 1) / SL_BLOCK;
     const int64_t cap = 2 * (int64_t)ctx->num_cu;
     if (blocks > cap) blocks = cap;
@@ -148,7 +136,7 @@ extern "C" int sl_action_gradient(sl_ctx* ctx, int64_t n, const double* d_points
 // dimension.  The accumulator tiles (4 per layer and wavefront) stay in registers for the whole
 // grid-stride loop.  Bias gradients: thread o < out adds column o of the delta tile, points ascending.
 // A point past n enters with coefficient 0.  No atomics: a workgroup writes its sums to its own slice of
-// the context's scratch and k_pg_reduce adds the slices in ascending order.
+// the context's scratch and sl_sum_slices adds the slices in ascending order.
 #define SL_PPG_WAVES 4
 #define SL_PPG_POINTS (64 * SL_PPG_WAVES)
 #define SL_PPG_STRIDE (SL_NN_MAXW + 2)          // staging row of one point (+2: LDS bank spread)
@@ -275,13 +263,20 @@ __global__ __launch_bounds__(SL_PPG_POINTS) void k_policy_param_grad(const SlPol
 }
 
 // out[e] = partials[0][e] + partials[1][e] + ... in that order: the same bits at every call
-__global__ __launch_bounds__(SL_BLOCK) void k_pg_reduce(const double* __restrict__ partials, int nblocks, int total,
-                                                        double* __restrict__ out) {
+__global__ __launch_bounds__(SL_BLOCK) void k_sum_slices(const double* __restrict__ partials, int nblocks, int total,
+                                                         double* __restrict__ out) {
     const int e = blockIdx.x * SL_BLOCK + threadIdx.x;
     if (e >= total) return;
     double s = 0.0;
     for (int b = 0; b < nblocks; ++b) s = s + partials[(size_t)b * total + e];
     out[e] = s;
+}
+
+int sl_sum_slices(sl_ctx* ctx, const double* partials, int nblocks, int total, double* out) {
+    hipLaunchKernelGGL(k_sum_slices, dim3((total + SL_BLOCK - 1) / SL_BLOCK), dim3(SL_BLOCK), 0, ctx->stream, partials,
+                       nblocks, total, out);
+    SL_HIP_CHECK(ctx, hipGetLastError());
+    return SL_OK;
 }
 
 extern "C" int sl_policy_param_grad(sl_ctx* ctx, int64_t n, int d, const double* d_points, const double* d_coeff,
@@ -315,10 +310,7 @@ extern "C" int sl_policy_param_grad(sl_ctx* ctx, int64_t n, int d, const double*
         return SL_OK;
     });
     if (rc) return rc;
-    hipLaunchKernelGGL(k_pg_reduce, dim3((total + SL_BLOCK - 1) / SL_BLOCK), dim3(SL_BLOCK), 0, ctx->stream, partials,
-                       (int)blocks, total, d_grad);
-    SL_HIP_CHECK(ctx, hipGetLastError());
-    return SL_OK;
+    return sl_sum_slices(ctx, partials, (int)blocks, total, d_grad);
 }
 
 // =============================================================================================

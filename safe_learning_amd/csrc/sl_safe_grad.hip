@@ -18,7 +18,7 @@
 //
 // No atomics; a point's results depend on that point alone (its column of the product), so they do not
 // depend on the tile it falls into or on the batch: the same bits at every call and for every split of a call.
-#include "sl_common.h"
+#include "sl_grad_host.h"
 #include "sl_safe_grad.h"
 
 typedef double sl_sg4 __attribute__((ext_vector_type(4)));
@@ -236,9 +236,8 @@ __global__ __launch_bounds__(SL_BLOCK) void k_sg_epilogue(const SlDevModel M, co
 
 extern "C" int sl_decrease_gradient(sl_ctx* ctx, int64_t n, const double* d_points, const double* d_actions,
                                     double* d_grad, double* d_constraint, double* d_terms) {
-    if (!ctx) return sl_fail(nullptr, SL_ERR_INVALID, "sl_decrease_gradient: NULL context");
-    if (!ctx->model_set) return sl_fail(ctx, SL_ERR_INVALID, "sl_decrease_gradient: call sl_model_set first");
-    if (n < 0 || !d_grad) return sl_fail(ctx, SL_ERR_INVALID, "sl_decrease_gradient: bad argument");
+    const char* who = "sl_decrease_gradient";
+    if (const int rc = sl_point_grad_arguments(ctx, who, n, d_grad)) return rc;
     const sl_model_desc& md = ctx->h_model.m;
     const int dk = md.dynamics.kind;
     if (dk == SL_DYN_PENDULUM || dk == SL_DYN_CARTPOLE)
@@ -253,8 +252,7 @@ extern "C" int sl_decrease_gradient(sl_ctx* ctx, int64_t n, const double* d_poin
     const int d = md.grid.d, m = md.policy.m, p = ctx->h_model.in_dim;
     if (md.value.kind == SL_V_TRI && (!ctx->h_tri[0].set || ctx->h_tri[0].grid.d != d))
         return sl_fail(ctx, SL_ERR_INVALID, "sl_decrease_gradient: the Lyapunov table must be slot 0, on %d dimensions", d);
-    if (ctx->h_gp.nheads < 1)
-        return sl_fail(ctx, SL_ERR_INVALID, "sl_decrease_gradient: GP dynamics without heads (sl_gp_configure)");
+    if (const int rc = sl_point_grad_gp_heads(ctx, who)) return rc;
     int covered = 0;
     size_t rows_max = 0;
     for (int h = 0; h < ctx->h_gp.nheads; ++h) {
@@ -270,22 +268,12 @@ extern "C" int sl_decrease_gradient(sl_ctx* ctx, int64_t n, const double* d_poin
     if (covered != d)
         return sl_fail(ctx, SL_ERR_INVALID, "sl_decrease_gradient: GP heads cover %d outputs, state dimension is %d",
                        covered, d);
-    if (!d_points && n > ctx->h_model.gf.nindex)
-        return sl_fail(ctx, SL_ERR_INVALID, "sl_decrease_gradient: %lld points on a grid of %lld", (long long)n,
-                       (long long)ctx->h_model.gf.nindex);
+    if (const int rc = sl_point_grad_on_grid(ctx, who, n, d_points)) return rc;
     if (n == 0) return SL_OK;
     SL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     // a network policy: one action per point first, as everywhere else
     SlPolicyTableScope network_policy(ctx, 0, d_actions ? 0 : n, d_points);
-    if (network_policy.rc) return network_policy.rc;
-    if (!d_actions) {
-        const int kind = ctx->h_model.m.policy.kind;
-        if (kind == SL_POLICY_TRI && !ctx->h_tri[1].set)
-            return sl_fail(ctx, SL_ERR_INVALID, "sl_decrease_gradient: policy table not set");
-        if (kind == SL_POLICY_TABLE && d_points && !network_policy.swapped)
-            return sl_fail(ctx, SL_ERR_UNSUPPORTED, "sl_decrease_gradient: a per-vertex policy table cannot be "
-                                                    "evaluated at arbitrary points");
-    }
+    if (const int rc = sl_point_grad_policy(ctx, who, d_points, d_actions, network_policy)) return rc;
     // scratch: [actions n m (policy only)] [B fragments of a batch] [ss heads x batch] [sab heads x batch x SL_M]
     const int64_t ntiles = (n + 15) / 16;
     const size_t tile_doubles = (size_t)16 * (1 + m) * rows_max;

@@ -762,14 +762,8 @@ class Triangulation(DeterministicFunction):
         if self.output_dim is None:
             raise ValueError('the table has no parameters yet')
         ctx, builder = _evaluate._builder(self.input_dim)
-        d_points = _evaluate._to_device(ctx, points)
-        n, d = d_points.shape
-        if d != self.input_dim:
-            raise ValueError('the table expects %d inputs, the points have %d columns' % (self.input_dim, d))
-        if not isinstance(coefficients, torch.Tensor):
-            coefficients = np.asarray(coefficients, dtype=np.float64)
-            coefficients = coefficients.reshape(max(len(np.atleast_1d(coefficients)), 1), -1)
-        d_coeff = _evaluate._to_device(ctx, coefficients)
+        d_points, d_coeff = _evaluate._points_and_coefficients(ctx, points, coefficients, self.input_dim, 'table')
+        n = d_points.shape[0]
         if tuple(d_coeff.shape) != (n, self.output_dim):
             raise ValueError('coefficients of shape %s for %d points and %d columns'
                              % (tuple(d_coeff.shape), n, self.output_dim))
@@ -1018,14 +1012,8 @@ class NeuralNetwork(DeterministicFunction):
         if self.negate:
             raise ValueError('differentiate the network itself, not its negation')
         ctx = self._on_engine()
-        d_points = _evaluate._to_device(ctx, points)
+        d_points, d_coeff = _evaluate._points_and_coefficients(ctx, points, coefficients, self.input_dim, 'network')
         n, d = d_points.shape
-        if d != self.input_dim:
-            raise ValueError('the network expects %d inputs, the points have %d columns' % (self.input_dim, d))
-        if not isinstance(coefficients, torch.Tensor):
-            coefficients = np.asarray(coefficients, dtype=np.float64)
-            coefficients = coefficients.reshape(max(len(np.atleast_1d(coefficients)), 1), -1)
-        d_coeff = _evaluate._to_device(ctx, coefficients)
         if tuple(d_coeff.shape) != (n, self.output_dim):
             raise ValueError('coefficients of shape %s for %d points and %d outputs'
                              % (tuple(d_coeff.shape), n, self.output_dim))
@@ -1140,13 +1128,10 @@ class LyapunovNetwork(DeterministicFunction):
         is the same bit for bit at every call."""
         from . import _evaluate
         ctx = self._on_engine()
-        d_points = _evaluate._to_device(ctx, points)
-        m, d = d_points.shape
-        if d != self.input_dim:
-            raise ValueError('the network expects %d inputs, the points have %d columns' % (self.input_dim, d))
-        d_coeff = _evaluate._to_device(ctx, coefficients).reshape(-1)
-        if d_coeff.numel() != m:
-            raise ValueError('%d coefficients for %d points' % (d_coeff.numel(), m))
+        d_points, d_coeff = _evaluate._points_and_coefficients(ctx, points, coefficients, self.input_dim, 'network')
+        d_coeff = d_coeff.reshape(-1)
+        if d_coeff.numel() != d_points.shape[0]:
+            raise ValueError('%d coefficients for %d points' % (d_coeff.numel(), d_points.shape[0]))
         gradient = self._weights_gradient(self._kernel_gradient(ctx, d_points, d_coeff))
         return [-g for g in gradient] if self.negate else gradient
 

@@ -359,15 +359,11 @@ class Lyapunov(object):
             m = int(self.policy.reshape(self.discretization.nindex, -1).shape[1])
         else:
             m = _evaluate._policy_output_dim(self.policy)
-        d_actions = None
         if actions is not None:
-            if not isinstance(actions, torch.Tensor):
-                actions = np.atleast_2d(np.asarray(actions, dtype=np.float64))
-            d_actions = _evaluate._to_device(ctx, actions)
-            if d_actions.shape[0] not in (1, n) or d_actions.shape[1] != m:
-                raise ValueError('actions must be [1, %d] or [%d, %d], got %s'
-                                 % (m, n, m, tuple(d_actions.shape)))
-            d_actions = d_actions.expand(n, m).contiguous()
+            actions = _evaluate._to_device(ctx, actions)
+            if actions.shape[0] not in (1, n) or actions.shape[1] != m:
+                raise ValueError('actions must be [1, %d] or [%d, %d], got %s' % (m, n, m, tuple(actions.shape)))
+        d_actions = _evaluate._action_rows(ctx, actions, n)
         self._upload_model()
         grad = torch.empty((n, m), dtype=torch.float64, device=ctx.torch_device)
         constraint = torch.empty((n, 1), dtype=torch.float64, device=ctx.torch_device)

@@ -169,6 +169,31 @@ class PolicyIteration(object):
         return updated
 
     # ---- policy gradients (the policy-improvement half of policy iteration) ---------------------
+    def _states_device(self, states):
+        """``states`` as an ``[n, d]`` device tensor; ``None`` or ``self.state_space``: the grid's
+        vertices, uploaded once."""
+        import torch
+        from . import _evaluate
+        if states is None or states is self.state_space:
+            dev = self._ctx.torch_device
+            if getattr(self, '_state_space_dev', None) is None or self._state_space_dev.device != dev:
+                self._state_space_dev = torch.from_numpy(np.ascontiguousarray(self.state_space)).to(dev)
+            d_states = self._state_space_dev
+        else:
+            d_states = _evaluate._to_device(self._ctx, states)
+        if d_states.shape[1] != self.discretization.ndim:
+            raise ValueError('states of %d columns, the state space has %d dimensions'
+                             % (d_states.shape[1], self.discretization.ndim))
+        return d_states
+
+    @staticmethod
+    def _own_lyapunov(lyapunov):
+        """The penalty is differentiated through ``Lyapunov.decrease_gradient``: nothing else will do."""
+        from .lyapunov import Lyapunov
+        if not isinstance(lyapunov, Lyapunov):
+            raise NotImplementedError('the gradient of the Lyapunov penalty is implemented for a Lyapunov '
+                                      'instance of this package, not for %s' % type(lyapunov).__name__)
+
     def _action_gradient_device(self, states, policy, actions):
         """One ``sl_action_gradient`` call -> device tensors (states [n, d], dQ/du [n, m], Q [n])."""
         import torch
@@ -178,26 +203,10 @@ class PolicyIteration(object):
                             '(GaussianProcess, FunctionStack), not for the Euler dynamics %s'
                             % type(self.dynamics).__name__)
         ctx = self._ctx
-        dev = ctx.torch_device
-        if states is None or states is self.state_space:
-            if getattr(self, '_state_space_dev', None) is None or self._state_space_dev.device != dev:
-                self._state_space_dev = torch.from_numpy(np.ascontiguousarray(self.state_space)).to(dev)
-            d_states = self._state_space_dev
-        else:
-            d_states = _evaluate._to_device(ctx, states)
-        n, d = d_states.shape
-        if d != self.discretization.ndim:
-            raise ValueError('states of %d columns, the state space has %d dimensions'
-                             % (d, self.discretization.ndim))
-        d_actions = None
-        if actions is not None:
-            if not isinstance(actions, torch.Tensor):
-                actions = np.atleast_2d(np.asarray(actions, dtype=np.float64))
-            d_actions = _evaluate._to_device(ctx, actions)
-            if d_actions.shape[0] not in (1, n):
-                raise ValueError('actions must be one row or one row per state (%d), got %d'
-                                 % (n, d_actions.shape[0]))
-            d_actions = d_actions.expand(n, d_actions.shape[1]).contiguous()
+        d_states = self._states_device(states)
+        n = d_states.shape[0]
+        d_actions = _evaluate._action_rows(ctx, actions, n)
+        if d_actions is not None:
             # explicit actions never evaluate the policy: a constant of their width stands in its slot
             policy = ConstantFunction(np.zeros(d_actions.shape[1]))
         elif policy is None:
@@ -206,8 +215,8 @@ class PolicyIteration(object):
             raise TypeError('a per-vertex action table is not a policy of the states: pass it as `actions`')
         self._upload(policy)
         m = int(self._builder._desc.policy.m)
-        grad = torch.empty((n, m), dtype=torch.float64, device=dev)
-        q = torch.empty(n, dtype=torch.float64, device=dev)
+        grad = torch.empty((n, m), dtype=torch.float64, device=ctx.torch_device)
+        q = torch.empty(n, dtype=torch.float64, device=ctx.torch_device)
         ctx.action_gradient(n, d_states, d_actions, grad, q)
         return d_states, grad, q
 
@@ -216,42 +225,26 @@ class PolicyIteration(object):
         ``dQ/du - lambda dC/du`` [n, m], ``Q - lambda C`` [n]).  The actions are evaluated ONCE and go as
         explicit actions to ``sl_action_gradient`` and to ``lyapunov.decrease_gradient``; the two
         results are combined on the device.  ``lagrange_multiplier = 0``: the penalty is evaluated and
-        left out (the unpenalised numbers bit for bit)."""
+        left out (the unpenalised numbers bit for bit).  ``lyapunov=None``: ``_action_gradient_device``."""
         import torch
         from . import _evaluate
         from .functions import UncertainFunction
-        from .lyapunov import Lyapunov
-        if not isinstance(lyapunov, Lyapunov):
-            raise NotImplementedError('the gradient of the Lyapunov penalty is implemented for a Lyapunov '
-                                      'instance of this package, not for %s' % type(lyapunov).__name__)
+        if lyapunov is None:
+            return self._action_gradient_device(states, policy, actions)
+        self._own_lyapunov(lyapunov)
         if lyapunov.dynamics is not self.dynamics:
             raise ValueError('the Lyapunov penalty is differentiated under ONE dynamics model: '
                              'lyapunov.dynamics must be the dynamics object of this PolicyIteration')
         if not isinstance(self.dynamics, UncertainFunction):
             raise TypeError('the Lyapunov penalty needs uncertain dynamics (mean, error): the '
                             'reference reads the error bound of the GP (:97-108)')
-        ctx = self._ctx
-        if states is None or states is self.state_space:
-            dev = ctx.torch_device
-            if getattr(self, '_state_space_dev', None) is None or self._state_space_dev.device != dev:
-                self._state_space_dev = torch.from_numpy(np.ascontiguousarray(self.state_space)).to(dev)
-            d_states = self._state_space_dev
-        else:
-            d_states = _evaluate._to_device(ctx, states)
-        n = d_states.shape[0]
+        d_states = self._states_device(states)
         if actions is None:
             chosen = self.policy if policy is None else policy
             if isinstance(chosen, (np.ndarray, torch.Tensor)):
                 raise TypeError('a per-vertex action table is not a policy of the states: pass it as `actions`')
-            d_actions = _evaluate.policy(chosen, d_states)
-        else:
-            if not isinstance(actions, torch.Tensor):
-                actions = np.atleast_2d(np.asarray(actions, dtype=np.float64))
-            d_actions = _evaluate._to_device(ctx, actions)
-            if d_actions.shape[0] not in (1, n):
-                raise ValueError('actions must be one row or one row per state (%d), got %d'
-                                 % (n, d_actions.shape[0]))
-        d_actions = d_actions.expand(n, d_actions.shape[1]).contiguous()
+            actions = _evaluate.policy(chosen, d_states)
+        d_actions = _evaluate._action_rows(self._ctx, actions, d_states.shape[0])
         d_states, grad, q = self._action_gradient_device(d_states, None, d_actions)
         d_grad_c, d_c = lyapunov.decrease_gradient(d_states, d_actions)
         rate = float(lagrange_multiplier)
@@ -278,10 +271,7 @@ class PolicyIteration(object):
         ``L_f`` is a number or ``c + ||M x||_1``)."""
         import torch
         keep = isinstance(states, torch.Tensor)
-        if lyapunov is not None:
-            _, grad, _ = self._penalised_gradient_device(states, policy, actions, lyapunov, lagrange_multiplier)
-            return grad if keep else grad.cpu().numpy()
-        _, grad, _ = self._action_gradient_device(states, policy, actions)
+        _, grad, _ = self._penalised_gradient_device(states, policy, actions, lyapunov, lagrange_multiplier)
         return grad if keep else grad.cpu().numpy()
 
     def policy_gradient(self, states=None, reduction='mean', lyapunov=None, lagrange_multiplier=1.):
@@ -299,10 +289,7 @@ class PolicyIteration(object):
         lagrange_multiplier=...)`` - the safe policy update of ``examples/inverted_pendulum.ipynb``
         cell 17 - see ``action_gradient`` for what is differentiated and what is not."""
         if lyapunov is not None:
-            from .lyapunov import Lyapunov
-            if not isinstance(lyapunov, Lyapunov):
-                raise NotImplementedError('the gradient of the Lyapunov penalty is implemented for a Lyapunov '
-                                          'instance of this package, not for %s' % type(lyapunov).__name__)
+            self._own_lyapunov(lyapunov)
         if reduction not in ('mean', 'sum'):
             raise ValueError("reduction must be 'mean' or 'sum', got %r" % (reduction,))
         if self._world > 1:
@@ -313,10 +300,7 @@ class PolicyIteration(object):
             raise TypeError('policy_gradient differentiates a bare NeuralNetwork or Triangulation policy, '
                             'not %s' % (('a negated ' if getattr(policy, 'negate', False) else '')
                                         + type(policy).__name__))
-        if lyapunov is not None:
-            d_states, grad, q = self._penalised_gradient_device(states, None, None, lyapunov, lagrange_multiplier)
-        else:
-            d_states, grad, q = self._action_gradient_device(states, None, None)
+        d_states, grad, q = self._penalised_gradient_device(states, None, None, lyapunov, lagrange_multiplier)
         if reduction == 'mean':
             n = d_states.shape[0]
             grad = grad * (1.0 / n)

@@ -15,6 +15,8 @@ operation, in that order - so the host build of the header equals them bit for b
 import numpy as np
 
 from oracle.np_functions import LyapunovNetwork
+import training_tolerance
+from training_tolerance import ratio_to_companion, recorded_or_measured
 
 
 def _kernels(net, dtype):
@@ -95,18 +97,6 @@ def max_abs_tanh(net, points):
         if act == 'tanh':
             worst = max(worst, float(np.abs(post).max()))
     return worst
-
-
-def ratio_to_companion(got, ref, comp):
-    """max over all entries of |got - ref| / A, in units of 2^-53 (entries with A = 0 must agree exactly)."""
-    worst = 0.0
-    for g, r, a in zip(got, ref, comp):
-        g, r, a = (np.asarray(v, dtype=np.longdouble) for v in (g, r, a))
-        diff = np.abs(g - r)
-        assert np.all(diff[a == 0] == 0)
-        if (a > 0).any():
-            worst = max(worst, float((diff[a > 0] / a[a > 0]).max()))
-    return worst * 2.0 ** 53
 
 
 # ---- the losses (sl_nn_train.h) --------------------------------------------------------------------
@@ -329,12 +319,10 @@ def measure_reference_ratio(key, m):
 def reference_ratio(key, m):
     """The recorded figure of a batch (m: its size, or the step of "steps-pre" / "steps-roa"); a batch size
     without one (the largest depends on the device's CU count) is measured on the spot, once."""
-    if (key, m) not in REFERENCE_RATIO:
-        REFERENCE_RATIO[key, m] = measure_reference_ratio(key, m)
-    return REFERENCE_RATIO[key, m]
+    return recorded_or_measured(REFERENCE_RATIO, (key, m), lambda pair: measure_reference_ratio(*pair))
 
 
 def tolerance(key, m):
     """32 times the reference's own error on that batch: room for another summation order, a device tanh a
     few ulp off where libm is within one, and that error's amplification by up to 24 in 1 - h^2 (MAX_TANH)."""
-    return 32.0 * reference_ratio(key, m) * 2.0 ** -53
+    return training_tolerance.tolerance(reference_ratio(key, m))

@@ -24,8 +24,8 @@ import scipy.linalg
 
 import oracle
 from oracle import np_functions as onp
-
-LONG = np.longdouble
+import training_tolerance
+from training_tolerance import LONG, _as_list, ratio_to_companion, recorded_or_measured
 
 
 # ---- kernels: value and derivative with respect to the query's action columns ------------------------------
@@ -307,26 +307,6 @@ def policy_improvement_step(rl, states, learning_rate, reduction='mean'):
     return float(objective), grad, comp
 
 
-# ---- comparing ------------------------------
-def _as_list(x):
-    return list(x) if isinstance(x, (list, tuple)) else [x]
-
-
-def ratio_to_companion(got, ref, comp, rows=None):
-    """max |got - ref| / A in units of 2^-53 (entries with A = 0 must agree exactly); ``rows``: a mask of the
-    leading axis (points that are compared)."""
-    worst = 0.0
-    for g, r, a in zip(_as_list(got), _as_list(ref), _as_list(comp)):
-        g, r, a = (np.asarray(v, dtype=LONG) for v in (g, r, a))
-        if rows is not None:
-            g, r, a = g[rows], r[rows], a[rows]
-        diff = np.abs(g - r)
-        assert np.all(diff[a == 0] == 0)
-        if (a > 0).any():
-            worst = max(worst, float((diff[a > 0] / a[a > 0]).max()))
-    return worst * 2.0 ** 53
-
-
 # ---- the cases of the tests ------------------------------
 def lqr_case():
     """The 1-D system of safe_learning/tests/test_rl.py:29-77 (tests/golden/reference_known_answers.json)."""
@@ -573,15 +553,13 @@ def measure_reference_ratio(key):
 
 
 def reference_ratio(key):
-    if key not in REFERENCE_RATIO:
-        REFERENCE_RATIO[key] = measure_reference_ratio(key)
-    return REFERENCE_RATIO[key]
+    return recorded_or_measured(REFERENCE_RATIO, key, measure_reference_ratio)
 
 
 def tolerance(*key):
     """32 times the reference's own measured error on that batch: room for another summation order, the
     device's exp and tanh a few ulp off where libm is within one, and fused operations in the kernel values."""
-    return 32.0 * reference_ratio(tuple(key)) * 2.0 ** -53
+    return training_tolerance.tolerance(reference_ratio(tuple(key)))
 
 
 TABLES = {

@@ -26,9 +26,9 @@ import scipy.linalg
 import np_gp_truth as G
 import np_policy_training as T
 from oracle import np_functions as onp
+import training_tolerance
+from training_tolerance import LONG, UNIT, recorded_or_measured
 
-LONG = np.longdouble
-UNIT = 2.0 ** -53
 ABS_MARGIN = 1e-9
 MAX_EXCLUDED = T.MAX_EXCLUDED
 RATIO_POINTS = 1000
@@ -499,12 +499,10 @@ def measure_reference_ratio(key):
 
 
 def reference_ratio(key):
-    if key not in REFERENCE_RATIO:
-        REFERENCE_RATIO[key] = measure_reference_ratio(key)
-    return REFERENCE_RATIO[key]
+    return recorded_or_measured(REFERENCE_RATIO, key, measure_reference_ratio)
 
 
 def tolerance(key):
     """-> (tolerance for dC/du, tolerance for C), each 32 times the reference's own measured error."""
     r_grad, r_c = reference_ratio(tuple(key))
-    return 32.0 * r_grad * UNIT, 32.0 * r_c * UNIT
+    return training_tolerance.tolerance(r_grad), training_tolerance.tolerance(r_c)

@@ -11,20 +11,16 @@ import sys
 import numpy as np
 import pytest
 
+import hostsim_build
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
 @pytest.fixture(scope="module")
 def sim(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("gp4_list") / "gp4_list_sim")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror",
-           "-I" + os.path.join(ROOT, "safe_learning_amd", "csrc"),
-           os.path.join(ROOT, "tests", "hostsim", "gp4_list_sim.cpp"), "-o", out]
-    sanitized = subprocess.run(cmd + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"],
-                               stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if sanitized.returncode != 0:                         # (no sanitizer runtime: the checks of the program remain)
-        subprocess.check_call(cmd)
+    out = hostsim_build.sanitized_program_or_plain("gp4_list_sim.cpp", tmp_path_factory.mktemp("gp4_list"),
+                                                   ["-O1"] + hostsim_build.SIM_FLAGS)
 
     def run(*args):
         res = subprocess.run([out] + [str(a) for a in args], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,

@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 import scipy.linalg
 
+import hostsim_build
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
@@ -25,11 +27,7 @@ SIGNAL_VARIANCE = 0.7
 @pytest.fixture(scope="module")
 def sim(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("gp_floor")
-    out = str(tmp / "gp_floor_sim")
-    subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror",
-                           "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I" + os.path.join(ROOT, "safe_learning_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "hostsim", "gp_floor_sim.cpp"), "-o", out])
+    out = hostsim_build.program("gp_floor_sim.cpp", tmp, ["-O2"] + hostsim_build.SIM_FLAGS, sanitize=True)
 
     def run(linv, rp, variance):
         n = len(linv)

@@ -15,6 +15,7 @@ import pytest
 from numpy.testing import assert_allclose, assert_array_equal
 
 import cases
+import guarded
 import np_lyapunov_training as T
 
 pytestmark = pytest.mark.gpu
@@ -78,23 +79,14 @@ def test_gradient_is_deterministic_and_stays_in_bounds(sl):
     points, coeff = T.make_batch("notebook", m)
     d_points, d_coeff = torch.from_numpy(points).cuda(), torch.from_numpy(coeff).cuda()
     total = sum(k.size for k in onet.kernels())
-    sentinel = -1.2345678e300
-    guard = 64
-    runs = []
-    for _ in range(2):
-        buf = torch.full((total + 2 * guard,), sentinel, dtype=torch.float64, device="cuda")
-        ctx.nn_param_grad(m, 2, d_points, d_coeff, buf[guard:guard + total])
-        host = buf.cpu().numpy()
-        assert np.all(host[:guard] == sentinel) and np.all(host[guard + total:] == sentinel)
-        assert not np.any(host[guard:guard + total] == sentinel)
-        runs.append(host[guard:guard + total].copy())
-    assert_array_equal(runs[0].view(np.uint64), runs[1].view(np.uint64))
+    runs = [guarded.run(lambda grad: ctx.nn_param_grad(m, 2, d_points, d_coeff, grad), [total])[0] for _ in range(2)]
+    assert_array_equal(runs[0], runs[1])
     nbytes, intact = ctx.nn_train_scratch()
     # (the area is one slice of `total` doubles per workgroup, the guard zones lie directly around it)
     assert nbytes >= 2 * 8 * total and nbytes % (8 * total) == 0
     assert intact, "a kernel wrote outside the scratch area"
     G = T.kernel_gradient(onet, points, coeff)[0]
-    assert_allclose(runs[0], np.concatenate([g.ravel() for g in G]), rtol=1e-9, atol=1e-9)
+    assert_allclose(runs[0].view(np.float64), np.concatenate([g.ravel() for g in G]), rtol=1e-9, atol=1e-9)
     a = net.parameter_gradient(points, coeff)
     b = net.parameter_gradient(points, coeff)
     for x, y in zip(a, b):

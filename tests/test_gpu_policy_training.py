@@ -9,11 +9,11 @@ import numpy as np
 import pytest
 from numpy.testing import assert_allclose, assert_array_equal
 
+import guarded
 import np_policy_training as T
+from training_tolerance import UNIT
 
 pytestmark = pytest.mark.gpu
-
-UNIT = 2.0 ** -53
 
 
 @pytest.fixture(scope="module")
@@ -134,33 +134,12 @@ def test_table_parameter_gradient_matches_reference(sl, key):
 
 
 # ---- determinism and bounds ------------------------------
-SENTINEL = -7.25e300
-GUARD = 512
-
-
-def _guarded(size):
-    import torch
-    buf = torch.full((GUARD + size + GUARD,), SENTINEL, dtype=torch.float64, device="cuda")
-    return buf, buf[GUARD:GUARD + size]
-
-
 def _twice(call, sizes):
-    """Run ``call(*outputs)`` twice into guarded buffers -> the outputs of the first run; the second run's
-    bits must be the same and no guard word may change."""
-    import torch
-    runs = []
-    for _ in range(2):
-        pairs = [_guarded(size) for size in sizes]
-        call(*[out for _, out in pairs])
-        torch.cuda.synchronize()
-        for (buf, _), size in zip(pairs, sizes):
-            host = buf.cpu().numpy()
-            assert (host[:GUARD] == SENTINEL).all() and (host[GUARD + size:] == SENTINEL).all(), "guard zone written"
-            assert not (host[GUARD:GUARD + size] == SENTINEL).any(), "output left unwritten"
-        runs.append([buf.cpu().numpy().view(np.uint64) for buf, _ in pairs])
-    for a, b in zip(*runs):
+    """Run ``call(*outputs)`` twice into guarded buffers -> the outputs' bits; the second run's must be the same."""
+    first, again = guarded.run(call, sizes), guarded.run(call, sizes)
+    for a, b in zip(first, again):
         assert_array_equal(a, b)
-    return runs[0]
+    return first
 
 
 def test_entry_points_are_deterministic_and_stay_in_bounds(sl):

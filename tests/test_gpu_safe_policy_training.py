@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 from numpy.testing import assert_array_equal
 
+import guarded
 import np_policy_training as T
 import np_safe_policy_training as S
 
@@ -105,31 +106,6 @@ def test_decrease_gradient_matches_reference(sl, key):
 
 
 # ---- determinism and bounds ------------------------------
-SENTINEL = -7.25e300
-GUARD = 512
-
-
-def _guarded(size):
-    import torch
-    buf = torch.full((GUARD + size + GUARD,), SENTINEL, dtype=torch.float64, device="cuda")
-    return buf, buf[GUARD:GUARD + size]
-
-
-def _run_guarded(call, sizes):
-    """``call(*outputs)`` into buffers with sentinel rows before and after -> the outputs' bits."""
-    import torch
-    pairs = [_guarded(size) for size in sizes]
-    call(*[out for _, out in pairs])
-    torch.cuda.synchronize()
-    outs = []
-    for (buf, _), size in zip(pairs, sizes):
-        host = buf.cpu().numpy()
-        assert (host[:GUARD] == SENTINEL).all() and (host[GUARD + size:] == SENTINEL).all(), "guard zone written"
-        assert not (host[GUARD:GUARD + size] == SENTINEL).any(), "output left unwritten"
-        outs.append(host[GUARD:GUARD + size].view(np.uint64).copy())
-    return outs
-
-
 @pytest.mark.parametrize("key", [("pendulum", None, "negtable", "abs_grad"), ("rbf", 300, "quadratic", "abs_linear"),
                                  ("two", None, "quadratic", "abs_linear")], ids=_ids)
 def test_entry_point_is_deterministic_and_stays_in_bounds(sl, key):
@@ -143,14 +119,14 @@ def test_entry_point_is_deterministic_and_stays_in_bounds(sl, key):
     lyap._upload_model()
     sizes = [n * m, n, n * (2 + 2 * d)]
     for acts in (d_actions, None):
-        first = _run_guarded(lambda g, c, t: lyap._ctx.decrease_gradient(n, d_states, acts, g, c, t), sizes)
-        again = _run_guarded(lambda g, c, t: lyap._ctx.decrease_gradient(n, d_states, acts, g, c, t), sizes)
+        first = guarded.run(lambda g, c, t: lyap._ctx.decrease_gradient(n, d_states, acts, g, c, t), sizes)
+        again = guarded.run(lambda g, c, t: lyap._ctx.decrease_gradient(n, d_states, acts, g, c, t), sizes)
         for a, b in zip(first, again):
             assert_array_equal(a, b)
         # 1000 points in one call = 992 + 8 points in two
-        head = _run_guarded(lambda g, c, t: lyap._ctx.decrease_gradient(
+        head = guarded.run(lambda g, c, t: lyap._ctx.decrease_gradient(
             992, d_states[:992], None if acts is None else acts[:992], g, c, t), [992 * m, 992, 992 * (2 + 2 * d)])
-        tail = _run_guarded(lambda g, c, t: lyap._ctx.decrease_gradient(
+        tail = guarded.run(lambda g, c, t: lyap._ctx.decrease_gradient(
             8, d_states[992:].contiguous(), None if acts is None else acts[992:].contiguous(), g, c, t),
             [8 * m, 8, 8 * (2 + 2 * d)])
         for whole, a, b in zip(first, head, tail):

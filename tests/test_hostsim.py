@@ -7,16 +7,14 @@ comparisons through the real kernels.
 """
 
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 from numpy.testing import assert_allclose, assert_array_equal
 
 import cases
+import hostsim_build
 import oracle
-from conftest import ROOT
 from safe_learning_amd import functions as F
 from safe_learning_amd._model import ModelBuilder
 from safe_learning_amd.benchmarks import build_specs
@@ -31,17 +29,8 @@ class _RecordingCtx(object):
 
 
 @pytest.fixture(scope="module")
-def hostsim():
-    src = os.path.join(ROOT, "tests", "hostsim", "hostsim.cpp")
-    lib = os.path.join(ROOT, "tests", "hostsim", "libhostsim.so")
-    deps = [src, os.path.join(ROOT, "safe_learning_amd", "csrc", "sl_model.h"),
-            os.path.join(ROOT, "include", "sl_hip.h")]
-    if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                               "-I" + os.path.join(ROOT, "include"),
-                               "-I" + os.path.join(ROOT, "safe_learning_amd", "csrc"),
-                               "-o", lib, src])
-    h = C.CDLL(lib)
+def hostsim(tmp_path_factory):
+    h = hostsim_build.shared("hostsim.cpp", tmp_path_factory.mktemp("hostsim"), hostsim_build.SHIM_FLAGS)
     h.hs_vbits.restype = C.c_uint64
     h.hs_vbits.argtypes = [C.c_double]
     h.hs_vbits_to_double.restype = C.c_double

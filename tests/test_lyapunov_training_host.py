@@ -24,15 +24,14 @@ Measured here (printed by the tests; float64 on x86-64 with glibc):
 """
 
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
 import pytest
 from numpy.testing import assert_allclose, assert_array_equal
 
+import hostsim_build
 import np_lyapunov_training as T
-from conftest import ROOT
 
 
 # ---- 1. the reference against finite differences ---------------------------------------------------------------
@@ -107,15 +106,10 @@ def test_step_batches_reference_error():
 # ---- 3. the per-sample arithmetic, compiled for the host ----------------------------------------------------------
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    src = os.path.join(ROOT, "tests", "hostsim", "nn_train.cpp")
-    csrc = os.path.join(ROOT, "safe_learning_amd", "csrc")
     out = tmp_path_factory.mktemp("nn_train")
-    flags = ["-O2", "-std=c++17", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), "-I" + csrc]
-    exe, lib = str(out / "nn_train"), str(out / "libnn_train.so")
-    subprocess.check_call(["g++"] + flags + ["-o", exe, src])
+    exe = hostsim_build.program("nn_train.cpp", out, hostsim_build.SHIM_FLAGS)
     assert subprocess.run([exe], stdout=subprocess.PIPE, text=True).stdout.strip() == "nn_train: ok"
-    subprocess.check_call(["g++"] + flags + ["-fPIC", "-shared", "-o", lib, src])
-    return C.CDLL(lib)
+    return hostsim_build.shared("nn_train.cpp", out, hostsim_build.SHIM_FLAGS)
 
 
 def _p(a):

@@ -8,31 +8,25 @@ sl_value_solve runs is checked on the reference's 4-state known answer and on ra
 """
 
 import ctypes as C
+import functools
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 from numpy.testing import assert_allclose, assert_array_equal
 
+import hostsim_build
 import oracle
 from conftest import ROOT
 from safe_learning_amd import functions as F
 
 
+@functools.lru_cache(maxsize=None)
 def load_shim():
-    """The shim, compiled when it is missing or older than its sources (also used by
-    tests/test_gpu_policy_evaluation.py)."""
-    src = os.path.join(ROOT, "tests", "hostsim", "policy_rows.cpp")
-    lib = os.path.join(ROOT, "tests", "hostsim", "libpolicyrows.so")
-    csrc = os.path.join(ROOT, "safe_learning_amd", "csrc")
-    deps = [src, os.path.join(csrc, "sl_policy_rows.h"), os.path.join(csrc, "sl_model.h"),
-            os.path.join(ROOT, "include", "sl_hip.h")]
-    if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                               "-I" + os.path.join(ROOT, "include"), "-I" + csrc, "-o", lib, src])
-    return C.CDLL(lib)
+    """The shim, compiled once per process (also used by tests/test_gpu_policy_evaluation.py and
+    tests/test_gpu_bellman_matrix.py)."""
+    return hostsim_build.shared("policy_rows.cpp", None, hostsim_build.SHIM_FLAGS)
 
 
 @pytest.fixture(scope="module")

@@ -18,15 +18,14 @@ Measured here (printed by the tests; float64 on x86-64 with glibc):
 """
 
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
 import pytest
 from numpy.testing import assert_allclose, assert_array_equal
 
+import hostsim_build
 import np_policy_training as T
-from conftest import ROOT
 from oracle import np_functions as onp
 
 EXTENDED = np.finfo(np.longdouble).eps < 1e-18
@@ -234,24 +233,12 @@ class _Head(C.Structure):
                 ("inv_ls", C.c_void_p), ("xs", C.c_void_p), ("alpha", C.c_void_p), ("kernel", C.c_void_p)]
 
 
-def _compile(out, sanitize):
-    src = os.path.join(ROOT, "tests", "hostsim", "policy_grad.cpp")
-    csrc = os.path.join(ROOT, "safe_learning_amd", "csrc")
-    flags = ["-O2", "-std=c++17", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), "-I" + csrc]
-    exe = str(out / ("policy_grad_san" if sanitize else "policy_grad"))
-    extra = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-    subprocess.check_call(["g++"] + flags + extra + ["-o", exe, src])
-    return exe, flags, src
-
-
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
     out = tmp_path_factory.mktemp("policy_grad")
-    exe, flags, src = _compile(out, False)
+    exe = hostsim_build.program("policy_grad.cpp", out, hostsim_build.SHIM_FLAGS)
     assert subprocess.run([exe], stdout=subprocess.PIPE, text=True).stdout.strip() == "policy_grad: ok"
-    lib = str(out / "libpolicy_grad.so")
-    subprocess.check_call(["g++"] + flags + ["-fPIC", "-shared", "-o", lib, src])
-    lib = C.CDLL(lib)
+    lib = hostsim_build.shared("policy_grad.cpp", out, hostsim_build.SHIM_FLAGS)
     lib.pg_dact.restype = C.c_double
     lib.pg_dact.argtypes = [C.c_int, C.c_double]
     return lib
@@ -259,7 +246,8 @@ def shim(tmp_path_factory):
 
 def test_header_under_sanitizers(tmp_path_factory):
     """The stand-alone program of tests/hostsim/policy_grad.cpp under AddressSanitizer and UBSan, on its own."""
-    exe, _, _ = _compile(tmp_path_factory.mktemp("policy_grad_san"), True)
+    exe = hostsim_build.program("policy_grad.cpp", tmp_path_factory.mktemp("policy_grad_san"),
+                                hostsim_build.SHIM_FLAGS + ["-g"], sanitize=True)
     run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert run.returncode == 0 and run.stdout.strip() == "policy_grad: ok", run.stdout
 

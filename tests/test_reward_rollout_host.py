@@ -13,40 +13,28 @@ comparisons through the real kernels.
 
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 from numpy.testing import assert_allclose, assert_array_equal
 
+import hostsim_build
 import np_reward_rollout as NR
 import np_rollout
 import reward_rollout_cases as RRC
 import rollout_cases as RC
-from conftest import GOLDEN_DIR, ROOT
+from conftest import GOLDEN_DIR
 from safe_learning_amd import functions as F
 from safe_learning_amd import utilities as U
 from safe_learning_amd._model import ModelBuilder
 from test_rollout_host import _FakeEngine, _RecordingCtx, _p
 
 
-def load_shim():
-    """tests/hostsim/reward_rollout.cpp with the flags of test_rollout_host.load_shim."""
-    src = os.path.join(ROOT, "tests", "hostsim", "reward_rollout.cpp")
-    lib = os.path.join(ROOT, "tests", "hostsim", "libreward_rollout.so")
-    csrc = os.path.join(ROOT, "safe_learning_amd", "csrc")
-    deps = [src, os.path.join(ROOT, "tests", "hostsim", "rollout.cpp"), os.path.join(csrc, "sl_reward_rollout.h"),
-            os.path.join(csrc, "sl_rollout.h"), os.path.join(csrc, "sl_model.h"),
-            os.path.join(ROOT, "include", "sl_hip.h")]
-    if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                               "-I" + os.path.join(ROOT, "include"), "-I" + csrc, "-o", lib, src])
-    return C.CDLL(lib)
-
-
 @pytest.fixture(scope="module")
-def shim():
-    return load_shim()
+def shim(tmp_path_factory):
+    """tests/hostsim/reward_rollout.cpp with the flags of test_rollout_host's shim."""
+    return hostsim_build.shared("reward_rollout.cpp", tmp_path_factory.mktemp("reward_rollout"),
+                                hostsim_build.SHIM_FLAGS)
 
 
 def _weights(discount, horizon):

@@ -10,36 +10,24 @@ interpolated policy, and mask for mask on full-horizon regions of attraction.  T
 
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 from numpy.testing import assert_allclose, assert_array_equal
 
 import exclusions
+import hostsim_build
 import np_rollout
 import rollout_cases as RC
-from conftest import GOLDEN_DIR, ROOT
+from conftest import GOLDEN_DIR
 from safe_learning_amd import functions as F
 from safe_learning_amd import utilities as U
 from safe_learning_amd._model import ModelBuilder
 
 
-def load_shim():
-    src = os.path.join(ROOT, "tests", "hostsim", "rollout.cpp")
-    lib = os.path.join(ROOT, "tests", "hostsim", "librollout.so")
-    csrc = os.path.join(ROOT, "safe_learning_amd", "csrc")
-    deps = [src, os.path.join(csrc, "sl_rollout.h"), os.path.join(csrc, "sl_model.h"),
-            os.path.join(ROOT, "include", "sl_hip.h")]
-    if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                               "-I" + os.path.join(ROOT, "include"), "-I" + csrc, "-o", lib, src])
-    return C.CDLL(lib)
-
-
 @pytest.fixture(scope="module")
-def shim():
-    return load_shim()
+def shim(tmp_path_factory):
+    return hostsim_build.shared("rollout.cpp", tmp_path_factory.mktemp("rollout"), hostsim_build.SHIM_FLAGS)
 
 
 def _p(a):

@@ -8,7 +8,6 @@ layer on a stand-in engine.  Every test prints the ratio it measured before it a
 
 import ctypes as C
 import inspect
-import os
 import subprocess
 import types
 
@@ -16,9 +15,9 @@ import numpy as np
 import pytest
 from numpy.testing import assert_allclose, assert_array_equal
 
+import hostsim_build
 import np_policy_training as T
 import np_safe_policy_training as S
-from conftest import ROOT
 from oracle import np_functions as onp
 
 EXTENDED = np.finfo(np.longdouble).eps < 1e-18
@@ -183,29 +182,18 @@ class _Head(C.Structure):
                 ("inv_ls", C.c_void_p), ("xs", C.c_void_p), ("alpha", C.c_void_p), ("kernel", C.c_void_p)]
 
 
-def _compile(out, sanitize):
-    src = os.path.join(ROOT, "tests", "hostsim", "safe_grad.cpp")
-    csrc = os.path.join(ROOT, "safe_learning_amd", "csrc")
-    flags = ["-O2", "-std=c++17", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), "-I" + csrc]
-    exe = str(out / ("safe_grad_san" if sanitize else "safe_grad"))
-    extra = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-    subprocess.check_call(["g++"] + flags + extra + ["-o", exe, src])
-    return exe, flags, src
-
-
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
     out = tmp_path_factory.mktemp("safe_grad")
-    exe, flags, src = _compile(out, False)
+    exe = hostsim_build.program("safe_grad.cpp", out, hostsim_build.SHIM_FLAGS)
     assert subprocess.run([exe], stdout=subprocess.PIPE, text=True).stdout.strip() == "safe_grad: ok"
-    lib = str(out / "libsafe_grad.so")
-    subprocess.check_call(["g++"] + flags + ["-fPIC", "-shared", "-o", lib, src])
-    return C.CDLL(lib)
+    return hostsim_build.shared("safe_grad.cpp", out, hostsim_build.SHIM_FLAGS)
 
 
 def test_header_under_sanitizers(tmp_path_factory):
     """The stand-alone program of tests/hostsim/safe_grad.cpp under AddressSanitizer and UBSan, on its own."""
-    exe, _, _ = _compile(tmp_path_factory.mktemp("safe_grad_san"), True)
+    exe = hostsim_build.program("safe_grad.cpp", tmp_path_factory.mktemp("safe_grad_san"),
+                                hostsim_build.SHIM_FLAGS + ["-g"], sanitize=True)
     run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert run.returncode == 0 and run.stdout.strip() == "safe_grad: ok", run.stdout
 
@@ -366,7 +354,7 @@ def _stand_in(monkeypatch):
     rl = R.PolicyIteration.__new__(R.PolicyIteration)
     rl.dynamics, rl.policy, rl._world = dynamics, policy, 1
     rl._ctx = types.SimpleNamespace(torch_device=torch.device("cpu"))
-    rl.discretization = types.SimpleNamespace(all_points=np.zeros((3, 2)))
+    rl.discretization = types.SimpleNamespace(all_points=np.zeros((3, 2)), ndim=2)
 
     def action_gradient_device(states, policy_arg, actions):
         calls.append(("action_gradient", actions))
