@@ -154,13 +154,17 @@ def roa_classification_step(net, states, successors, labels, weights, safe_level
     return means, terms, comps
 
 
-# ---- the four networks of the tests -------------------------------------------------------------------
+# ---- the networks of the tests ------------------------------------------------------------------------
+# ("five-inputs" and "six-inputs": the second input slab of the kernels, inputs 4 and 5; "five-inputs" is
+# the two-layer instantiation of k_nn_loss / k_nn_param_grad)
 
 NETWORKS = {
     "notebook": (2, [64, 64, 64], ['tanh', 'tanh', 'tanh']),
     "one-layer": (4, [4], ['tanh']),
     "ragged": (2, [5, 5, 17], ['tanh', 'relu', 'linear']),
     "four-layers": (3, [16, 16, 16, 64], ['tanh'] * 4),
+    "five-inputs": (5, [8, 12], ['tanh', 'tanh']),
+    "six-inputs": (6, [18, 40, 64], ['relu', 'tanh', 'tanh']),
 }
 
 
@@ -236,6 +240,23 @@ def training_batch(case):
     return dict(states=states, successors=successors, labels=labels, weights=weights, targets=0.09 * cost * (1.0 + 0.5 * states[:, 0]))
 
 
+def wide_input_batch(net, m=1003, seed=21):
+    """A loss batch for a network of five or six inputs (no grid case has one): states uniform in [-0.5, 0.5]^d
+    (V of make_network("five-inputs") and of make_network("six-inputs") then straddles SAFE_LEVEL), successors under a fixed linear map with
+    expanding and contracting directions (V increases along it at some labelled states and decreases at
+    others), labels = a ball, balanced class weights, pre-training targets around V on both sides of it."""
+    d = net.input_dim
+    rng = np.random.default_rng(seed)
+    states = rng.uniform(-0.5, 0.5, (m, d))
+    step = np.diag(np.linspace(1.15, 0.7, d)) + 0.05 * rng.normal(size=(d, d))
+    successors = states.dot(step.T)
+    labels = (np.sum(states * states, axis=1) <= 0.5).astype(np.float64)
+    positives = labels.sum()
+    weights = np.where(labels > 0, m / positives, m / (m - positives))
+    targets = values(net, states) * (1.0 + 0.5 * states[:, 0]) + 0.01 * states[:, 1]
+    return dict(states=states, successors=successors, labels=labels, weights=weights, targets=targets)
+
+
 def oracle_network(case):
     spec = case["V"]
     return LyapunovNetwork(case["d"], spec["layer_dims"], spec["activations"], spec["eps"],
@@ -269,6 +290,10 @@ REFERENCE_RATIO = {
     ("one-layer", 1000): 0.37, ("one-layer", 70001): 0.029,
     ("ragged", 1): 2013., ("ragged", 15): 12.6, ("ragged", 16): 59.3, ("ragged", 17): 13.0,
     ("ragged", 1000): 5.9, ("ragged", 70001): 0.70,
+    ("five-inputs", 1): 13.4, ("five-inputs", 15): 2.51, ("five-inputs", 16): 6.21, ("five-inputs", 17): 3.14,
+    ("five-inputs", 1000): 1.07, ("five-inputs", 70001): 0.148,
+    ("six-inputs", 1): 72.6, ("six-inputs", 15): 7.29, ("six-inputs", 16): 6.76, ("six-inputs", 17): 6.33,
+    ("six-inputs", 1000): 1.64, ("six-inputs", 70001): 0.250,
     ("steps-pre", 0): 6.28, ("steps-pre", 1): 6.29, ("steps-pre", 2): 6.83, ("steps-pre", 3): 7.54,
     ("steps-pre", 4): 3.91,
     ("steps-roa", 0): 10.3, ("steps-roa", 1): 7.60, ("steps-roa", 2): 5.77, ("steps-roa", 3): 9.62,

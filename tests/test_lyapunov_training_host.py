@@ -14,6 +14,8 @@ Measured here (printed by the tests; float64 on x86-64 with glibc):
     [4]               1.83 / 0.408 / 0.623 / 0.811 / 0.362 / 0.028
     [5, 5, 17]        2013 / 12.5 / 59.3 / 12.9 / 5.863 / 0.693
     [16, 16, 16, 64]  445 / 23.2 / 8.97 / 8.24 / 1.355 / 0.216
+    [8, 12], d = 5    13.4 / 2.51 / 6.21 / 3.14 / 1.068 / 0.148
+    [18, 40, 64], 6   72.6 / 7.29 / 6.76 / 6.33 / 1.638 / 0.250
   (A does not carry the forward pass's rounding where a pre-activation cancels, so a few points are far from
   long double in units of A; over M points A grows like M, the error like sqrt(M)); another summation order of
   float64 at M = 1000: 0.308, 0.278, 1.625, 1.280.  On the step tests' [16, 16, 16] network: 6.276
@@ -69,10 +71,10 @@ def test_oracle_gradient_matches_finite_differences(key):
 def test_reference_error_and_tanh_range(key):
     net = T.make_network(key)
     extended = np.finfo(np.longdouble).eps < 1e-18         # (no extended precision: nothing to measure)
-    # the recorded ratio of every batch of the GPU test (the 70 001-point batches of the two large networks
-    # take half a minute in long double: measured once with the same function, 0.049 and 0.216)
+    # the recorded ratio of every batch of the GPU test (the 70 001-point batches of the three large networks
+    # take 12 s to half a minute in long double: measured once with the same function, 0.049, 0.216 and 0.250)
     for m in (1, 15, 16, 17, 1000, 70001):
-        if m == 70001 and key in ("notebook", "four-layers"):
+        if m == 70001 and key in ("notebook", "four-layers", "six-inputs"):
             continue
         ratio = T.measure_reference_ratio(key, m)
         print("%s, M = %d: float64 vs long double %.3f x 2^-53 of A" % (key, m, ratio))
@@ -233,6 +235,31 @@ def test_gpu_test_batches_are_decided():
             objective, terms, _ = T.pretraining_step(net, batch["states"], batch["targets"], 0.05)
             assert T.undecided(terms, "abs").mean() <= 0.01
             assert (terms["diff"] > 0).any() and (terms["diff"] < 0).any()
+
+
+@pytest.mark.parametrize("key", ["five-inputs", "six-inputs"])
+def test_wide_input_batch_is_decided(key):
+    """The loss batches of tests/test_gpu_network_matrix.py::test_loss_kernel_with_five_and_six_inputs: the same
+    properties, more than one workgroup of k_nn_loss (128 samples each) and a last one that is not full."""
+    net = T.make_network(key)
+    batch = T.wide_input_batch(net)
+    m = len(batch["states"])
+    assert m > 128 and m % 128 and batch["states"].shape[1] == net.input_dim > 4
+    labels = batch["labels"] > 0
+    assert 0.2 < labels.mean() < 0.8
+    means, terms, _ = T.roa_classification_step(net, batch["states"], batch["successors"], batch["labels"],
+                                                batch["weights"], T.SAFE_LEVEL, T.LAGRANGE, None, T.EPS)
+    print("%s: %s, %.2f %% undecided" % (key, means, 100 * T.undecided(terms, "roa").mean()))
+    assert T.undecided(terms, "roa").mean() <= 0.01
+    assert terms["hinge_on"][labels].any() and terms["hinge_on"][~labels].any()
+    assert not terms["hinge_on"][labels].all() and not terms["hinge_on"][~labels].all()
+    assert (terms["dec_on"] & labels).any() and (~terms["dec_on"] & labels).any()
+    assert means["classifier_loss"] > 0 and means["decrease_loss"] > 0
+    _, terms, _ = T.pretraining_step(net, batch["states"], batch["targets"], None)
+    assert T.undecided(terms, "abs").mean() <= 0.01
+    assert (terms["diff"] > 0).any() and (terms["diff"] < 0).any()
+    points = np.vstack((batch["states"], batch["successors"]))
+    assert T.max_abs_tanh(net, points) <= T.MAX_TANH
 
 
 # ---- 4. the reference optimisation does something ------------------------------------------------------------------

@@ -147,7 +147,11 @@ def main():
              "* `dispatch_matrix.md`: every instantiation the `sl_with_dim` lists of `sl_bellman.hip`, `sl_bellman4.hip`, "
              "`sl_succ.hip` and `sl_policy_solve.hip` compile - the test that reaches it or why none can "
              "(`tests/bellman_matrix.py`), the largest oracle and cross-kernel differences of the newly covered ones "
-             "(`tests/test_gpu_bellman_matrix.py`) and the outcome of two numerically perturbed scratch builds.", ""]
+             "(`tests/test_gpu_bellman_matrix.py`) and the outcome of two numerically perturbed scratch builds.",
+             "* `network_parity.md`: the twelve `k_nn_check_mfma<layers, d>` instantiations of `sl_nn.hip` with the test that "
+             "reaches each, V, grad V and the sweep records against the network in extended precision "
+             "(`tests/np_network_truth.py`, `tests/test_gpu_network_matrix.py`) per case, the device `sl_tanh` in ulp per "
+             "segment, and the outcome of two numerically perturbed scratch builds.", ""]
     for key in sorted(by_round):
         text.append("* %s: %s" % (key, ", ".join("`%s`" % n for n in by_round[key])))
     with open(os.path.join(P, "README.md"), "w") as f:
