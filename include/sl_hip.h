@@ -699,6 +699,44 @@ SL_API int  sl_tri_param_grad(sl_ctx* ctx, int slot, int64_t n, const double* d_
 SL_API int  sl_decrease_gradient(sl_ctx* ctx, int64_t n, const double* d_points, const double* d_actions,
                     double* d_grad, double* d_constraint, double* d_terms);
 
+/* ---- actor-critic with a NeuralNetwork value function (examples/reinforcement_learning_pendulum.ipynb cells
+ * 16, 31, 34, 48; examples/reinforcement_learning_cartpole.ipynb cell 15): with u = pi(x), x+ = f(x, u), z = [x, u]
+ *   target = stop_gradient(r(z) + gamma V(x+))
+ *   value objective  = reduce |V(x) - target|          (minimised over the value network's parameters)
+ *   policy objective = reduce (r(z) + gamma V(x+))      (maximised over the policy's parameters)
+ * The context's one network slot belongs to the policy (sl_policy_network_set), so both calls are stateless about
+ * the value network: nlayers, h_dims [nlayers + 1], h_activations, h_has_bias (may be NULL: none) and output_scale
+ * as sl_policy_network_set takes them (widths <= 64, at most SL_MAX_NN_LAYERS layers), and d_params = ONE device
+ * array of the parameters in the order sl_policy_network_set packs its own: W_0, b_0, W_1, b_1, ..., W_l [in][out]
+ * row-major, a bias only for the layers that have one.  The caller owns d_params.
+ * sl_critic_batch: under the dynamics (SL_DYN_PENDULUM, SL_DYN_CARTPOLE with their action tangent carried through
+ *   the ten Euler sub-steps, SL_DYN_LINEAR), the quadratic reward and gamma of sl_model_set - its value slot is
+ *   ignored - for the n states d_states [n][d] and actions d_actions [n][m] (explicit: the caller evaluates the
+ *   policy once, e.g. sl_eval_points, so every policy kind and a saturation work), and a value network d -> 1:
+ *     d_next [n][d] (may be NULL) = x+, bit for bit the successor of sl_eval_points(SL_EVAL_DYNAMICS)
+ *     d_value [n] = V(x),  d_q [n] = q = r + gamma V(x+)
+ *     d_dq_du [n][m] (may be NULL): dq/du_a = [(P + P^T) z]_{d+a} + gamma sum_k g_k dx+_k/du_a, g = dV/dx at x+ by
+ *       the transposed chain (activation derivatives as sl_policy_param_grad: relu' = 1 for a pre-activation > 0)
+ *     d_coeff [n] (may be NULL) = w sign(V(x) - q), sign(0) = 0, w = 1/n (SL_REDUCE_MEAN) or 1 (SL_REDUCE_SUM):
+ *       d value objective / d V(x_i) with the target held constant
+ *     d_sums [2] = {sum_i |V(x_i) - q_i|, sum_i q_i}, unscaled
+ *   One sample per thread; workgroups write partial sums to context scratch and a second kernel adds them in
+ *   ascending order: no atomics, the same bits at every call.  SL_DYN_GP: SL_ERR_UNSUPPORTED (sl_action_gradient
+ *   serves GP models with a value table).  n == 0, a width above 64, another output width than 1, and a network
+ *   or Euler model whose dimensions are not the model's: SL_ERR_INVALID.
+ * sl_dense_param_grad: d_out = sum_i sum_o d_coeff[i][o] d net_o(p_i)/d theta for the network of the arguments,
+ *   flat in the order of d_params (d = its input width, at most SL_MAX_STATE_DIM; d_points [n][d], d_coeff
+ *   [n][outputs]): the kernel of sl_policy_param_grad on a description built from the arguments - for the same
+ *   network the two calls return identical bits.  No sl_model_set needed. */
+enum sl_reduction { SL_REDUCE_MEAN = 0, SL_REDUCE_SUM = 1 };
+SL_API int  sl_critic_batch(sl_ctx* ctx, int nlayers, const int32_t* h_dims, const int32_t* h_activations,
+                    const int32_t* h_has_bias, double output_scale, const double* d_params, int64_t n,
+                    const double* d_states, const double* d_actions, int reduction, double* d_next,
+                    double* d_value, double* d_q, double* d_dq_du, double* d_coeff, double* d_sums);
+SL_API int  sl_dense_param_grad(sl_ctx* ctx, int nlayers, const int32_t* h_dims, const int32_t* h_activations,
+                    const int32_t* h_has_bias, double output_scale, const double* d_params, int64_t n, int d,
+                    const double* d_points, const double* d_coeff, double* d_out);
+
 /* ---- multi-GPU collectives directly on RCCL ----------------------------- *
  * For callers without torch.distributed (the Python package issues the same exchanges through
  * torch.distributed, backend "nccl" = RCCL).  One communicator per context, one rank per GPU; every

@@ -9,8 +9,9 @@ from .configuration import config
 from .functions import *          # noqa: F401,F403
 from .lyapunov import *           # noqa: F401,F403
 from .reinforcement_learning import *   # noqa: F401,F403
-from . import utilities, distributed, kernels, training
+from .actor_critic import *       # noqa: F401,F403
+from . import utilities, distributed, kernels, training, actor_critic
 from .utilities import compute_roa, compute_trajectory, reward_rollout
 from .training import (balanced_class_weights, policy_improvement_step, pretraining_step,
-                       roa_classification_step)
+                       roa_classification_step, supervised_value_step, value_function_step)
 from ._hip import HipEngineError

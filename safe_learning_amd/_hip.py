@@ -113,6 +113,7 @@ class ValueSolveStats(C.Structure):
 
 
 SOLVE_GMRES, SOLVE_JACOBI = 0, 1
+REDUCTIONS = {'mean': 0, 'sum': 1}          # enum sl_reduction
 
 
 # sl_sweep_result as int64 words (a torch int64[8] tensor backs it on the device)
@@ -216,6 +217,10 @@ SIGNATURES = {
     "sl_tri_param_grad": (_int, (_vp, _int, _i64, _vp, _vp, _vp)),
     # the Lyapunov penalty of future_values, differentiated
     "sl_decrease_gradient": (_int, (_vp, _i64, _vp, _vp, _vp, _vp, _vp)),
+    # actor-critic with a NeuralNetwork value function
+    "sl_critic_batch": (_int, (_vp, _int, _int32_p, _int32_p, _int32_p, _dbl, _vp, _i64, _vp, _vp, _int, _vp, _vp, _vp,
+                               _vp, _vp, _vp)),
+    "sl_dense_param_grad": (_int, (_vp, _int, _int32_p, _int32_p, _int32_p, _dbl, _vp, _i64, _int, _vp, _vp, _vp)),
     # RCCL collectives
     "sl_comm_unique_id": (_int, (C.c_char_p,)),
     "sl_comm_init": (_int, (_vp, C.c_char_p, _int, _int)),
@@ -684,6 +689,33 @@ class Context(object):
         at ``n`` points under the uploaded model (``d_actions=None``: the policy's actions)."""
         self.lib.sl_decrease_gradient(self.handle, int(n), _ptr(d_points), _ptr(d_actions), _ptr(d_grad),
                                       _ptr(d_constraint), _ptr(d_terms))
+
+    @staticmethod
+    def _dense_description(dims, activations, has_bias):
+        """The host arrays of a dense network's description (kept alive by the caller for the call)."""
+        arrays = [np.ascontiguousarray(v, dtype=np.int32) for v in (dims, activations, has_bias)]
+        if len(arrays[0]) != len(arrays[1]) + 1 or len(arrays[2]) != len(arrays[1]):
+            raise ValueError('a network of %d layers needs %d widths and %d bias flags'
+                             % (len(arrays[1]), len(arrays[1]) + 1, len(arrays[1])))
+        return arrays, [a.ctypes.data_as(_int32_p) for a in arrays]
+
+    def critic_batch(self, dims, activations, has_bias, output_scale, d_params, n, d_states, d_actions, reduction,
+                     d_value, d_q, d_sums, d_next=None, d_dq_du=None, d_coeff=None):
+        """``sl_critic_batch``: per sample ``V(x)``, ``q = r + gamma V(x+)``, optionally ``x+``, ``dq/du`` and the
+        TD coefficient ``w sign(V(x) - q)``, and ``d_sums = (sum |V(x) - q|, sum q)`` under the uploaded model,
+        for the value network ``(dims, activations, has_bias, output_scale)`` with its packed parameters in
+        ``d_params``.  ``reduction``: ``'mean'`` or ``'sum'``."""
+        keep, (pd, pa, pb) = self._dense_description(dims, activations, has_bias)
+        self.lib.sl_critic_batch(self.handle, len(keep[1]), pd, pa, pb, float(output_scale), _ptr(d_params), int(n),
+                                 _ptr(d_states), _ptr(d_actions), REDUCTIONS[reduction], _ptr(d_next), _ptr(d_value),
+                                 _ptr(d_q), _ptr(d_dq_du), _ptr(d_coeff), _ptr(d_sums))
+
+    def dense_param_grad(self, dims, activations, has_bias, output_scale, d_params, n, d, d_points, d_coeff, d_out):
+        """``sl_dense_param_grad``: ``sum_i sum_o coeff[i][o] d net_o(p_i)/d theta`` of the network described by the
+        arguments, flat in the order of ``d_params`` (``W_0, b_0, W_1, b_1, ...``)."""
+        keep, (pd, pa, pb) = self._dense_description(dims, activations, has_bias)
+        self.lib.sl_dense_param_grad(self.handle, len(keep[1]), pd, pa, pb, float(output_scale), _ptr(d_params),
+                                     int(n), int(d), _ptr(d_points), _ptr(d_coeff), _ptr(d_out))
 
     def nn_train_scratch(self):
         """``sl_debug_nn_train_scratch`` -> (bytes of the scratch area, its guard zones are intact)."""

@@ -8,6 +8,11 @@
 // ctx->stream (k_sum_slices, sl_policy_grad.hip): what makes the parameter gradients the same bits at every call
 int sl_sum_slices(sl_ctx* ctx, const double* partials, int nblocks, int total, double* out);
 
+// k_policy_param_grad (sl_policy_grad.hip) for a network description the caller has checked (widths, layer count,
+// d = net.dims[0] <= SL_MAX_STATE_DIM, n >= 1, non-null pointers), then sl_sum_slices into d_grad
+int sl_param_grad_launch(sl_ctx* ctx, const SlPolicyNet& net, int64_t n, int d, const double* d_points,
+                         const double* d_coeff, double* d_grad);
+
 // The checks sl_action_gradient and sl_decrease_gradient have in common (`who`: the entry point, for the
 // message), in the order both call them, each with its own checks in between.
 static inline int sl_point_grad_arguments(sl_ctx* ctx, const char* who, int64_t n, const double* d_grad) {

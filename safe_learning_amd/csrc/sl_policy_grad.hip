@@ -279,20 +279,10 @@ int sl_sum_slices(sl_ctx* ctx, const double* partials, int nblocks, int total, d
     return SL_OK;
 }
 
-extern "C" int sl_policy_param_grad(sl_ctx* ctx, int64_t n, int d, const double* d_points, const double* d_coeff,
-                                    double* d_grad) {
-    if (!ctx) return sl_fail(nullptr, SL_ERR_INVALID, "sl_policy_param_grad: NULL context");
-    const SlPolicyNet& net = ctx->pnet;
-    if (!net.set) return sl_fail(ctx, SL_ERR_INVALID, "sl_policy_param_grad: network policy not set "
-                                                      "(sl_policy_network_set)");
-    if (n <= 0) return sl_fail(ctx, SL_ERR_INVALID, "sl_policy_param_grad: n = %lld points", (long long)n);
-    if (d != net.dims[0])
-        return sl_fail(ctx, SL_ERR_INVALID, "sl_policy_param_grad: points of %d columns, the network takes %d "
-                       "inputs", d, net.dims[0]);
-    if (d < 1 || d > SL_MAX_STATE_DIM)
-        return sl_fail(ctx, SL_ERR_INVALID, "sl_policy_param_grad: input width %d outside [1,%d]", d,
-                       SL_MAX_STATE_DIM);
-    if (!d_points || !d_coeff || !d_grad) return sl_fail(ctx, SL_ERR_INVALID, "sl_policy_param_grad: NULL argument");
+// k_policy_param_grad on a checked network description, then the slices in order (sl_policy_param_grad: the
+// context's policy network; sl_dense_param_grad, sl_critic.hip: a description built from its arguments)
+int sl_param_grad_launch(sl_ctx* ctx, const SlPolicyNet& net, int64_t n, int d, const double* d_points,
+                         const double* d_coeff, double* d_grad) {
     SL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const int L = net.nlayers;
     int total = net.koff[L - 1] + net.dims[L - 1] * net.dims[L];
@@ -311,6 +301,23 @@ extern "C" int sl_policy_param_grad(sl_ctx* ctx, int64_t n, int d, const double*
     });
     if (rc) return rc;
     return sl_sum_slices(ctx, partials, (int)blocks, total, d_grad);
+}
+
+extern "C" int sl_policy_param_grad(sl_ctx* ctx, int64_t n, int d, const double* d_points, const double* d_coeff,
+                                    double* d_grad) {
+    if (!ctx) return sl_fail(nullptr, SL_ERR_INVALID, "sl_policy_param_grad: NULL context");
+    const SlPolicyNet& net = ctx->pnet;
+    if (!net.set) return sl_fail(ctx, SL_ERR_INVALID, "sl_policy_param_grad: network policy not set "
+                                                      "(sl_policy_network_set)");
+    if (n <= 0) return sl_fail(ctx, SL_ERR_INVALID, "sl_policy_param_grad: n = %lld points", (long long)n);
+    if (d != net.dims[0])
+        return sl_fail(ctx, SL_ERR_INVALID, "sl_policy_param_grad: points of %d columns, the network takes %d "
+                       "inputs", d, net.dims[0]);
+    if (d < 1 || d > SL_MAX_STATE_DIM)
+        return sl_fail(ctx, SL_ERR_INVALID, "sl_policy_param_grad: input width %d outside [1,%d]", d,
+                       SL_MAX_STATE_DIM);
+    if (!d_points || !d_coeff || !d_grad) return sl_fail(ctx, SL_ERR_INVALID, "sl_policy_param_grad: NULL argument");
+    return sl_param_grad_launch(ctx, net, n, d, d_points, d_coeff, d_grad);
 }
 
 // =============================================================================================

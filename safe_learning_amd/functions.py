@@ -1000,6 +1000,33 @@ class NeuralNetwork(DeterministicFunction):
         builder._write_policy(_hip.ModelDesc(), self)
         return ctx
 
+    def _description(self):
+        """``(dims, activation codes, bias flags)`` of the chain, as the engine's stateless calls take them
+        (``sl_critic_batch``, ``sl_dense_param_grad``)."""
+        if self.input_dim is None:
+            raise ValueError('the network has no parameters yet: give input_dim or parameters')
+        nl = len(self.layers)
+        return ([self.input_dim] + self.layers, [self._ACTIVATIONS[a] for a in self.nonlinearities],
+                [int(self.use_bias and l < nl - 1) for l in range(nl)])
+
+    def _device_parameters(self, ctx):
+        """The parameters as ONE device tensor in the order ``W_0, b_0, W_1, b_1, ...`` (what
+        ``sl_policy_network_set`` packs on its side), copied again only when ``_version`` moved."""
+        import torch
+        key = (self._version, str(ctx.torch_device))
+        cached = getattr(self, '_device_copy', None)
+        if cached is None or cached[0] != key:
+            flat = np.concatenate([np.asarray(p, dtype=np.float64).ravel() for p in self._parameters])
+            cached = (key, torch.from_numpy(flat).to(ctx.torch_device))
+            self._device_copy = cached
+        return cached[1]
+
+    def _unflatten(self, flat):
+        """A flat array in the order of ``_device_parameters`` as a list shaped like ``parameters``."""
+        shapes = self._shapes()
+        offsets = np.concatenate(([0], np.cumsum([int(np.prod(shape)) for shape in shapes])))
+        return [flat[offsets[k]:offsets[k + 1]].reshape(shape).copy() for k, shape in enumerate(shapes)]
+
     def parameter_gradient(self, points, coefficients):
         """``sum_i sum_o coefficients[i, o] * d policy_o(points[i]) / d theta`` for every array
         ``theta`` of ``parameters`` (a list shaped like ``parameters``): what

@@ -14,7 +14,8 @@ import numpy as np
 
 from . import _hip
 
-__all__ = ['balanced_class_weights', 'pretraining_step', 'roa_classification_step', 'policy_improvement_step']
+__all__ = ['balanced_class_weights', 'pretraining_step', 'roa_classification_step', 'policy_improvement_step',
+           'value_function_step', 'supervised_value_step']
 
 
 def _check_single_process():
@@ -157,4 +158,48 @@ def policy_improvement_step(rl, states, learning_rate, reduction='mean', lyapuno
             policy.parameters = [w + rate * g for w, g in zip(policy.parameters, gradient)]
         else:
             policy.parameters = policy.parameters + rate * gradient
+    return objective
+
+
+def value_function_step(ac, states, learning_rate, scaling=1., reduction='mean', policy=None):
+    """One gradient-descent step of the critic of an ``ActorCritic`` on ``scaling * reduce_i |V(x_i) -
+    target_i|``, ``target = stop_gradient(r(x, u) + gamma V(f(x, u)))`` at ``u = policy(x)`` - the
+    ``optimizer.minimize(value_objective, var_list=value_function.parameters)`` of
+    ``examples/reinforcement_learning_pendulum.ipynb`` cells 34/48 and ``reinforcement_learning_cartpole.ipynb``
+    cell 15: ``theta <- theta - learning_rate * scaling * gradient``.  ``policy=`` evaluates another policy than
+    ``ac.policy`` (the pendulum notebook's cell 16 fits the value function of a fixed saturated LQR policy).
+    Returns the UNSCALED objective before the step; ``learning_rate=None`` evaluates it only."""
+    _check_single_process()
+    objective, gradient = ac.value_gradient(states, reduction, policy=policy)
+    if learning_rate is not None:
+        network, step = ac.value_function, float(learning_rate) * float(scaling)
+        network.parameters = [w - step * g for w, g in zip(network.parameters, gradient)]
+    return objective
+
+
+def supervised_value_step(value_function, states, targets, learning_rate):
+    """One gradient-descent step of a ``NeuralNetwork`` with one output on ``mean |V(states) - targets|``
+    (the supervised pre-training of ``examples/reinforcement_learning_pendulum.ipynb`` cell 31): ``V`` from the
+    point kernels, the coefficients ``sign(V - y) / n`` formed on the device (``sign(0) = 0``), the sum over the
+    batch by ``parameter_gradient``.  Returns the objective before the step; ``learning_rate=None`` evaluates it
+    only."""
+    import torch
+    from . import _evaluate
+    from .functions import NeuralNetwork
+    _check_single_process()
+    if type(value_function) is not NeuralNetwork or value_function.negate:
+        raise TypeError('value_function must be a bare NeuralNetwork')
+    if value_function.output_dim != 1:
+        raise ValueError('a value function has one output, this network %d' % value_function.output_dim)
+    ctx = _evaluate._ctx()
+    d_states = _states(value_function, ctx, states)
+    n = d_states.shape[0]
+    d_targets = _column(ctx, targets, n, 'targets')
+    error = _evaluate.policy(value_function, d_states).reshape(-1) - d_targets
+    objective = float(error.abs().sum()) / n
+    if learning_rate is not None:
+        coeff = (torch.sign(error) * (1.0 / n)).reshape(-1, 1)
+        gradient = value_function.parameter_gradient(d_states, coeff)
+        rate = float(learning_rate)
+        value_function.parameters = [w - rate * g for w, g in zip(value_function.parameters, gradient)]
     return objective

@@ -141,6 +141,10 @@ def main():
              "their tolerances, a safe policy-improvement step at the notebook's shape beside the unpenalised one and "
              "`sl_decrease_gradient` under a 1024-point RBF head against the FP64 matrix peak (`tools/safe_policy_probe.py`; "
              "DESIGN.md 4.5c).",
+             "* `actor_critic.md`, `actor_critic_probe.jsonl`: actor-critic with a NeuralNetwork value function (`k_critic_batch`, "
+             "csrc/sl_critic.hip, `sl_dense_param_grad`): registers / scratch / LDS, the measured ratios of the GPU tests against "
+             "their tolerances, a critic and an actor step at the cart-pole notebook's batch and at 2^20 samples, split per call, "
+             "beside torch autograd (`tools/actor_critic_probe.py`; DESIGN.md 4.5d).",
              "* `gp_posterior_truth.md`: the GP posterior of `k_gp_sweep4`, `k_gp_sweep` and `k_gp_small` against the posterior in "
              "extended precision (`tests/np_gp_truth.py`): per case cond(K), the oracle's own error, a NumPy restatement of the "
              "engine's formula and the engine's measured error (`tests/test_gpu_gp_truth.py`; DESIGN.md 6 (iv)).",
