@@ -59,7 +59,8 @@ enum sl_dynamics_kind {
     SL_DYN_LINEAR   = 1,    /* [x,u] M^T            (functions.py:1567-1583)                */
     SL_DYN_PENDULUM = 2,    /* examples/utilities.py:242-289, 10 Euler sub-steps            */
     SL_DYN_CARTPOLE = 3,    /* examples/utilities.py:387-437, 10 Euler sub-steps            */
-    SL_DYN_GP       = 4     /* GP posterior (functions.py:417-458, 507-515, 278-291)        */
+    SL_DYN_GP       = 4,    /* GP posterior (functions.py:417-458, 507-515, 278-291)        */
+    SL_DYN_POLYNOMIAL = 5   /* term table of sl_dynamics_polynomial_set (VanDerPol: examples/utilities.py:440-519) */
 };
 enum sl_value_kind {
     SL_V_QUADRATIC  = 1,    /* x P x^T              (functions.py:1534-1539)                */
@@ -169,6 +170,26 @@ SL_API int  sl_model_set(sl_ctx* ctx, const sl_model_desc* h_model);
  * with new values is the same description.  Call this after such an edit (before the next sweep);
  * handing in another pointer (sl_model_set, sl_tri_set_table) needs no call. */
 SL_API int  sl_policy_touch(sl_ctx* ctx);
+
+/* Polynomial dynamics (SL_DYN_POLYNOMIAL): a vector field given as data, nterms terms
+ *     coef * prod_q z_q^e_q,   z = [x, u] (d + m entries),
+ * term t adding to output row h_rows[t] in [0, d).  h_exponents is [nterms][SL_MAX_INPUT_DIM] (entries at
+ * q >= d + m must be 0); the sum of a term's exponents is at most SL_POLY_MAX_DEGREE, nterms at most
+ * SL_POLY_MAX_TERMS (0: the zero field); a row may have no term.  The table is copied (sorted by row, the
+ * caller's order kept within a row).  One call x -> x+ of the dynamics (csrc/sl_polynomial.h states the
+ * operation order, multiplications and additions only, powers by repeated multiplication):
+ *     substeps > 0:  `substeps` explicit-Euler steps z_i <- z_i + h * p_i(z), all rows from the same z,
+ *                    the action entries held (h = dt / substeps is the caller's);
+ *     substeps = 0:  the polynomial is the map itself, x+_i = p_i(z) (h is not used).
+ * sl_dynamics_desc's normalize / tx / tx_inv / tu apply as for the pendulum: z = [x * tx, u * tu] going in,
+ * x+ * tx_inv coming out; its other fields are not read.  sl_model_set accepts kind SL_DYN_POLYNOMIAL only
+ * when the table's d and m are the model's.  A new table is a new model: everything the context derived
+ * from the dynamics (successor cache, policy-select arrays) is dropped.  Action tangents are not implemented:
+ * sl_critic_batch, sl_action_gradient and sl_decrease_gradient return SL_ERR_UNSUPPORTED for this kind. */
+#define SL_POLY_MAX_TERMS  64
+#define SL_POLY_MAX_DEGREE 8      /* total degree of one term: at most 8 multiplications per term */
+SL_API int  sl_dynamics_polynomial_set(sl_ctx* ctx, int d, int m, int nterms, const int32_t* h_rows,
+                    const double* h_coef, const uint8_t* h_exponents, int substeps, double h);
 
 /* GP head `head` of the dynamics (FunctionStack: one head per output column,
  * functions.py:278-291; a shared-kernel multi-output GPRCached is one head with dout = D).

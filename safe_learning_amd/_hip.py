@@ -24,7 +24,8 @@ MAX_SIMPLICES = 32
 # error codes and enum values of include/sl_hip.h
 OK, ERR_INVALID, ERR_HIP, ERR_UNSUPPORTED, ERR_NOMEM = 0, -1, -2, -3, -4
 POLICY_LINEAR, POLICY_CONST, POLICY_TABLE, POLICY_TRI, POLICY_NETWORK = 1, 2, 3, 4, 5
-DYN_LINEAR, DYN_PENDULUM, DYN_CARTPOLE, DYN_GP = 1, 2, 3, 4
+DYN_LINEAR, DYN_PENDULUM, DYN_CARTPOLE, DYN_GP, DYN_POLYNOMIAL = 1, 2, 3, 4, 5
+POLY_MAX_TERMS, POLY_MAX_DEGREE = 64, 8
 V_QUADRATIC, V_TRI, V_NETWORK = 1, 2, 3
 LIP_CONST, LIP_ABS_LINEAR, LIP_NORM_LINEAR, LIP_ABS_GRAD, LIP_NORM_GRAD = 0, 1, 2, 3, 4
 LF_CONST, LF_AFFINE_NORM1 = 0, 1
@@ -143,6 +144,8 @@ SIGNATURES = {
     # model upload
     "sl_model_set": (_int, (_vp, C.POINTER(ModelDesc))),
     "sl_policy_touch": (_int, (_vp,)),
+    "sl_dynamics_polynomial_set": (_int, (_vp, _int, _int, _int, _int32_p, c_double_p, C.POINTER(C.c_uint8), _int,
+                                          _dbl)),
     "sl_gp_set_head": (_int, (_vp, _int, _int, _int, _int, _int, c_double_p, c_double_p, c_double_p, _dbl,
                               c_double_p)),
     "sl_gp_set_head_kernel": (_int, (_vp, _int, _int, _int, _int, _int, c_double_p, c_double_p, c_double_p,
@@ -369,6 +372,21 @@ class Context(object):
     def policy_touch(self):
         """``sl_policy_touch``: the policy table the model points at was overwritten in place."""
         self.lib.sl_policy_touch(self.handle)
+
+    def dynamics_polynomial_set(self, d, m, rows, coef, exponents, substeps, h):
+        """``sl_dynamics_polynomial_set``: the term table of ``DYN_POLYNOMIAL`` - ``rows [nterms]`` output rows,
+        ``coef [nterms]``, ``exponents [nterms, d + m]`` (small non-negative integers)."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        coef, pc = _as_c(np.reshape(coef, -1))
+        given = np.asarray(exponents, dtype=np.int64).reshape(len(rows), -1)
+        if len(coef) != len(rows) or given.shape[1] > MAX_INPUT_DIM or (given < 0).any() or (given > 255).any():
+            raise ValueError("polynomial terms: %d rows, %d coefficients, exponents of shape %s (at most %d columns, "
+                             "entries in 0..255)" % (len(rows), len(coef), given.shape, MAX_INPUT_DIM))
+        expo = np.zeros((len(rows), MAX_INPUT_DIM), dtype=np.uint8)
+        expo[:, :given.shape[1]] = given
+        self.lib.sl_dynamics_polynomial_set(self.handle, int(d), int(m), len(rows),
+                                            rows.ctypes.data_as(_int32_p), pc,
+                                            expo.ctypes.data_as(C.POINTER(C.c_uint8)), int(substeps), float(h))
 
     def gp_set_head(self, head, X, Linv, alpha, col0, variance, lengthscales):
         X, pX = _as_c(X)

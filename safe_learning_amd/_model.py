@@ -12,7 +12,7 @@ from . import _hip
 from .functions import (AbsFunction, CartPole, ConstantFunction, FunctionStack,
                         GaussianProcess, Gradient, InvertedPendulum, LinearSystem, LyapunovNetwork,
                         NeuralNetwork,
-                        Norm1Function, QuadraticFunction, Saturation, Triangulation, _gp_heads,
+                        Norm1Function, PolynomialSystem, QuadraticFunction, Saturation, Triangulation, _gp_heads,
                         _is_plain_rbf)
 
 
@@ -38,6 +38,7 @@ class ModelBuilder(object):
         self._policy_table = None
         self._policy_source = None         # (tensor, its state) of a tensor policy used in place
         self._policy_net_signature = None
+        self._poly_signature = None        # version token of the PolynomialSystem whose table the context holds
 
     # ---- pieces --------------------------------------------------------------------------
     def _write_policy(self, desc, policy):
@@ -138,6 +139,14 @@ class ModelBuilder(object):
                     dd.matrix[i][j] = float(dynamics.matrix[i, j])
         elif isinstance(dynamics, (InvertedPendulum, CartPole)):
             dynamics._write_dynamics(dd)
+        elif isinstance(dynamics, PolynomialSystem):
+            if dynamics.state_dim != d:
+                raise ValueError('%s has %d states, the grid has %d dimensions'
+                                 % (type(dynamics).__name__, dynamics.state_dim, d))
+            if dynamics.action_dim != m:
+                raise ValueError('%s takes %d actions, the policy gives %d'
+                                 % (type(dynamics).__name__, dynamics.action_dim, m))
+            dynamics._write_dynamics(dd, self)       # (uploads the term table when it is a new one)
         elif isinstance(dynamics, (GaussianProcess, FunctionStack)):
             dd.kind = _hip.DYN_GP
             heads, beta = _gp_heads(dynamics)
@@ -150,7 +159,8 @@ class ModelBuilder(object):
                             dd.matrix[col0 + r][j] = float(mat[r, j])
             self._upload_gp(heads, beta, d + m)
         else:
-            raise TypeError('unsupported dynamics spec %r' % (dynamics,))
+            raise TypeError('unsupported dynamics spec %r: use LinearSystem, InvertedPendulum, CartPole, '
+                            'PolynomialSystem, VanDerPol, GaussianProcess or a FunctionStack of them' % (dynamics,))
 
     def _upload_gp(self, heads, beta, p):
         # _version / _table_version are process-wide unique tokens (functions._TOKENS), never reused.

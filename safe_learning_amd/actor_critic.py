@@ -21,7 +21,7 @@ from . import _hip
 from . import distributed as dist_utils
 from ._model import ModelBuilder
 from .functions import (CartPole, ConstantFunction, InvertedPendulum, LinearSystem, NeuralNetwork,
-                        QuadraticFunction, Triangulation)
+                        PolynomialSystem, QuadraticFunction, Triangulation)
 
 __all__ = ['ActorCritic', 'CriticEvaluation']
 
@@ -62,6 +62,9 @@ class ActorCritic(object):
             d, m = dynamics.output_dim, dynamics.input_dim - dynamics.output_dim
             if m < 1:
                 raise ValueError('linear dynamics of %d x %d have no action columns' % dynamics.matrix.shape)
+        elif isinstance(dynamics, PolynomialSystem):
+            raise TypeError('dynamics must be InvertedPendulum, CartPole or LinearSystem: a PolynomialSystem (%s) has '
+                            'no action tangent in the engine yet' % type(dynamics).__name__)
         else:
             raise TypeError('dynamics must be InvertedPendulum, CartPole or LinearSystem, not %s (GP models: '
                             'PolicyIteration.action_gradient with a Triangulation value function)'

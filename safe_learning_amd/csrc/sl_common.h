@@ -92,6 +92,9 @@ struct sl_ctx {
     double* d_tri_points[2] = {nullptr, nullptr};
     SlNet h_net;
     SlNet* d_net = nullptr;
+    SlPolyTable h_poly = {};       // term table of SL_DYN_POLYNOMIAL (sl_dynamics_polynomial_set)
+    SlPolyTable* d_poly = nullptr; // its device copy: the model the kernels get points at it
+    bool poly_set = false;
     double* d_net_kernels = nullptr;
 
     void* d_scratch = nullptr;         // grown on demand (sl_eval_points)

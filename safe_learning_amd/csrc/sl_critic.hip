@@ -158,6 +158,9 @@ extern "C" int sl_critic_batch(sl_ctx* ctx, int nlayers, const int32_t* h_dims, 
     if (kind == SL_DYN_GP)
         return sl_fail(ctx, SL_ERR_UNSUPPORTED, "%s: GP dynamics are not implemented here; sl_action_gradient serves "
                        "GP models with a value table", who);
+    if (kind == SL_DYN_POLYNOMIAL)
+        return sl_fail(ctx, SL_ERR_UNSUPPORTED, "%s: polynomial dynamics (SL_DYN_POLYNOMIAL) have no action tangent "
+                       "in the engine yet", who);
     if (kind != SL_DYN_LINEAR && kind != SL_DYN_PENDULUM && kind != SL_DYN_CARTPOLE)
         return sl_fail(ctx, SL_ERR_UNSUPPORTED, "%s: dynamics kind %d", who, kind);
     // (sl_model_set has checked the Euler models' dimensions: (2, 1) and (4, 1))

@@ -155,6 +155,7 @@ extern "C" int sl_ctx_destroy(sl_ctx* ctx) {
     if (ctx->succ.d) (void)hipFree(ctx->succ.d);
     if (ctx->succ.d_select) (void)hipFree(ctx->succ.d_select);
     if (ctx->d_records) (void)hipFree(ctx->d_records);
+    if (ctx->d_poly) (void)hipFree(ctx->d_poly);
     (void)sl_timing_configure(ctx, 0);
     (void)hipFree(ctx->d_partials);
     (void)hipFree(ctx->d_partial_counts);
@@ -257,8 +258,17 @@ extern "C" int sl_model_set(sl_ctx* ctx, const sl_model_desc* h_model) {
         return sl_fail(ctx, SL_ERR_INVALID, "state+action dimension %d > %d", M.in_dim,
                        SL_MAX_INPUT_DIM);
     const int dk = M.m.dynamics.kind;
-    if (dk < SL_DYN_LINEAR || dk > SL_DYN_GP)
+    if (dk < SL_DYN_LINEAR || dk > SL_DYN_POLYNOMIAL)
         return sl_fail(ctx, SL_ERR_INVALID, "unknown dynamics kind %d", dk);
+    if (dk == SL_DYN_POLYNOMIAL) {
+        if (!ctx->poly_set)
+            return sl_fail(ctx, SL_ERR_INVALID, "polynomial dynamics (SL_DYN_POLYNOMIAL) without a term table: call "
+                                                "sl_dynamics_polynomial_set first");
+        if (ctx->h_poly.d != M.m.grid.d || ctx->h_poly.m != p.m)
+            return sl_fail(ctx, SL_ERR_INVALID, "polynomial dynamics: the term table is for %d states and %d actions, "
+                           "the model has %d and %d", ctx->h_poly.d, ctx->h_poly.m, M.m.grid.d, p.m);
+        M.poly = ctx->d_poly;
+    }
     if (dk == SL_DYN_PENDULUM && (M.m.grid.d != 2 || p.m != 1))
         return sl_fail(ctx, SL_ERR_INVALID, "pendulum dynamics need d=2, m=1");
     if (dk == SL_DYN_CARTPOLE && (M.m.grid.d != 4 || p.m != 1))
@@ -292,6 +302,27 @@ extern "C" int sl_model_set(sl_ctx* ctx, const sl_model_desc* h_model) {
     // description before every sweep, as the Python layer does, costs nothing here).
     ctx->h_model = M;
     ctx->model_set = true;
+    return SL_OK;
+}
+
+// The term table of SL_DYN_POLYNOMIAL.  It is not part of the model description's bytes, so the
+// comparison in sl_model_set cannot see a new one: the token the successor cache and its select
+// arrays are keyed on moves here.
+extern "C" int sl_dynamics_polynomial_set(sl_ctx* ctx, int d, int m, int nterms, const int32_t* h_rows,
+                                          const double* h_coef, const uint8_t* h_exponents, int substeps, double h) {
+    if (!ctx) return sl_fail(nullptr, SL_ERR_INVALID, "sl_dynamics_polynomial_set: NULL context");
+    SlPolyTable table;
+    char msg[200];
+    if (sl_poly_build(&table, d, m, nterms, h_rows, h_coef, h_exponents, substeps, h, msg, sizeof(msg)) != SL_OK)
+        return sl_fail(ctx, SL_ERR_INVALID, "sl_dynamics_polynomial_set: %s", msg);
+    SL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (!ctx->d_poly) SL_HIP_CHECK(ctx, hipMalloc(&ctx->d_poly, sizeof(SlPolyTable)));
+    // launches that read the old table may still be queued: wait for them, then replace it
+    SL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    SL_HIP_CHECK(ctx, hipMemcpy(ctx->d_poly, &table, sizeof(SlPolyTable), hipMemcpyHostToDevice));
+    ctx->h_poly = table;
+    ctx->poly_set = true;
+    ++ctx->dynamics_token;
     return SL_OK;
 }
 
@@ -584,8 +615,11 @@ template <int DT, int MT, int DYN>
 __device__ __forceinline__ void sl_constants_to_vgprs(SlDevModel& L) {
 #define SL_TO_VGPR(x) asm volatile("" : "+v"(x))
     if (DYN != SL_DYN_LINEAR) {
+        // (the polynomial kind reads no coef[]: its terms come from the context's table)
+        if (DYN != SL_DYN_POLYNOMIAL) {
 #pragma unroll
-        for (int q = 0; q < 16; ++q) SL_TO_VGPR(L.m.dynamics.coef[q]);
+            for (int q = 0; q < 16; ++q) SL_TO_VGPR(L.m.dynamics.coef[q]);
+        }
 #pragma unroll
         for (int k = 0; k < DT; ++k) { SL_TO_VGPR(L.m.dynamics.tx[k]); SL_TO_VGPR(L.m.dynamics.tx_inv[k]); }
 #pragma unroll
@@ -881,6 +915,7 @@ static int sweep_det(sl_ctx* ctx, const SlSweepArgs& a, int* blocks) {
         if (!G && D > 0 && dyn == SL_DYN_LINEAR) return launch(std::integral_constant<int, SL_DYN_LINEAR>());
         if (!G && D == 2 && dyn == SL_DYN_PENDULUM) return launch(std::integral_constant<int, SL_DYN_PENDULUM>());
         if (!G && D == 4 && dyn == SL_DYN_CARTPOLE) return launch(std::integral_constant<int, SL_DYN_CARTPOLE>());
+        if (!G && D > 0 && dyn == SL_DYN_POLYNOMIAL) return launch(std::integral_constant<int, SL_DYN_POLYNOMIAL>());
         return launch(std::integral_constant<int, 0>());
     });
 }

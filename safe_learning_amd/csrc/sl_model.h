@@ -12,6 +12,7 @@
 //   policy / linear dyn.  safe_learning/functions.py:1567-1583, saturation :349-354
 //   quadratic V           safe_learning/functions.py:1534-1539
 //   pendulum / cart-pole  examples/utilities.py:242-289 / 387-437
+//   polynomial (VanDerPol) examples/utilities.py:440-519, as a term table (sl_polynomial.h)
 //   threshold             safe_learning/lyapunov.py:265-288
 //   decrease + bound      safe_learning/lyapunov.py:324-376
 #pragma once
@@ -30,6 +31,8 @@
 #define SL_D SL_MAX_STATE_DIM
 #define SL_M SL_MAX_ACTION_DIM
 #define SL_P SL_MAX_INPUT_DIM
+
+#include "sl_polynomial.h"
 
 // Device-side view of one auxiliary grid with a vertex table (Triangulation).
 #define SL_TRI_CODES   64      // 2^(pairs of coordinates), d <= 4
@@ -1176,6 +1179,7 @@ struct SlDevModel {
     SlGridFast    gf;
     int32_t       in_dim;      // d + m
     int32_t       uncertain;   // dynamics returns (mean, error)
+    const SlPolyTable* poly;   // SL_DYN_POLYNOMIAL: the context's term table (device memory in the kernels)
 };
 
 // Dimensions of one kernel instantiation.  Kernels are compiled for fixed (state, action)
@@ -1286,6 +1290,10 @@ SL_HD void sl_dynamics_det(const SlDevModel& M, SlDims n, const double* z, doubl
 #pragma unroll
         for (int q = 0; q < SL_P; ++q) if (q == n.d) u0 = z[q];
         if (kind == SL_DYN_PENDULUM) sl_pendulum(f, z, &u0, nxt); else sl_cartpole(f, z, &u0, nxt);
+        return;
+    }
+    if (kind == SL_DYN_POLYNOMIAL) {
+        sl_polynomial(f, *M.poly, n.d, n.m, z, nxt);
         return;
     }
     sl_rows_dot<SL_D, SL_P>(f.matrix, n.d, n.p, z, nxt);

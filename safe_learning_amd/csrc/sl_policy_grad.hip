@@ -85,6 +85,10 @@ extern "C" int sl_action_gradient(sl_ctx* ctx, int64_t n, const double* d_points
     const char* who = "sl_action_gradient";
     if (const int rc = sl_point_grad_arguments(ctx, who, n, d_grad)) return rc;
     const sl_model_desc& md = ctx->h_model.m;
+    if (md.dynamics.kind == SL_DYN_POLYNOMIAL)
+        return sl_fail(ctx, SL_ERR_UNSUPPORTED, "sl_action_gradient: polynomial dynamics (SL_DYN_POLYNOMIAL) have no "
+                       "action tangent in the engine yet; the action gradient is implemented for linear and GP "
+                       "dynamics");
     if (md.dynamics.kind != SL_DYN_LINEAR && md.dynamics.kind != SL_DYN_GP)
         return sl_fail(ctx, SL_ERR_UNSUPPORTED, "sl_action_gradient: dynamics kind %d; the action gradient is "
                        "implemented for SL_DYN_LINEAR and SL_DYN_GP", md.dynamics.kind);

@@ -59,8 +59,11 @@ template <int DT, int MT, int DYN>
 __device__ __forceinline__ void rollout_constants_to_vgprs(SlDevModel& L) {
 #define SL_TO_VGPR(x) asm volatile("" : "+v"(x))
     if (DYN != SL_DYN_LINEAR) {
+        // (the polynomial kind reads no coef[]: its terms come from the context's table)
+        if (DYN != SL_DYN_POLYNOMIAL) {
 #pragma unroll
-        for (int q = 0; q < 16; ++q) SL_TO_VGPR(L.m.dynamics.coef[q]);
+            for (int q = 0; q < 16; ++q) SL_TO_VGPR(L.m.dynamics.coef[q]);
+        }
 #pragma unroll
         for (int k = 0; k < DT; ++k) { SL_TO_VGPR(L.m.dynamics.tx[k]); SL_TO_VGPR(L.m.dynamics.tx_inv[k]); }
 #pragma unroll
@@ -306,6 +309,11 @@ int launch_any(sl_ctx* ctx, const Args& a) {
     } else if (dyn == SL_DYN_LINEAR && m == 1 && d >= 1 && d <= 4) {
         sl_with_dim<1, 2, 3, 4>(d, [&](auto dt) {
             launch_variant<false, dt, 1, SL_DYN_LINEAR>(ctx, a);
+            return SL_OK;
+        });
+    } else if (dyn == SL_DYN_POLYNOMIAL && m == 1 && d >= 1 && d <= 4) {
+        sl_with_dim<1, 2, 3, 4>(d, [&](auto dt) {
+            launch_variant<false, dt, 1, SL_DYN_POLYNOMIAL>(ctx, a);
             return SL_OK;
         });
     } else {

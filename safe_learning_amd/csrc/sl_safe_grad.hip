@@ -243,6 +243,10 @@ extern "C" int sl_decrease_gradient(sl_ctx* ctx, int64_t n, const double* d_poin
     if (dk == SL_DYN_PENDULUM || dk == SL_DYN_CARTPOLE)
         return sl_fail(ctx, SL_ERR_UNSUPPORTED, "sl_decrease_gradient: Euler dynamics (kind %d); the gradient of the "
                        "Lyapunov penalty is implemented for SL_DYN_GP", dk);
+    if (dk == SL_DYN_POLYNOMIAL)
+        return sl_fail(ctx, SL_ERR_UNSUPPORTED, "sl_decrease_gradient: polynomial dynamics (SL_DYN_POLYNOMIAL) have no "
+                       "action tangent in the engine yet; the gradient of the Lyapunov penalty is implemented for GP "
+                       "dynamics");
     if (dk != SL_DYN_GP)
         return sl_fail(ctx, SL_ERR_UNSUPPORTED, "sl_decrease_gradient: linear dynamics (kind %d) carry no error bound; "
                        "the gradient of the Lyapunov penalty is implemented for SL_DYN_GP", dk);

@@ -47,7 +47,8 @@ _TOKENS = itertools.count(1)
 __all__ = ['GridWorld', 'DimensionError', 'DeterministicFunction', 'UncertainFunction',
            'QuadraticFunction', 'LinearSystem', 'Saturation', 'AbsFunction', 'Norm1Function',
            'AbsGradient', 'Gradient', 'ConstantFunction', 'RBF', 'Matern32', 'Linear', 'GPRCached', 'GaussianProcess',
-           'FunctionStack', 'Triangulation', 'InvertedPendulum', 'CartPole', 'LyapunovNetwork',
+           'FunctionStack', 'Triangulation', 'InvertedPendulum', 'CartPole', 'PolynomialSystem', 'VanDerPol',
+           'LyapunovNetwork',
            'NeuralNetwork']
 
 
@@ -883,6 +884,144 @@ def _write_norm(desc, normalization, inv_norm, d):
         desc.tx[k] = 1.0 if normalization is None else float(normalization[0][k])
         desc.tx_inv[k] = 1.0 if normalization is None else float(inv_norm[0][k])
     desc.tu[0] = 1.0 if normalization is None else float(normalization[1][0])
+
+
+class PolynomialSystem(DeterministicFunction):
+    """Dynamics whose vector field is a polynomial in ``z = [x, u]``, given as data: the way to run a
+    system of one's own (Van der Pol, Duffing, Lotka-Volterra, Lorenz, Taylor models) through the
+    sweeps, rollouts and dynamic programming without a callable.
+
+    ``terms`` holds one list per state, each entry ``(coefficient, exponents)`` with one non-negative
+    integer exponent per entry of ``z`` (``len(exponents) == state_dim + action_dim``): row ``i`` is
+    ``sum coefficient * prod_q z_q ** exponents[q]``.  One call advances the state by
+    ``inner_euler_steps`` explicit-Euler steps of ``dt / inner_euler_steps`` with the action held;
+    ``inner_euler_steps=0`` makes the polynomial the discrete map ``x+ = p(x, u)`` itself.
+    ``normalization = [state_norm, action_norm]`` as for :class:`InvertedPendulum`: inputs and outputs
+    are in normalised coordinates, the polynomial in physical ones.  At most ``_hip.POLY_MAX_TERMS``
+    terms of total degree ``_hip.POLY_MAX_DEGREE`` or less.  The engine evaluates every term by
+    repeated multiplication in the order given (``csrc/sl_polynomial.h``)."""
+
+    _role = 'dynamics'
+
+    def __init__(self, terms, state_dim, action_dim=1, dt=0.01, inner_euler_steps=10, normalization=None):
+        self.state_dim, self.action_dim = int(state_dim), int(action_dim)
+        d, m = self.state_dim, self.action_dim
+        if not 1 <= d <= _hip.MAX_STATE_DIM or not 1 <= m <= _hip.MAX_ACTION_DIM or d + m > _hip.MAX_INPUT_DIM:
+            raise ValueError('PolynomialSystem: %d states and %d actions (the engine takes 1..%d and 1..%d, %d inputs)'
+                             % (d, m, _hip.MAX_STATE_DIM, _hip.MAX_ACTION_DIM, _hip.MAX_INPUT_DIM))
+        self.input_dim, self.output_dim = d + m, d
+        self.dt = float(dt)
+        self.inner_euler_steps = int(inner_euler_steps)
+        if self.inner_euler_steps < 0:
+            raise ValueError('PolynomialSystem: inner_euler_steps must not be negative')
+        terms = [list(row) for row in terms]
+        if len(terms) != d:
+            raise ValueError('PolynomialSystem: %d term lists for %d states (one list per state, [] for none)'
+                             % (len(terms), d))
+        rows, coef, expo = [], [], []
+        for i, row in enumerate(terms):
+            for coefficient, exponents in row:
+                exponents = [int(e) for e in exponents]
+                if len(exponents) != d + m:
+                    raise ValueError('PolynomialSystem: a term of row %d has %d exponents, state_dim + action_dim = %d'
+                                     % (i, len(exponents), d + m))
+                if min(exponents) < 0:
+                    raise ValueError('PolynomialSystem: negative exponent in row %d' % i)
+                if sum(exponents) > _hip.POLY_MAX_DEGREE:
+                    raise ValueError('PolynomialSystem: a term of row %d has total degree %d, the engine takes %d'
+                                     % (i, sum(exponents), _hip.POLY_MAX_DEGREE))
+                rows.append(i)
+                coef.append(float(coefficient))
+                expo.append(exponents)
+        if len(rows) > _hip.POLY_MAX_TERMS:
+            raise ValueError('PolynomialSystem: %d terms, the engine takes %d' % (len(rows), _hip.POLY_MAX_TERMS))
+        self.terms = [[(c, tuple(e)) for r, c, e in zip(rows, coef, expo) if r == i] for i in range(d)]
+        self._rows = np.array(rows, dtype=np.int32)
+        self._coef = np.array(coef, dtype=np.float64)
+        self._expo = np.array(expo, dtype=np.uint8).reshape(len(rows), d + m)
+        self.normalization, self.inv_norm = _normalization(normalization)
+        if self.normalization is not None and (len(self.normalization) != 2 or self.normalization[0].shape != (d,)
+                                               or self.normalization[1].shape != (m,)):
+            raise ValueError('PolynomialSystem: normalization is [state_norm (%d), action_norm (%d)]' % (d, m))
+        self._version = next(_TOKENS)          # a spec is immutable: one upload per context
+
+    @property
+    def step(self):
+        """Length of one Euler sub-step (not used by a discrete map)."""
+        return self.dt / self.inner_euler_steps if self.inner_euler_steps else 0.0
+
+    def ode(self, states, actions=None):
+        """The polynomial itself at physical ``states`` ``[n, state_dim]`` and ``actions``
+        ``[n, action_dim]`` (``None``: zeros), in NumPy: the time derivative, or the next state of a
+        discrete map."""
+        states = np.atleast_2d(np.asarray(states, dtype=config.np_dtype))
+        if actions is None:
+            actions = np.zeros((len(states), self.action_dim), dtype=config.np_dtype)
+        actions = np.atleast_2d(np.asarray(actions, dtype=config.np_dtype))
+        z = np.hstack((states, np.broadcast_to(actions, (len(states), self.action_dim))))
+        out = np.zeros((len(states), self.state_dim), dtype=config.np_dtype)
+        for i, row in enumerate(self.terms):
+            for coefficient, exponents in row:
+                prod = np.full(len(states), coefficient, dtype=config.np_dtype)
+                for q, e in enumerate(exponents):
+                    for _ in range(e):
+                        prod = prod * z[:, q]
+                out[:, i] = out[:, i] + prod
+        return out
+
+    def linearize(self):
+        """``(Ad, Bd)`` about the origin in normalised coordinates: the degree-1 terms under a
+        zero-order hold over ``dt``; for a discrete map (``inner_euler_steps=0``) the degree-1 terms
+        themselves."""
+        d, m = self.state_dim, self.action_dim
+        jac = np.zeros((d, d + m), dtype=config.np_dtype)
+        for i, row in enumerate(self.terms):
+            for coefficient, exponents in row:
+                if sum(exponents) == 1:
+                    jac[i, exponents.index(1)] += coefficient
+        A, B = jac[:, :d], jac[:, d:]
+        if self.normalization is not None:
+            Tx, Tu = np.diag(self.normalization[0]), np.diag(self.normalization[1])
+            Tx_inv = np.diag(self.inv_norm[0])
+            A = np.linalg.multi_dot((Tx_inv, A, Tx))
+            B = np.linalg.multi_dot((Tx_inv, B, Tu))
+        if self.inner_euler_steps == 0:
+            return A, B
+        Ad, Bd, _, _, _ = scipy.signal.cont2discrete((A, B, 0, 0), self.dt, method='zoh')
+        return Ad, Bd
+
+    def _write_dynamics(self, desc, builder):
+        d, m = self.state_dim, self.action_dim
+        desc.kind = _hip.DYN_POLYNOMIAL
+        desc.normalize = 0 if self.normalization is None else 1
+        for k in range(d):
+            desc.tx[k] = 1.0 if self.normalization is None else float(self.normalization[0][k])
+            desc.tx_inv[k] = 1.0 if self.normalization is None else float(self.inv_norm[0][k])
+        for a in range(m):
+            desc.tu[a] = 1.0 if self.normalization is None else float(self.normalization[1][a])
+        if builder._poly_signature != self._version:
+            builder.ctx.dynamics_polynomial_set(d, m, self._rows, self._coef, self._expo, self.inner_euler_steps,
+                                                self.step)
+            builder._poly_signature = self._version
+
+
+class VanDerPol(PolynomialSystem):
+    """Van der Pol oscillator in reverse time, ten explicit-Euler sub-steps
+    (``examples/utilities.py:440-519``): ``x' = -y``, ``y' = x + damping (x^2 - 1) y``.
+    ``normalization`` holds the two state scales.  The reference evaluates it on ``[state, action]``
+    rows with one action column that it drops (``tf.split(state_action, [2, 1])``): here that column
+    is an action no term reads."""
+
+    def __init__(self, damping=1, dt=0.01, normalization=None):
+        self.damping = damping
+        terms = [[(-1.0, (0, 1, 0))],
+                 [(1.0, (1, 0, 0)), (float(damping), (2, 1, 0)), (-float(damping), (0, 1, 0))]]
+        pair = None if normalization is None else [normalization, [1.0]]
+        super(VanDerPol, self).__init__(terms, 2, 1, dt=dt, inner_euler_steps=10, normalization=pair)
+
+    def linearize(self):
+        """``Ad`` of the discretised linearisation in normalised coordinates (``examples/utilities.py:471-487``)."""
+        return super(VanDerPol, self).linearize()[0]
 
 
 # ----------------------------------------------------------------------------------------------

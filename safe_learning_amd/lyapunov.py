@@ -341,10 +341,14 @@ class Lyapunov(object):
         ``LyapunovNetwork`` is not differentiated."""
         import torch
         from . import _evaluate
-        from .functions import CartPole, InvertedPendulum, LyapunovNetwork, UncertainFunction
+        from .functions import CartPole, InvertedPendulum, LyapunovNetwork, PolynomialSystem, UncertainFunction
         if isinstance(self.lyapunov_function, LyapunovNetwork):
             raise TypeError('the gradient of the Lyapunov penalty is implemented for a quadratic or table '
                             'Lyapunov function, not for a LyapunovNetwork')
+        if isinstance(self.dynamics, PolynomialSystem):
+            raise TypeError('the gradient of the Lyapunov penalty needs uncertain GP dynamics (mean, error): a '
+                            'PolynomialSystem (%s) is deterministic and has no action tangent in the engine yet'
+                            % type(self.dynamics).__name__)
         if isinstance(self.dynamics, (InvertedPendulum, CartPole)) or not isinstance(self.dynamics, UncertainFunction):
             raise TypeError('the gradient of the Lyapunov penalty needs uncertain GP dynamics (mean, error), '
                             'not %s' % type(self.dynamics).__name__)

@@ -14,7 +14,8 @@ import numpy as np
 from . import _hip
 from . import distributed as dist_utils
 from ._model import ModelBuilder
-from .functions import CartPole, ConstantFunction, InvertedPendulum, NeuralNetwork, Triangulation
+from .functions import (CartPole, ConstantFunction, InvertedPendulum, NeuralNetwork, PolynomialSystem,
+                        Triangulation)
 
 __all__ = ['PolicyIteration', 'OptimizationError']
 
@@ -194,10 +195,18 @@ class PolicyIteration(object):
             raise NotImplementedError('the gradient of the Lyapunov penalty is implemented for a Lyapunov '
                                       'instance of this package, not for %s' % type(lyapunov).__name__)
 
+    def _refuse_polynomial(self):
+        """Polynomial dynamics carry no action tangent in the engine: said before anything is uploaded."""
+        if isinstance(self.dynamics, PolynomialSystem):
+            raise TypeError('the action gradient is implemented for LinearSystem and GP dynamics (GaussianProcess, '
+                            'FunctionStack): a PolynomialSystem (%s) has no action tangent in the engine yet'
+                            % type(self.dynamics).__name__)
+
     def _action_gradient_device(self, states, policy, actions):
         """One ``sl_action_gradient`` call -> device tensors (states [n, d], dQ/du [n, m], Q [n])."""
         import torch
         from . import _evaluate
+        self._refuse_polynomial()
         if isinstance(self.dynamics, (InvertedPendulum, CartPole)):
             raise TypeError('the action gradient is implemented for LinearSystem and GP dynamics '
                             '(GaussianProcess, FunctionStack), not for the Euler dynamics %s'
@@ -270,6 +279,7 @@ class PolicyIteration(object):
         parameters through a ``lipschitz_dynamics`` callable that reads ``policy.lipschitz()`` (here
         ``L_f`` is a number or ``c + ||M x||_1``)."""
         import torch
+        self._refuse_polynomial()
         keep = isinstance(states, torch.Tensor)
         _, grad, _ = self._penalised_gradient_device(states, policy, actions, lyapunov, lagrange_multiplier)
         return grad if keep else grad.cpu().numpy()
@@ -288,6 +298,7 @@ class PolicyIteration(object):
         With ``lyapunov=`` the objective is ``reduce_i future_values(x_i, lyapunov=lyapunov,
         lagrange_multiplier=...)`` - the safe policy update of ``examples/inverted_pendulum.ipynb``
         cell 17 - see ``action_gradient`` for what is differentiated and what is not."""
+        self._refuse_polynomial()
         if lyapunov is not None:
             self._own_lyapunov(lyapunov)
         if reduction not in ('mean', 'sum'):

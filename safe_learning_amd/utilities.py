@@ -47,14 +47,14 @@ def _check_single_process():
 def _check_pair(dynamics, policy):
     """The (dynamics, policy) specs the fused kernel takes."""
     from .functions import (CartPole, ConstantFunction, InvertedPendulum, LinearSystem, NeuralNetwork,
-                            Saturation, Triangulation, UncertainFunction)
+                            PolynomialSystem, Saturation, Triangulation, UncertainFunction)
     if isinstance(dynamics, UncertainFunction):
         raise ValueError('the fused rollout needs deterministic dynamics; %s returns (mean, error): pass '
                          'a callable instead of the pair, e.g. `lambda x: dynamics(x, policy(x))[0]`'
                          % type(dynamics).__name__)
-    if not isinstance(dynamics, (LinearSystem, InvertedPendulum, CartPole)):
-        raise TypeError('unsupported dynamics spec %r: use LinearSystem, InvertedPendulum, CartPole, or '
-                        'pass a callable on states' % (dynamics,))
+    if not isinstance(dynamics, (LinearSystem, InvertedPendulum, CartPole, PolynomialSystem)):
+        raise TypeError('unsupported dynamics spec %r: use LinearSystem, InvertedPendulum, CartPole, '
+                        'PolynomialSystem, VanDerPol, or pass a callable on states' % (dynamics,))
     inner = policy.fun if isinstance(policy, Saturation) else policy
     if not isinstance(inner, (LinearSystem, ConstantFunction, Triangulation, NeuralNetwork)):
         raise TypeError('unsupported policy spec %r: use LinearSystem, ConstantFunction, a Saturation of '

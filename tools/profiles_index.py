@@ -145,6 +145,9 @@ def main():
              "csrc/sl_critic.hip, `sl_dense_param_grad`): registers / scratch / LDS, the measured ratios of the GPU tests against "
              "their tolerances, a critic and an actor step at the cart-pole notebook's batch and at 2^20 samples, split per call, "
              "beside torch autograd (`tools/actor_critic_probe.py`; DESIGN.md 4.5d).",
+             "* `polynomial_dynamics.md`, `polynomial_probe.jsonl`: polynomial dynamics (`SL_DYN_POLYNOMIAL`, csrc/sl_polynomial.h): registers "
+             "and scratch of the new instantiations, Van der Pol against the pendulum in the same kernels, and the eight entries of "
+             "`pmc_valu.json` before and after the edit of the shared headers (`tools/polynomial_probe.py`; DESIGN.md 4.2c).",
              "* `gp_posterior_truth.md`: the GP posterior of `k_gp_sweep4`, `k_gp_sweep` and `k_gp_small` against the posterior in "
              "extended precision (`tests/np_gp_truth.py`): per case cond(K), the oracle's own error, a NumPy restatement of the "
              "engine's formula and the engine's measured error (`tests/test_gpu_gp_truth.py`; DESIGN.md 6 (iv)).",
