@@ -274,6 +274,15 @@ SL_API int  sl_gp4_segment_configure(sl_ctx* ctx, int tiles);
  * paired composites and the slots of them that held one half only.  Belongs to the context, takes
  * effect at its next sweep. */
 SL_API int  sl_gp4_halves_configure(sl_ctx* ctx, int enable);
+/* A segmented block-mode sweep first decides, in a streaming pass (k_gp_mean_lattice, k_gp_predecide),
+ * the 16-cell blocks that a bound of the posterior mean shows to fail whatever their variance: the
+ * first-order Taylor expansion of the mean about a reference cell with the remainder
+ * |g_j(z) - g_j(z_c) - J_j (z - z_c)| <= (sqrt(3) / 2) ||g_j||_H s |z - z_c|^2, the reference cells on a lattice
+ * of every `spacing`-th grid index per axis (and the last index of the axis).  Closed-form policies only.  k_gp_mean_blocks skips those
+ * blocks.  The results are the same bits either way; sl_last_kernel reports the blocks decided.
+ * enable = 0 switches the pass off (A/B runs and tests); spacing = 0 keeps the spacing (default 8).
+ * Belongs to the context, takes effect at its next sweep. */
+SL_API int  sl_gp4_predecide_configure(sl_ctx* ctx, int enable, int spacing);
 
 /* Auxiliary grid #slot with a per-vertex table (Triangulation: functions.py:1002-1032,
  * 1064-1101): slot 0 = value function, slot 1 = policy.  h_simplices [nsimplex][d+1] are the

@@ -33,6 +33,8 @@ UNITS = [("sl_kernels", "sl_kernels.hip", []), ("sl_gp", "sl_gp.hip", []),
 UNITS += [("sl_gp4_d%d" % dim, "sl_gp4.hip", GP4_FLAGS + ["-DSL_GP4_DIM=%d" % dim]) for dim in (1, 2, 3, 4)]
 # k_gp_mean_blocks (the source pass of k_gp_sweep4's block mode), once per dimension as well
 UNITS += [("sl_gp4_mean_d%d" % dim, "sl_gp4_mean.hip", ["-DSL_GP4_DIM=%d" % dim]) for dim in (1, 2, 3, 4)]
+# k_gp_mean_lattice / k_gp_predecide (the deciding pass in front of k_gp_mean_blocks), per dimension too
+UNITS += [("sl_gp4_predecide_d%d" % dim, "sl_gp4_predecide.hip", ["-DSL_GP4_DIM=%d" % dim]) for dim in (1, 2, 3, 4)]
 LIB = os.path.join(HERE, "libslhip.so")
 
 

@@ -157,6 +157,7 @@ SIGNATURES = {
     "sl_gp4_workgroups_configure": (_int, (_vp, _int)),
     "sl_gp4_segment_configure": (_int, (_vp, _int)),
     "sl_gp4_halves_configure": (_int, (_vp, _int)),
+    "sl_gp4_predecide_configure": (_int, (_vp, _int, _int)),
     "sl_tri_set": (_int, (_vp, _int, C.POINTER(GridDesc), _int, _int32_p, c_double_p, c_double_p, _int, _int,
                           _vp)),
     "sl_tri_set_table": (_int, (_vp, _int, _vp)),
@@ -349,6 +350,11 @@ class Context(object):
         # their 8-cell halves.  Same results bit for bit; last_kernel() names the granule.
         if os.environ.get("SL_GP4_HALVES") == "0":
             self.lib.sl_gp4_halves_configure(self.handle, 0)
+        # SL_GP4_PREDECIDE=0 (A/B runs, tests): no deciding pass in front of k_gp_mean_blocks;
+        # SL_GP4_PREDECIDE_SPACING=S: the lattice spacing of its reference cells (default 8).  Same
+        # results bit for bit; last_kernel() reports the blocks the pass decided.
+        self.lib.sl_gp4_predecide_configure(self.handle, 0 if os.environ.get("SL_GP4_PREDECIDE") == "0" else 1,
+                                            int(os.environ.get("SL_GP4_PREDECIDE_SPACING") or 0))
 
     def close(self):
         if getattr(self, "handle", None):

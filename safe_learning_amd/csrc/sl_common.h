@@ -21,6 +21,10 @@ struct SlGpHeadHost {
     bool set = false;
     int n = 0, n_pad = 0, p = 0, dout = 0, col0 = 0, cfg = 0;
     double linv00 = 0.0;                          // Linv[0][0] = 1 / sqrt(k(x_0, x_0) + sigma_n^2)
+    // Lipschitz bound of the mean (sl_gp_mean_bound.h): RKHS norm and rounding allowance per column;
+    // off after sl_gp_append_point until the next full upload
+    bool mb_ok = false;
+    double mb_norm[SL_MAX_STATE_DIM] = {}, mb_eps[SL_MAX_STATE_DIM] = {};
     double lengthscales[SL_MAX_INPUT_DIM] = {};   // as uploaded: appended points are scaled by the
                                                   // same division as the packed ones (bit-identical)
     double* d_xs = nullptr;
@@ -107,7 +111,15 @@ struct sl_ctx {
                                        // (sl_gp4_segment_configure; off: large launches only, segments from the scratch budget)
     bool gp4_halves = true;            // block mode decides and queues 8-cell halves (sl_gp4_halves_configure)
     size_t gp4_seed_bytes = 0;
-    void* d_records = nullptr;         // GP posterior records of the two-pass network check
+    // k_gp_predecide (sl_gp4_predecide.hip): blocks of a segmented block-mode sweep decided before
+    // k_gp_mean_blocks from a Lipschitz bound of the mean (sl_gp4_predecide_configure)
+    bool gp4_predecide = true;
+    int gp4_pre_spacing = 8;           // lattice spacing S of its reference cells
+    void* d_gp4_pre = nullptr;         // the lattice table, then one byte per 64-cell tile of the shard
+    size_t gp4_pre_bytes = 0;
+    const unsigned char* gp4_pre_tiles = nullptr;   // the tile bytes of the sweep under way, or null: pass off
+    const unsigned long long* gp4_pre_count = nullptr;   // its device counter of decided blocks, read with the note
+    void* d_records = nullptr;        // GP posterior records of the two-pass network check
     size_t records_bytes = 0;
     sl_key* d_partials = nullptr;      // SL_MAX_GRID entries x 4 keys
     int64_t* d_partial_counts = nullptr;
@@ -119,7 +131,7 @@ struct sl_ctx {
     void* comm = nullptr;              // RCCL communicator (sl_comm.hip), optional
     void* d_comm_records = nullptr;    // [world] gathered sl_sweep_result records
     int comm_rank = 0, comm_world = 1;
-    char last_kernel[256] = "";        // dominant kernel(s) of the last sweep call (sl_last_kernel)
+    char last_kernel[320] = "";        // dominant kernel(s) of the last sweep call (sl_last_kernel)
     // block mode of k_gp_sweep4: the launch's two device counters (paired composites, lone-half
     // slots), added to the note when it is read (sl_last_kernel); nullptr: nothing to add
     const unsigned long long* gp4_pair_counts = nullptr;

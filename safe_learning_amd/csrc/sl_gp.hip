@@ -22,6 +22,7 @@
 //    failing cells run in the same kernel; HBM traffic is 8 B (V) + 1 bit per cell.
 #include "sl_common.h"
 #include "sl_gp_floor.h"
+#include "sl_gp_mean_bound.h"
 
 typedef double sl_d4 __attribute__((ext_vector_type(4)));
 typedef double sl_d2 __attribute__((ext_vector_type(2)));
@@ -432,6 +433,15 @@ static int gp_set_head(sl_ctx* ctx, int head, int n, int p, int dout, int col0, 
         alphap[(size_t)n_pad * dout] = 2.0 * 64.0 * (double)n * 0x1p-53 * variance;   // 2 delta (gp4_early_ok)
         for (int s = 0; s < floor_stages; ++s) alphap[(size_t)n_pad * dout + 1 + s] = floor_c[s];
     }
+    // Constants of k_gp_predecide's bound of the mean (sl_gp_mean_bound.h): the same heads, in a context
+    // whose deciding pass is on at this upload; n^2 / 2 kernel values in long double - measured with
+    // this build's host compiler and flags: 6.5 ms at 300 points, 68 ms at 1024, 278 ms at 2048, beside
+    // the 1.2 s of the floor above at 1024.  "off" on any doubt.
+    double mb_norm[SL_MAX_STATE_DIM] = {}, mb_eps[SL_MAX_STATE_DIM] = {};
+    bool mb_ok = false;
+    if (!h_kernel && ctx->gp4_early && ctx->gp4_predecide && ctx->env.gp_cfg < 0 && n_pad % SL_GP_FLOOR_RP == 0 &&
+        floor_stages <= SL_GP_FLOOR_STAGES && n <= SL_GP_FLOOR_MAX_N && dout <= SL_MAX_STATE_DIM)
+        mb_ok = gpbound::mean_bound(xs.data(), n, n_pad, p, alphap.data(), dout, variance, mb_norm, mb_eps);
     // MFMA A fragments: [row block I][slab pair S2][lane][2]; A[i = lane & 15][k = lane >> 4]
     for (int I = 0; I < n_pad / 16; ++I) {
         for (int S2 = 0; S2 < nslab2; ++S2) {
@@ -470,6 +480,8 @@ static int gp_set_head(sl_ctx* ctx, int head, int n, int p, int dout, int col0, 
     SL_HIP_CHECK(ctx, hipMemcpy(hh.d_alpha, alphap.data(), alphap.size() * sizeof(double), hipMemcpyHostToDevice));
     hh.set = true; hh.n = n; hh.n_pad = n_pad; hh.p = p; hh.dout = dout; hh.col0 = col0; hh.cfg = cfg;
     hh.linv00 = h_Linv[0];
+    hh.mb_ok = mb_ok;
+    for (int j = 0; j < SL_MAX_STATE_DIM; ++j) { hh.mb_norm[j] = mb_norm[j]; hh.mb_eps[j] = mb_eps[j]; }
 
     SlGpHeadDev& dv = ctx->h_gp.head[head];
     memset(&dv, 0, sizeof(dv));
@@ -569,6 +581,7 @@ extern "C" int sl_gp_append_point(sl_ctx* ctx, int head, const double* h_x, cons
     dv.n = n + 1;
     // a new row grows the Schur complements: the old constants are no bounds of the new model
     SL_HIP_CHECK(ctx, hipMemset(hh.d_alpha + (size_t)hh.n_pad * hh.dout, 0, SL_GP_FLOOR_WORDS * sizeof(double)));
+    hh.mb_ok = false;                              // ... and the RKHS norm of the mean grows with alpha'
     SL_HIP_CHECK(ctx, hipMemcpy(ctx->d_gp, &ctx->h_gp, sizeof(SlGpDev), hipMemcpyHostToDevice));
     return SL_OK;
 }

@@ -16,7 +16,11 @@
 //  * a block the bounds decide writes its 16 mask bits and folds its failing key, as in the panel
 //    kernel; a block they leave open appends a stage-0 record - first cell and 16 x d means - to
 //    the segment's list, position from a device counter (order free).  The panel kernel then
-//    draws its stage-0 composite tiles from that list (sl_gp4_queue.h).
+//    draws its stage-0 composite tiles from that list (sl_gp4_queue.h);
+//  * a block that k_gp_predecide (sl_gp4_predecide.hip: a bound of the mean, in front of the first
+//    segment) has already decided as failing is skipped before any input is formed: one bit of the
+//    tile's byte, tested per block with a scalar load (keeping the byte across the four blocks cost
+//    the d = 4 kernel five scratch operations).
 //
 // The arithmetic of a block is that of sl_gp4.hip because it is the same source, sl_gp4_gen.h: seed
 // of a run, 16-cell recurrence, direct path, alpha' and k_x fragment loads, the MFMA group of the
@@ -40,6 +44,7 @@
 #include "sl_common.h"
 #include "sl_gp4_gen.h"
 #include "sl_gp4_mean.h"
+#include "sl_gp4_predecide.h"
 #include "sl_gp4_queue.h"
 
 #ifndef SL_NO_GP4
@@ -75,7 +80,7 @@ __global__ __launch_bounds__(256, 4) void k_gp_mean_blocks(
     uint64_t* __restrict__ neg_bits, sl_key* __restrict__ partials, int fold,
     const double* __restrict__ points, int skip_arg, unsigned long long* __restrict__ ticket,
     unsigned* __restrict__ list_count, long long* __restrict__ list_cell, double* __restrict__ list_mean,
-    unsigned list_cap) {
+    unsigned list_cap, const unsigned char* __restrict__ pre_tiles) {
     // skip (SL_GP4_SKIP; development builds only): 1 no k_x generation, 2 no mean product
 #ifdef SL_DIAG
     const int skip = skip_arg;
@@ -127,7 +132,9 @@ __global__ __launch_bounds__(256, 4) void k_gp_mean_blocks(
             if (lane == 0) neg_bits[(tile_base - lo) >> 6] = 0ull;
             continue;
         }
+        // blocks k_gp_predecide has decided (mask bits and key written there): one byte per tile
         for (int jb = 0; jb < 4; ++jb) {
+            if (pre_tiles && ((reinterpret_cast<const unsigned*>(pre_tiles)[tile >> 2] >> (8 * (int)(tile & 3) + jb)) & 1u)) continue;
             const int64_t blk0 = tile_base + 16 * jb;
             // scaled GP input [x, policy(x)] / lengthscales of the 16 cells (lane = cell)
             if (lk == 0) {
@@ -331,10 +338,24 @@ template <int DT, int MT>
 static int launch_mean(sl_ctx* ctx, const SlDevModel& model, const SlSweepArgs& a, const Gp4MeanLaunch& m) {
     SlAux aux{ctx->d_tri, ctx->d_net};
     const int skip = sl_diag_flags("SL_GP4_SKIP");            // (development builds only: 0 otherwise)
+    // The first segment of a sweep: the lattice pass and k_gp_predecide over the whole shard, in
+    // front of everything else.  Its keys go to this kernel's slots (one per wavefront of as many
+    // workgroups), which every segment then folds; its count to word [6] of the scratch's head.
+    if (!m.fold) {
+        ctx->gp4_pre_tiles = nullptr;
+        ctx->gp4_pre_count = nullptr;
+        if (sl_gp4_predecide_ok(ctx, model, a)) {
+            const Gp4PreLaunch pl{m.workgroups, m.partials, m.ticket + 5};
+            const int rc = sl_gp4_predecide_launch_dim<DT>(ctx, model, a, pl, &ctx->gp4_pre_tiles);
+            if (rc) return rc;
+            ctx->gp4_pre_count = m.ticket + 5;
+        }
+    }
+    const int fold = m.fold || ctx->gp4_pre_tiles != nullptr;
     hipLaunchKernelGGL((k_gp_mean_blocks<DT, MT>), dim3((unsigned)m.workgroups), dim3(gp4m::W * 64), 0, ctx->stream,
                        model, ctx->h_gp, aux, a.lo, a.hi, (int64_t)m.tile0, (int64_t)m.tile1, a.init_bits, a.values,
-                       a.neg_bits, m.partials, m.fold, a.points, skip, m.ticket, m.list_count, m.list_cell,
-                       m.list_mean, m.list_cap);
+                       a.neg_bits, m.partials, fold, a.points, skip, m.ticket, m.list_count, m.list_cell,
+                       m.list_mean, m.list_cap, ctx->gp4_pre_tiles);
     SL_HIP_CHECK(ctx, hipGetLastError());
     return SL_OK;
 }

@@ -34,14 +34,20 @@ extern "C" const char* sl_last_kernel(const sl_ctx* ctx) {
     if (ctx->gp4_pair_counts) {
         // the counts of the block-mode launch the note names: read once, when somebody asks
         sl_ctx* c = const_cast<sl_ctx*>(ctx);
-        unsigned long long n[2] = {0, 0};
+        unsigned long long n[3] = {0, 0, 0};      // ([2]: blocks k_gp_predecide decided, the word behind the two)
         const unsigned long long* from = c->gp4_pair_counts;
+        const bool pre = c->gp4_pre_count == from + 2;
         c->gp4_pair_counts = nullptr;
+        c->gp4_pre_count = nullptr;
         if (hipStreamSynchronize(c->stream) == hipSuccess &&
             hipMemcpy(n, from, sizeof(n), hipMemcpyDeviceToHost) == hipSuccess) {
             const size_t used = strlen(c->last_kernel);
             snprintf(c->last_kernel + used, sizeof(c->last_kernel) - used,
                      ", %llu paired composite(s), %llu lone half slot(s)", n[0], n[1]);
+            if (pre) {
+                const size_t now = strlen(c->last_kernel);
+                snprintf(c->last_kernel + now, sizeof(c->last_kernel) - now, ", %llu block(s) decided before the mean", n[2]);
+            }
         }
     }
     return ctx->last_kernel;
@@ -149,6 +155,7 @@ extern "C" int sl_ctx_destroy(sl_ctx* ctx) {
     (void)hipFree(ctx->d_net);
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
     if (ctx->d_gp4_seeds) (void)hipFree(ctx->d_gp4_seeds);
+    if (ctx->d_gp4_pre) (void)hipFree(ctx->d_gp4_pre);
     if (ctx->d_policy_cache) (void)hipFree(ctx->d_policy_cache);
     if (ctx->d_pnet_params) (void)hipFree(ctx->d_pnet_params);
     if (ctx->d_policy_actions) (void)hipFree(ctx->d_policy_actions);
@@ -929,6 +936,7 @@ int sl_sweep_any(sl_ctx* ctx, const SlSweepArgs& a, sl_sweep_result* d_result, b
         return sl_fail(ctx, SL_ERR_INVALID, "sl_lyap_sweep: bad range (lo must be a multiple of 64)");
     // with explicit points a TABLE policy is indexed by the point number (one action per point)
     if (!a.neg_bits || !d_result) return sl_fail(ctx, SL_ERR_INVALID, "sl_lyap_sweep: NULL output");
+    ctx->gp4_pre_count = nullptr;                  // (set again by a sweep that runs k_gp_predecide)
     SlTimed timing(timed ? ctx : nullptr, 0);
     SL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     SlPolicyTableScope network_policy(ctx, a.lo, a.hi, a.points);   // (a network policy becomes a per-cell table)

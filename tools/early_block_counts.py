@@ -7,7 +7,7 @@ granules of 64 / 32 / 16 / 1 cells.  The kernel's granule is the 16-cell block (
 1-cell row the floor.
 
     python tools/early_block_counts.py [--variant informed|tight|survey] [--tiles 3000] [--seed 0]
-                                       [--variance-floor] [--headline-tau] [--halves]
+                                       [--variance-floor] [--headline-tau] [--halves] [--mean-lattice S]
 
 --variance-floor: the lower bound of a cell before panel s is the decrease at err = beta sqrt(c_s
 (variance - partial |a|^2)) instead of err = 0, with c_s = sigma_n^2 sigma_min(Linv[256 s:, 256 s:])^2
@@ -25,6 +25,14 @@ as the rarer kind allows), the lone halves (the surplus of the other kind, a slo
 open halves whose sibling is open too, the slots over the blocks open at the 16-cell granule - and
 the panel work at that packing.  (The first decision of a large launch is per block: the line
 "halves from panel 1 on" keeps the 16-cell count for panel 0.)
+
+--mean-lattice S: the blocks k_gp_predecide decides before the mean is computed, by the kernel's
+rule (safe_learning_amd/csrc/sl_gp4_predecide.h, the constants of sl_gp_mean_bound.h) in NumPy: the
+mean of a cell lies within (sqrt(3) / 2) norm_j s |z - z_c|^2 (and a rounding allowance) of its
+first-order Taylor expansion about the nearest point of a lattice of every S-th grid index per axis
+(and the last index), and a block is decided when
+the lower bound of V(mean) that follows keeps every cell of it from passing.  Printed beside the
+blocks the exact mean decides (stage 0 of the table above).
 
 Panel p of a tile multiplies (p + 1) 4 chunks against its 16 row blocks, the diagonal band a
 triangle: 40 / 104 / 168 / 232 (row block, chunk) products for p = 0 .. 3, 64 more per panel
@@ -131,6 +139,108 @@ def half_packing(stage, npan):
     return rows, work, work_from_1
 
 
+# ---- k_gp_predecide's rule (sl_gp4_predecide.h), vectorised ---------------------------------------
+NORM_MARGIN, ROUND_TERMS, EPS_MULT, SLACK = 1e-6, 8.0, 4096.0, 2.0 ** -40      # sl_gp_mean_bound.h, sl_gp4_predecide.h
+HALF_SQRT3 = 0.8660254037844388
+
+
+def mean_bound_constants(xs, alphap, variance):
+    """(norm[dout], eps[dout]) of sl_gp_mean_bound.h from the scaled inputs xs [n][p] and alpha'
+    [n][dout], in np.longdouble."""
+    ld = np.longdouble
+    n = len(xs)
+    x = xs.astype(ld)
+    a = alphap.astype(ld)
+    quad = np.zeros(a.shape[1], dtype=ld)
+    mag = np.zeros(a.shape[1], dtype=ld)
+    for i in range(n):                                   # (row by row: n x n long doubles are 16 MB at 1024)
+        k = ld(variance) * np.exp(ld(-0.5) * ((x - x[i]) ** 2).sum(1))
+        quad += a[i] * (k[:, None] * a).sum(0)
+        mag += np.abs(a[i]) * (k[:, None] * np.abs(a)).sum(0)
+    up = np.maximum(quad, 0) + ld(ROUND_TERMS) * n * np.finfo(ld).eps * mag
+    norm = (np.sqrt(up) * (1 + ld(NORM_MARGIN))).astype(np.float64)
+    eps = (ld(EPS_MULT) * n * ld(2.0) ** -53 * ld(variance) * np.abs(a).sum(0) * (1 + ld(2.0) ** -40)).astype(np.float64)
+    return norm, eps
+
+
+def lattice_nearest(i, num, spacing):
+    """Grid index of the lattice point nearest to grid index i (arrays), the lower one on a tie."""
+    ia = (i // spacing) * spacing
+    ib = np.minimum(ia + spacing, num - 1)
+    return np.where((i - ia) > (ib - i), ib, ia)
+
+
+def mean_lattice_sure(case, idx, spacing):
+    """Per cell of ``idx``: does k_gp_predecide's rule at lattice spacing ``spacing`` show it to fail?"""
+    import cases
+    ol = cases.oracle_lyapunov(case, compute_values=False)
+    grid, gp = ol.discretization, ol.dynamics.gaussian_process
+    dyn = case["dynamics"]
+    ls = np.asarray(dyn["lengthscales"], dtype=float)
+    variance = float(dyn["variance"])
+    xs = gp.X / ls
+    alphap = scipy.linalg.solve_triangular(gp.cholesky, gp.alpha, lower=True, trans="T")
+    norm, eps = mean_bound_constants(xs, alphap, variance)
+    sdev = np.sqrt(variance) * (1 + 2.0 ** -50)
+    idx = np.asarray(idx)
+    num = np.asarray(grid.num_points)
+    ijk = np.stack(np.unravel_index(idx, num), 1)
+    near = np.stack([lattice_nearest(ijk[:, k], num[k], spacing) for k in range(len(num))], 1)
+    ref = np.ravel_multi_index(tuple(near.T), num)
+    uniq, inverse = np.unique(ref, return_inverse=True)
+
+    def scaled(cells):
+        x = grid.index_to_state(cells)
+        return x, np.hstack((x, ol.policy(x))) / ls
+
+    _, zc_u = scaled(uniq)
+    g_u = np.empty((len(uniq), alphap.shape[1]))
+    J_u = np.empty((len(uniq), alphap.shape[1], xs.shape[1]))
+    for b in range(0, len(uniq), 2048):
+        diff = xs[None, :, :] - zc_u[b:b + 2048][:, None, :]
+        k = variance * np.exp(-0.5 * (diff ** 2).sum(2))
+        g_u[b:b + 2048] = k.dot(alphap)
+        J_u[b:b + 2048] = np.einsum("ci,ij,ciq->cjq", k, alphap, diff)      # d/dz k(z, z_i) = k (z_i - z)
+    x, z = scaled(idx)
+    z_c, g_c, J = zc_u[inverse], g_u[inverse], J_u[inverse]
+    prior = gp._mean(np.hstack((x, ol.policy(x))))
+    v_x = ol.lyapunov_function(x)[:, 0]
+    thr = np.broadcast_to(ol.threshold(x, ol.tau), (len(idx), 1))[:, 0]
+    P = np.asarray(case["P"], dtype=float)
+    D = z - z_c
+    dist2 = (D ** 2).sum(1) * (1 + 2.0 ** -40)
+    zmax = np.maximum(1.0, np.maximum(np.abs(z).max(1), np.abs(z_c).max(1)))
+    terms = J * D[:, None, :]
+    mu = g_c + terms.sum(2) + prior
+    absm = np.abs(g_c) + np.abs(terms).sum(2) + np.abs(prior)
+    B = (((HALF_SQRT3 * norm) * sdev) * dist2[:, None] + eps * (2 * zmax + np.abs(D).sum(1))[:, None]) * (1 + 2.0 ** -40) \
+        + 2.0 ** -48 * absm
+    A = np.abs(mu) + B
+    vc = (mu.dot(P) * mu).sum(1)
+    lin = (np.abs(mu.dot(P + P.T)) * B).sum(1)
+    quad = (B.dot(np.abs(P)) * B).sum(1)
+    mag = (A.dot(np.abs(P)) * A).sum(1) + np.abs(v_x) + np.abs(thr)
+    lower = ((vc - lin) - quad) - v_x
+    return np.isfinite(mag) & (lower >= thr + SLACK * mag)
+
+
+def count_mean_lattice(variant=None, tiles=1500, seed=0, spacing=8, headline_tau=False, batch=500):
+    """(blocks the bound decides, blocks the exact mean decides) as fractions of the blocks of random
+    headline tiles."""
+    from safe_learning_amd.benchmarks import headline_case
+    case = headline_case(variant=variant)
+    if headline_tau:
+        case["tau"] = headline_case()["tau"]
+    idx = sample_tiles(case, tiles, seed)
+    sure = mean_lattice_sure(case, idx, spacing)
+    stages = [cell_stages(case, idx[b:b + batch * 64])[0] for b in range(0, len(idx), batch * 64)]
+    stage = np.concatenate(stages)
+    final_fail_at_0 = granule_stages(stage, 16) == 0
+    by_bound = sure.reshape(-1, 16).all(1)
+    assert not (by_bound & ~final_fail_at_0).any()       # (the bound decides nothing the exact mean leaves open)
+    return float(by_bound.mean()), float(final_fail_at_0.mean())
+
+
 def sample_tiles(case, tiles, seed):
     """Cell indices of ``tiles`` random 64-cell tiles of the case's grid (tile-aligned)."""
     n = int(np.prod(case["num_points"]))
@@ -168,7 +278,14 @@ if __name__ == "__main__":
     ap.add_argument("--variance-floor", action="store_true")
     ap.add_argument("--headline-tau", action="store_true")
     ap.add_argument("--halves", action="store_true")
+    ap.add_argument("--mean-lattice", type=int, default=0, metavar="S")
     args = ap.parse_args()
+    if args.mean_lattice:
+        bound, exact = count_mean_lattice(args.variant, args.tiles, args.seed, args.mean_lattice, args.headline_tau)
+        print("# headline_case(variant=%r)%s, %d random tiles, seed %d, lattice spacing %d" % (
+            args.variant, " at the headline tau" if args.headline_tau else "", args.tiles, args.seed, args.mean_lattice))
+        print("blocks with all 16 cells decided by the bound: %.4f | blocks the exact mean decides: %.4f" % (bound, exact))
+        sys.exit(0)
     granules = (64, 32, 16, 8, 4, 1) if args.halves else GRANULES
     result, npan = count(args.variant, args.tiles, args.seed, floor=args.variance_floor, headline_tau=args.headline_tau,
                          granules=granules, halves=args.halves)
