@@ -247,14 +247,14 @@ def build_specs(case):
                     kern = kernel_from_products(dyn['kernels'][k], {'rbf': F.RBF, 'matern32': F.Matern32,
                                                                     'linear': F.Linear})
                 else:
-                    kern = F.RBF(d + 1, dyn['variance'], dyn['lengthscales'][k], ARD=True)
+                    kern = F.RBF(d + case['m'], dyn['variance'], dyn['lengthscales'][k], ARD=True)
                 gp = F.GPRCached(dyn['X'], dyn['Y'][:, [k]], kern,
                                  F.LinearSystem((dyn['prior'][[k], :],)),
                                  likelihood_variance=dyn['noise_variance'])
                 heads.append(F.GaussianProcess(gp, dyn['beta']))
             dynamics = F.FunctionStack(heads)
         else:
-            kern = F.RBF(d + 1, dyn['variance'], dyn['lengthscales'], ARD=True)
+            kern = F.RBF(d + case['m'], dyn['variance'], dyn['lengthscales'], ARD=True)
             gp = F.GPRCached(dyn['X'], dyn['Y'], kern, F.LinearSystem((dyn['prior'],)),
                              likelihood_variance=dyn['noise_variance'])
             dynamics = F.GaussianProcess(gp, dyn['beta'])

@@ -38,14 +38,14 @@ def oracle_specs(case):
                     from safe_learning_amd.benchmarks import kernel_from_products
                     kern = kernel_from_products(dyn['kernels'][k], ORACLE_KERNEL_LEAVES)
                 else:
-                    kern = oracle.RBF(d + 1, dyn['variance'], dyn['lengthscales'][k], ARD=True)
+                    kern = oracle.RBF(d + case['m'], dyn['variance'], dyn['lengthscales'][k], ARD=True)
                 gp = oracle.GPRCached(dyn['X'], dyn['Y'][:, [k]], kern,
                                       oracle.LinearSystem((dyn['prior'][[k], :],)),
                                       likelihood_variance=dyn['noise_variance'])
                 heads.append(oracle.GaussianProcess(gp, dyn['beta']))
             dynamics = oracle.FunctionStack(heads)
         else:
-            kern = oracle.RBF(d + 1, dyn['variance'], dyn['lengthscales'], ARD=True)
+            kern = oracle.RBF(d + case['m'], dyn['variance'], dyn['lengthscales'], ARD=True)
             gp = oracle.GPRCached(dyn['X'], dyn['Y'], kern, oracle.LinearSystem((dyn['prior'],)),
                                   likelihood_variance=dyn['noise_variance'])
             dynamics = oracle.GaussianProcess(gp, dyn['beta'])

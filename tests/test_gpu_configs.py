@@ -17,6 +17,7 @@ import pytest
 from numpy.testing import assert_allclose, assert_array_equal
 
 import cases
+import gp_sweep_matrix
 import oracle
 from conftest import ROOT
 from test_gpu_full_size import (_grid_points, _level_set_properties, _neg_mask, _point_records,
@@ -281,6 +282,7 @@ def test_sixteen_wavefront_workgroups_of_the_small_gp_kernel(flags, monkeypatch)
         lyap._ctx.lyap_sweep(0, n, lyap._d_init, lyap._values_arg(), bits, record, dbg)
         kernel = lyap._ctx.last_kernel()
         assert "k_gp_small" in kernel and ("16 wavefronts" in kernel) == (cap is None), kernel
+        assert kernel.startswith(gp_sweep_matrix.config_note(flags, cap)), kernel      # flavour, placement, heads
         outs.append((dbg, bits, record))
         del lyap
     assert torch.equal(outs[0][1], outs[1][1])
@@ -316,6 +318,7 @@ def test_four_wavefront_workgroups_of_the_small_gp_kernel(flags, monkeypatch):
         lyap._ctx.lyap_sweep(0, n, lyap._d_init, lyap._values_arg(), bits, record, dbg)
         kernel = lyap._ctx.last_kernel()
         assert "k_gp_small" in kernel and ("4 wavefronts" in kernel) == (cap is None), kernel
+        assert kernel.startswith(gp_sweep_matrix.config_note(flags, cap)), kernel      # flavour, placement, heads
         outs.append((dbg, bits, record))
         del lyap
     assert torch.equal(outs[0][1], outs[1][1])

@@ -161,7 +161,12 @@ def main():
              "* `network_parity.md`: the twelve `k_nn_check_mfma<layers, d>` instantiations of `sl_nn.hip` with the test that "
              "reaches each, V, grad V and the sweep records against the network in extended precision "
              "(`tests/np_network_truth.py`, `tests/test_gpu_network_matrix.py`) per case, the device `sl_tanh` in ulp per "
-             "segment, and the outcome of two numerically perturbed scratch builds.", ""]
+             "segment, and the outcome of two numerically perturbed scratch builds.",
+             "* `gp_sweep_matrix.md`: the 105 instantiations of `k_gp_small` (`sl_gp_small.hip`) and `k_gp_sweep` (`sl_gp.hip`) "
+             "with the test that reaches each (`tests/gp_sweep_matrix.py`), the posterior of the newly covered ones against "
+             "the long-double posterior in units of the oracle's own error, 4 / 12 / 16 against eight wavefronts bit for bit "
+             "(`tests/test_gpu_gp_sweep_matrix.py`), wall times, and the outcome of two numerically perturbed scratch builds.",
+             ""]
     for key in sorted(by_round):
         text.append("* %s: %s" % (key, ", ".join("`%s`" % n for n in by_round[key])))
     with open(os.path.join(P, "README.md"), "w") as f:
