@@ -65,7 +65,8 @@ enum sl_dynamics_kind {
 enum sl_value_kind {
     SL_V_QUADRATIC  = 1,    /* x P x^T              (functions.py:1534-1539)                */
     SL_V_TRI        = 2,    /* Triangulation on the auxiliary grid #0 (functions.py:1473-1499) */
-    SL_V_NETWORK    = 3     /* LyapunovNetwork      (examples/utilities.py:85-104)          */
+    SL_V_NETWORK    = 3,    /* LyapunovNetwork      (examples/utilities.py:85-104)          */
+    SL_V_POLYNOMIAL = 4     /* term table of sl_value_polynomial_set (lyapunov_function_learning.ipynb cell 17) */
 };
 enum sl_lipschitz_kind {
     SL_LIP_CONST       = 0, /* scalar                                  (lyapunov.py:241-263) */
@@ -190,6 +191,24 @@ SL_API int  sl_policy_touch(sl_ctx* ctx);
 #define SL_POLY_MAX_DEGREE 8      /* total degree of one term: at most 8 multiplications per term */
 SL_API int  sl_dynamics_polynomial_set(sl_ctx* ctx, int d, int m, int nterms, const int32_t* h_rows,
                     const double* h_coef, const uint8_t* h_exponents, int substeps, double h);
+
+/* Polynomial Lyapunov / value function (SL_V_POLYNOMIAL): a candidate given as data, nterms terms
+ *     V(x) = sum_t coef_t * prod_q z_q^e_tq,   z_q = x_q * h_tx[q] (normalize != 0) or x_q,
+ * h_exponents is [nterms][SL_MAX_STATE_DIM] (entries at q >= d must be 0); the sum of a term's exponents is at
+ * most SL_POLY_MAX_DEGREE.  The call validates, builds the device table - the value row and one row per
+ * partial derivative (every term with e_k >= 1 gives coef * e_k and the exponents with e_k - 1) - waits for the
+ * stream and uploads; value row and gradient rows together hold at most SL_POLYV_MAX_ENTRIES entries (a full
+ * quartic in four states: 69 + 4 * 35; a full sextic in three: 83 + 3 * 56).  csrc/sl_poly_value.h states the
+ * operation order: multiplications and additions only, powers by repeated multiplication, the gradient with
+ * respect to x (times h_tx[k]).  sl_value_desc.negate applies; its matrix is not read.  sl_model_set accepts
+ * kind SL_V_POLYNOMIAL only after this call and only when the table's d is the grid's.  SL_LIP_ABS_GRAD and
+ * SL_LIP_NORM_GRAD take the table's gradient.  A new table is a new value function; a table of another d than
+ * that of a set model of the kind unsets the model (the entry points then ask for sl_model_set again).  The sweeps, sl_values and
+ * sl_eval_points (also SL_EVAL_GRADIENT) take the kind; second derivatives are not implemented:
+ * sl_decrease_gradient returns SL_ERR_UNSUPPORTED for it, and the Bellman entry points take tables only. */
+#define SL_POLYV_MAX_ENTRIES 256
+SL_API int  sl_value_polynomial_set(sl_ctx* ctx, int d, int nterms, const double* h_coef,
+                    const uint8_t* h_exponents, int normalize, const double* h_tx);
 
 /* GP head `head` of the dynamics (FunctionStack: one head per output column,
  * functions.py:278-291; a shared-kernel multi-output GPRCached is one head with dout = D).
@@ -588,7 +607,8 @@ enum sl_eval_what {
     SL_EVAL_POLICY = 2,     /* policy(x)               out [n][m]                  */
     SL_EVAL_DYNAMICS = 3,   /* per-point record        out [n][2+2d] =             */
     SL_EVAL_DECREASE = 4,   /*   [v_decrease_bound, threshold, mean f[d], error[d]] (both selectors) */
-    SL_EVAL_LV = 5          /* L_v(x)                  out [n][lv_cols]            */
+    SL_EVAL_LV = 5,         /* L_v(x)                  out [n][lv_cols]            */
+    SL_EVAL_GRADIENT = 6    /* dV/dx(x), signed        out [n][d]  (SL_V_POLYNOMIAL only)  */
 };
 SL_API int  sl_eval_points(sl_ctx* ctx, int what, int64_t n, const double* d_points /* [n][d] */,
                     double* d_out);

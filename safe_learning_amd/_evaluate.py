@@ -108,6 +108,21 @@ def value(spec, points, lipschitz=None):
     return (out, lv) if keep else (out.cpu().numpy(), lv.cpu().numpy())
 
 
+def value_gradient(spec, points):
+    """``dV/dx(points)`` -> ``[n, d]``, signed (a ``PolynomialFunction``: ``SL_EVAL_GRADIENT``)."""
+    import torch
+    from .functions import ConstantFunction, LinearSystem
+    keep = _on_device(points)
+    ctx = _ctx()
+    d_pts = _to_device(ctx, points)
+    n, d = d_pts.shape
+    ctx, builder = _builder(d)
+    builder.upload(ConstantFunction(np.zeros(1)), LinearSystem((np.eye(d), np.zeros((d, 1)))), spec, 0.0, 0.0, 0.0)
+    out = torch.empty((n, d), dtype=torch.float64, device=ctx.torch_device)
+    ctx.eval_points(_hip.EVAL_GRADIENT, n, d_pts, out)
+    return out if keep else out.cpu().numpy()
+
+
 def policy(spec, points):
     """``policy(points)`` -> ``[n, m]``."""
     import torch

@@ -26,10 +26,11 @@ OK, ERR_INVALID, ERR_HIP, ERR_UNSUPPORTED, ERR_NOMEM = 0, -1, -2, -3, -4
 POLICY_LINEAR, POLICY_CONST, POLICY_TABLE, POLICY_TRI, POLICY_NETWORK = 1, 2, 3, 4, 5
 DYN_LINEAR, DYN_PENDULUM, DYN_CARTPOLE, DYN_GP, DYN_POLYNOMIAL = 1, 2, 3, 4, 5
 POLY_MAX_TERMS, POLY_MAX_DEGREE = 64, 8
-V_QUADRATIC, V_TRI, V_NETWORK = 1, 2, 3
+V_QUADRATIC, V_TRI, V_NETWORK, V_POLYNOMIAL = 1, 2, 3, 4
+POLYV_MAX_ENTRIES = 256
 LIP_CONST, LIP_ABS_LINEAR, LIP_NORM_LINEAR, LIP_ABS_GRAD, LIP_NORM_GRAD = 0, 1, 2, 3, 4
 LF_CONST, LF_AFFINE_NORM1 = 0, 1
-EVAL_VALUE, EVAL_POLICY, EVAL_DYNAMICS, EVAL_DECREASE, EVAL_LV = 1, 2, 3, 4, 5
+EVAL_VALUE, EVAL_POLICY, EVAL_DYNAMICS, EVAL_DECREASE, EVAL_LV, EVAL_GRADIENT = 1, 2, 3, 4, 5, 6
 NN_LOSS_ABS, NN_LOSS_ROA = 1, 2
 
 c_double_p = C.POINTER(C.c_double)
@@ -146,6 +147,7 @@ SIGNATURES = {
     "sl_policy_touch": (_int, (_vp,)),
     "sl_dynamics_polynomial_set": (_int, (_vp, _int, _int, _int, _int32_p, c_double_p, C.POINTER(C.c_uint8), _int,
                                           _dbl)),
+    "sl_value_polynomial_set": (_int, (_vp, _int, _int, c_double_p, C.POINTER(C.c_uint8), _int, c_double_p)),
     "sl_gp_set_head": (_int, (_vp, _int, _int, _int, _int, _int, c_double_p, c_double_p, c_double_p, _dbl,
                               c_double_p)),
     "sl_gp_set_head_kernel": (_int, (_vp, _int, _int, _int, _int, _int, c_double_p, c_double_p, c_double_p,
@@ -393,6 +395,23 @@ class Context(object):
         self.lib.sl_dynamics_polynomial_set(self.handle, int(d), int(m), len(rows),
                                             rows.ctypes.data_as(_int32_p), pc,
                                             expo.ctypes.data_as(C.POINTER(C.c_uint8)), int(substeps), float(h))
+
+    def value_polynomial_set(self, d, coef, exponents, normalization=None):
+        """``sl_value_polynomial_set``: the term table of ``V_POLYNOMIAL`` - ``coef [nterms]``, ``exponents
+        [nterms, d]`` (small non-negative integers), ``normalization [d]`` (the scales ``T``) or ``None``."""
+        coef, pc = _as_c(np.reshape(coef, -1))
+        given = np.asarray(exponents, dtype=np.int64)
+        given = given.reshape(len(coef), -1) if len(coef) else np.zeros((0, int(d)), dtype=np.int64)
+        if given.shape[1] > MAX_STATE_DIM or (given < 0).any() or (given > 255).any():
+            raise ValueError("polynomial terms: exponents of shape %s (at most %d columns, entries in 0..255)"
+                             % (given.shape, MAX_STATE_DIM))
+        expo = np.zeros((len(coef), MAX_STATE_DIM), dtype=np.uint8)
+        expo[:, :given.shape[1]] = given
+        tx, ptx = _as_c(np.ones(MAX_STATE_DIM))
+        if normalization is not None:
+            tx[:len(normalization)] = np.asarray(normalization, dtype=np.float64)
+        self.lib.sl_value_polynomial_set(self.handle, int(d), len(coef), pc, expo.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                         0 if normalization is None else 1, ptx)
 
     def gp_set_head(self, head, X, Linv, alpha, col0, variance, lengthscales):
         X, pX = _as_c(X)

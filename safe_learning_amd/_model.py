@@ -12,7 +12,7 @@ from . import _hip
 from .functions import (AbsFunction, CartPole, ConstantFunction, FunctionStack,
                         GaussianProcess, Gradient, InvertedPendulum, LinearSystem, LyapunovNetwork,
                         NeuralNetwork,
-                        Norm1Function, PolynomialSystem, QuadraticFunction, Saturation, Triangulation, _gp_heads,
+                        Norm1Function, PolynomialFunction, PolynomialSystem, QuadraticFunction, Saturation, Triangulation, _gp_heads,
                         _is_plain_rbf)
 
 
@@ -39,6 +39,7 @@ class ModelBuilder(object):
         self._policy_source = None         # (tensor, its state) of a tensor policy used in place
         self._policy_net_signature = None
         self._poly_signature = None        # version token of the PolynomialSystem whose table the context holds
+        self._polyv_signature = None       # ... and of the PolynomialFunction
 
     # ---- pieces --------------------------------------------------------------------------
     def _write_policy(self, desc, policy):
@@ -245,15 +246,38 @@ class ModelBuilder(object):
             if signature != self._net_signature:
                 fun._upload(self.ctx)
                 self._net_signature = signature
+        elif isinstance(fun, PolynomialFunction):
+            fun._write_value(vd, self)               # (uploads the term table when it is a new one)
         else:
-            raise TypeError('unsupported value-function spec %r' % (fun,))
+            raise TypeError('unsupported value-function spec %r: use QuadraticFunction, Triangulation, '
+                            'LyapunovNetwork or PolynomialFunction' % (fun,))
 
-    def _write_lipschitz(self, ld, lipschitz_lyapunov, lipschitz_dynamics, tau):
+    @staticmethod
+    def _check_gradient_source(source, value_function):
+        """``Gradient(W)`` inside L_v is evaluated as the gradient of the value function the model holds.  Where
+        a ``PolynomialFunction`` is involved, ``W`` must be that function (``-V`` shares V's table and counts
+        as V): the gradient of another function would silently become the polynomial's, or the other way round."""
+        if value_function is None:
+            return
+        poly_w, poly_v = isinstance(source, PolynomialFunction), isinstance(value_function, PolynomialFunction)
+        if (poly_w or poly_v) and not (poly_w and poly_v and source._version == value_function._version):
+            raise ValueError('lipschitz_lyapunov takes the gradient of %s (%s), the Lyapunov function is %s (%s): '
+                             'Gradient(V) must be built on the Lyapunov function itself (or on -V)'
+                             % (type(source).__name__, getattr(source, 'name', '?'),
+                                type(value_function).__name__, getattr(value_function, 'name', '?')))
+
+    def _write_lipschitz(self, ld, lipschitz_lyapunov, lipschitz_dynamics, tau, value_function=None):
         d = self.grid.ndim
         if isinstance(lipschitz_lyapunov, Norm1Function) and lipschitz_lyapunov.constant != 0.0:
             raise TypeError('a constant offset is only supported for lipschitz_dynamics')
+        if isinstance(lipschitz_lyapunov, Gradient):
+            raise TypeError('a bare Gradient(V) (of a %s) is not a lipschitz_lyapunov: it is signed, and a signed '
+                            'gradient times the error bound of the dynamics is not a bound.  Use AbsGradient(V) '
+                            '(|dV/dx| per dimension) or Norm1Function(Gradient(V)) (||dV/dx||_1)'
+                            % type(lipschitz_lyapunov.fun).__name__)
         if (isinstance(lipschitz_lyapunov, (AbsFunction, Norm1Function))
                 and isinstance(lipschitz_lyapunov.fun, Gradient)):
+            self._check_gradient_source(lipschitz_lyapunov.fun.fun, value_function)
             ld.lv_kind = (_hip.LIP_ABS_GRAD if isinstance(lipschitz_lyapunov, AbsFunction)
                           else _hip.LIP_NORM_GRAD)
         elif isinstance(lipschitz_lyapunov, (AbsFunction, Norm1Function)):
@@ -303,8 +327,12 @@ class ModelBuilder(object):
         m = self._write_policy(desc, policy)
         self._write_dynamics(desc, dynamics, m)
         self._write_value(desc.value, value_function)
-        self._write_lipschitz(desc.lipschitz, lipschitz_lyapunov, lipschitz_dynamics, tau)
+        self._write_lipschitz(desc.lipschitz, lipschitz_lyapunov, lipschitz_dynamics, tau, value_function)
         if reward is not None:
+            if isinstance(reward, PolynomialFunction):
+                raise NotImplementedError('a PolynomialFunction (%s) as reward_function is not implemented: the '
+                                          'Bellman and rollout kernels take a QuadraticFunction on [x, u]'
+                                          % reward.name)
             if not isinstance(reward, QuadraticFunction):
                 raise TypeError('reward_function must be a QuadraticFunction on [x, u]')
             reward._write_value(desc.reward)

@@ -874,7 +874,8 @@ extern "C" int sl_bellman_sweep(sl_ctx* ctx, int64_t lo, int64_t hi, int n_actio
 // =============================================================================================
 __global__ __launch_bounds__(SL_BLOCK) void k_eval_simple(const SlDevModel M, SlAux aux, int what,
                                                           int64_t n, const double* __restrict__ points,
-                                                          double* __restrict__ out) {
+                                                          double* __restrict__ out,
+                                                          const SlPolyValue* __restrict__ polyv) {
     const SlDims nd = sl_dims<0, 0>(M);
     const int d = nd.d;
     for (int64_t i = (int64_t)blockIdx.x * SL_BLOCK + threadIdx.x; i < n;
@@ -883,15 +884,20 @@ __global__ __launch_bounds__(SL_BLOCK) void k_eval_simple(const SlDevModel M, Sl
 #pragma unroll
         for (int k = 0; k < SL_D; ++k) if (k < d) x[k] = points[i * d + k];
         if (what == SL_EVAL_VALUE) {
-            out[i] = sl_value_any<SL_FULL>(M, d, aux, x);
+            out[i] = sl_value_any<SL_FULL>(M, d, aux, x, polyv);
         } else if (what == SL_EVAL_POLICY) {
             double u[SL_M];
             sl_policy_any<true>(M, nd, aux.tri, 0, x, u);
 #pragma unroll
             for (int a = 0; a < SL_M; ++a) if (a < nd.m) out[i * nd.m + a] = u[a];
+        } else if (what == SL_EVAL_GRADIENT) {      // (sl_eval_points: SL_V_POLYNOMIAL only)
+            double g[SL_D];
+            sl_polyv_gradient(*polyv, d, M.m.value.negate, x, g);
+#pragma unroll
+            for (int k = 0; k < SL_D; ++k) if (k < d) out[i * d + k] = g[k];
         } else {   // SL_EVAL_LV
             double lv[SL_D];
-            sl_lv_any<SL_FULL>(M, d, aux, x, lv);
+            sl_lv_any<SL_FULL>(M, d, aux, x, lv, polyv);
             const int cols = M.m.lipschitz.lv_cols;
 #pragma unroll
             for (int k = 0; k < SL_D; ++k) if (k < cols) out[i * cols + k] = lv[k];
@@ -930,7 +936,10 @@ extern "C" int sl_eval_points(sl_ctx* ctx, int what, int64_t n, const double* d_
         SL_HIP_CHECK(ctx, hipGetLastError());
         return SL_OK;
     }
-    if (what == SL_EVAL_VALUE || what == SL_EVAL_POLICY || what == SL_EVAL_LV) {
+    if (what == SL_EVAL_GRADIENT && M.m.value.kind != SL_V_POLYNOMIAL)
+        return sl_fail(ctx, SL_ERR_UNSUPPORTED, "sl_eval_points: SL_EVAL_GRADIENT is implemented for a polynomial "
+                                                "value function (SL_V_POLYNOMIAL) only");
+    if (what == SL_EVAL_VALUE || what == SL_EVAL_POLICY || what == SL_EVAL_LV || what == SL_EVAL_GRADIENT) {
         if (what == SL_EVAL_POLICY && M.m.policy.kind == SL_POLICY_TABLE)
             return sl_fail(ctx, SL_ERR_UNSUPPORTED, "a per-vertex policy table cannot be evaluated "
                                                     "at arbitrary points");
@@ -942,7 +951,7 @@ extern "C" int sl_eval_points(sl_ctx* ctx, int what, int64_t n, const double* d_
         if (b > SL_MAX_GRID) b = SL_MAX_GRID;
         SlAux aux{ctx->d_tri, ctx->d_net};
         hipLaunchKernelGGL(k_eval_simple, dim3((unsigned)b), dim3(SL_BLOCK), 0, ctx->stream,
-                           ctx->h_model, aux, what, n, d_points, d_out);
+                           ctx->h_model, aux, what, n, d_points, d_out, ctx->d_polyv);
         SL_HIP_CHECK(ctx, hipGetLastError());
         return SL_OK;
     }

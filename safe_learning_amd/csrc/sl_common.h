@@ -99,6 +99,9 @@ struct sl_ctx {
     SlPolyTable h_poly = {};       // term table of SL_DYN_POLYNOMIAL (sl_dynamics_polynomial_set)
     SlPolyTable* d_poly = nullptr; // its device copy: the model the kernels get points at it
     bool poly_set = false;
+    SlPolyValue h_polyv = {};      // term table of SL_V_POLYNOMIAL (sl_value_polynomial_set)
+    SlPolyValue* d_polyv = nullptr;   // its device copy: handed to the kernels that take the kind as an argument
+    bool polyv_set = false;
     double* d_net_kernels = nullptr;
 
     void* d_scratch = nullptr;         // grown on demand (sl_eval_points)
@@ -287,6 +290,10 @@ int sl_bellman4_launch(sl_ctx* ctx, const SlBellmanArgs& b);
 int sl_bellman4_policy_launch(sl_ctx* ctx, const SlBellmanArgs& b);
 int sl_nn_values_launch(sl_ctx* ctx, int64_t lo, int64_t hi, double* d_values);
 int sl_nn_check_launch(sl_ctx* ctx, const SlSweepArgs& a, const double* d_records, int* nblocks);
+// polynomial V (sl_poly_value.hip): values, the deterministic sweep, the check over posterior records
+int sl_poly_values_launch(sl_ctx* ctx, int64_t lo, int64_t hi, double* d_values);
+int sl_poly_sweep_launch(sl_ctx* ctx, const SlSweepArgs& a, int* nblocks);
+int sl_poly_check_launch(sl_ctx* ctx, const SlSweepArgs& a, const double* d_records, int* nblocks);
 
 #define SL_HIP_CHECK(ctx, call)                                                             \
     do {                                                                                    \
@@ -498,15 +505,37 @@ __device__ __forceinline__ SlAux sl_stage_aux(SlTriLds<ON>& lds, const SlAux& au
 // per-thread LyapunovNetwork (4.6 KB of private arrays per lane).  The grid sweeps never need
 // SL_FULL: a network V is routed to the matrix-core kernels of sl_nn.hip, so their "general"
 // instantiations are compiled as SL_TABLES and carry no network scratch; only the point
-// evaluation of sl_eval_points uses SL_FULL.
+// evaluation of sl_eval_points uses SL_FULL.  A polynomial V (SL_V_POLYNOMIAL) is a fourth kind that only
+// SL_FULL knows: the sweeps route it to the kernels of sl_poly_value.hip, which take its term table as an
+// argument, so neither SL_FAST nor SL_TABLES carries its code.
 enum { SL_FAST = 0, SL_FULL = 1, SL_TABLES = 2 };
 template <bool GENERAL> struct SlSweepFlavour { static constexpr int value = GENERAL ? SL_TABLES : SL_FAST; };
 
-// V(z)
+// L_v(z) of a polynomial V (the table is a kernel argument of the kernels that take the kind)
+__device__ __forceinline__ void sl_polyv_lv(const SlDevModel& M, const SlPolyValue& table, int d, const double* z,
+                                            double* lv) {
+    const int kind = M.m.lipschitz.lv_kind;
+    if (kind != SL_LIP_ABS_GRAD && kind != SL_LIP_NORM_GRAD) { sl_lv(M, d, z, lv); return; }
+    double g[SL_D];
+    sl_polyv_gradient(table, d, M.m.value.negate, z, g);
+    if (kind == SL_LIP_ABS_GRAD) {
+#pragma unroll
+        for (int k = 0; k < SL_D; ++k) if (k < d) lv[k] = fabs(g[k]);
+    } else {
+        double acc = fabs(g[0]);
+#pragma unroll
+        for (int k = 1; k < SL_D; ++k) if (k < d) acc = acc + fabs(g[k]);
+        lv[0] = acc;
+    }
+}
+
+// V(z).  polyv: the table of SL_V_POLYNOMIAL, read by the SL_FULL flavour only (the sweeps route the kind
+// to the kernels of sl_poly_value.hip)
 template <int G>
 __device__ __forceinline__ double sl_value_any(const SlDevModel& M, int d, const SlAux& aux,
-                                               const double* z) {
+                                               const double* z, const SlPolyValue* polyv = nullptr) {
     if (G == SL_FAST || M.m.value.kind == SL_V_QUADRATIC) return sl_quadratic(M.m.value, d, z);
+    if (G == SL_FULL && M.m.value.kind == SL_V_POLYNOMIAL) return sl_polyv_value(*polyv, d, M.m.value.negate, z);
     if (G == SL_TABLES || M.m.value.kind == SL_V_TRI) {
         double v = sl_tri_eval(aux.tri[0], z, 0, nullptr);
         return M.m.value.negate ? (v * -1.0) : v;
@@ -518,9 +547,10 @@ __device__ __forceinline__ double sl_value_any(const SlDevModel& M, int d, const
 // L_v(z) including |grad V|
 template <int G>
 __device__ __forceinline__ void sl_lv_any(const SlDevModel& M, int d, const SlAux& aux,
-                                          const double* z, double* lv) {
+                                          const double* z, double* lv, const SlPolyValue* polyv = nullptr) {
     const int kind = M.m.lipschitz.lv_kind;
     if (G == SL_FAST || (kind != SL_LIP_ABS_GRAD && kind != SL_LIP_NORM_GRAD)) { sl_lv(M, d, z, lv); return; }
+    if (G == SL_FULL && M.m.value.kind == SL_V_POLYNOMIAL) { sl_polyv_lv(M, *polyv, d, z, lv); return; }
     double g[SL_D];
     if (G == SL_TABLES || M.m.value.kind == SL_V_TRI) sl_tri_eval(aux.tri[0], z, 0, g);
     else sl_network_value(*aux.net, z, d, g);

@@ -163,6 +163,7 @@ extern "C" int sl_ctx_destroy(sl_ctx* ctx) {
     if (ctx->succ.d_select) (void)hipFree(ctx->succ.d_select);
     if (ctx->d_records) (void)hipFree(ctx->d_records);
     if (ctx->d_poly) (void)hipFree(ctx->d_poly);
+    if (ctx->d_polyv) (void)hipFree(ctx->d_polyv);
     (void)sl_timing_configure(ctx, 0);
     (void)hipFree(ctx->d_partials);
     (void)hipFree(ctx->d_partial_counts);
@@ -282,8 +283,16 @@ extern "C" int sl_model_set(sl_ctx* ctx, const sl_model_desc* h_model) {
         return sl_fail(ctx, SL_ERR_INVALID, "cart-pole dynamics need d=4, m=1");
     M.uncertain = (dk == SL_DYN_GP);
     const int vk = M.m.value.kind;
-    if (vk < SL_V_QUADRATIC || vk > SL_V_NETWORK)
+    if (vk < SL_V_QUADRATIC || vk > SL_V_POLYNOMIAL)
         return sl_fail(ctx, SL_ERR_INVALID, "unknown value-function kind %d", vk);
+    if (vk == SL_V_POLYNOMIAL) {
+        if (!ctx->polyv_set)
+            return sl_fail(ctx, SL_ERR_INVALID, "polynomial value function (SL_V_POLYNOMIAL) without a term table: "
+                                                "call sl_value_polynomial_set first");
+        if (ctx->h_polyv.d != M.m.grid.d)
+            return sl_fail(ctx, SL_ERR_INVALID, "polynomial value function: the term table of "
+                           "sl_value_polynomial_set is for %d states, the model has %d", ctx->h_polyv.d, M.m.grid.d);
+    }
     const int lk = M.m.lipschitz.lv_kind;
     if (lk < SL_LIP_CONST || lk > SL_LIP_NORM_GRAD)
         return sl_fail(ctx, SL_ERR_INVALID, "unknown L_v kind %d", lk);
@@ -330,6 +339,33 @@ extern "C" int sl_dynamics_polynomial_set(sl_ctx* ctx, int d, int m, int nterms,
     ctx->h_poly = table;
     ctx->poly_set = true;
     ++ctx->dynamics_token;
+    return SL_OK;
+}
+
+// The term table of SL_V_POLYNOMIAL (value row and gradient rows, csrc/sl_poly_value.h).  Like the
+// dynamics' table it is not part of the model description's bytes.  Nothing the context keeps between
+// calls is derived from a polynomial V (the implicit keys, the successor cache and the deciding pass of
+// the GP sweep belong to quadratic and table functions), so a new table needs no token: the next launch
+// reads it.
+extern "C" int sl_value_polynomial_set(sl_ctx* ctx, int d, int nterms, const double* h_coef,
+                                       const uint8_t* h_exponents, int normalize, const double* h_tx) {
+    if (!ctx) return sl_fail(nullptr, SL_ERR_INVALID, "sl_value_polynomial_set: NULL context");
+    SlPolyValue table;
+    char msg[240];
+    if (sl_polyv_build(&table, d, nterms, h_coef, h_exponents, normalize, h_tx, msg, sizeof(msg)) != SL_OK)
+        return sl_fail(ctx, SL_ERR_INVALID, "sl_value_polynomial_set: %s", msg);
+    SL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (!ctx->d_polyv) SL_HIP_CHECK(ctx, hipMalloc(&ctx->d_polyv, sizeof(SlPolyValue)));
+    // launches that read the old table may still be queued: wait for them, then replace it
+    SL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    SL_HIP_CHECK(ctx, hipMemcpy(ctx->d_polyv, &table, sizeof(SlPolyValue), hipMemcpyHostToDevice));
+    ctx->h_polyv = table;
+    ctx->polyv_set = true;
+    // a model of the kind that is set pairs its d with the table's rows: under a table of another dimension
+    // it is no model any more - every entry point asks for sl_model_set until one is set again (the table has to
+    // come first, so the call itself cannot refuse)
+    if (ctx->model_set && ctx->h_model.m.value.kind == SL_V_POLYNOMIAL && ctx->h_model.m.grid.d != d)
+        ctx->model_set = false;
     return SL_OK;
 }
 
@@ -520,6 +556,7 @@ extern "C" int sl_values(sl_ctx* ctx, int64_t lo, int64_t hi, double* d_values) 
     if (hi == lo) return SL_OK;
     SL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     if (ctx->h_model.m.value.kind == SL_V_NETWORK) return sl_nn_values_launch(ctx, lo, hi, d_values);
+    if (ctx->h_model.m.value.kind == SL_V_POLYNOMIAL) return sl_poly_values_launch(ctx, lo, hi, d_values);
     SlAux aux{ctx->d_tri, ctx->d_net};
     const int blocks = sl_grid_blocks(hi - lo);
     return sl_with_flavour(sl_model_is_general(ctx->h_model), sl_dim_variant_of(ctx->h_model), [&](auto g, auto d, auto m) {
@@ -847,6 +884,20 @@ static int sweep_network_value(sl_ctx* ctx, const SlSweepArgs& a, int* blocks) {
     return sl_nn_check_launch(ctx, a, posterior.dbg, blocks);
 }
 
+// polynomial V: the "general" instantiations of the sweeps below take a non-quadratic V for a table, so
+// the kind goes round them - deterministic dynamics to k_poly_sweep, GP dynamics to the posterior pass
+// and k_poly_check over its records
+static int sweep_polynomial_value(sl_ctx* ctx, const SlSweepArgs& a, int* blocks) {
+    if (ctx->h_model.m.value.kind != SL_V_POLYNOMIAL) return SL_DECLINED;
+    if (ctx->h_model.m.dynamics.kind != SL_DYN_GP) return sl_poly_sweep_launch(ctx, a, blocks);
+    SlSweepArgs posterior{};
+    int gp_blocks = 0;
+    int rc = sl_posterior_pass(ctx, a, 0, &posterior);
+    if (!rc) rc = sl_gp_sweep_launch(ctx, sl_posterior_only(ctx->h_model), posterior, &gp_blocks);
+    if (rc) return rc;
+    return sl_poly_check_launch(ctx, a, posterior.dbg, blocks);
+}
+
 // table flavours (V, L_v = |grad V|, interpolated policy) of a GP model whose heads are served by
 // k_gp_sweep4: action table + posterior records + check instead of k_gp_sweep's 16x16x4 structure
 static int sweep_gp_three_pass(sl_ctx* ctx, const SlSweepArgs& a, int* blocks) {
@@ -944,7 +995,7 @@ int sl_sweep_any(sl_ctx* ctx, const SlSweepArgs& a, sl_sweep_result* d_result, b
     int blocks = 0;
     ctx->last_kernel[0] = 0;
     if (a.hi > a.lo) {
-        for (auto launch : {sweep_network_value, sweep_gp_three_pass, sweep_gp, sl_det_rows_launch, sweep_det}) {
+        for (auto launch : {sweep_polynomial_value, sweep_network_value, sweep_gp_three_pass, sweep_gp, sl_det_rows_launch, sweep_det}) {
             rc = launch(ctx, a, &blocks);
             if (rc != SL_DECLINED) break;
         }

@@ -33,6 +33,7 @@
 #define SL_P SL_MAX_INPUT_DIM
 
 #include "sl_polynomial.h"
+#include "sl_poly_value.h"
 
 // Device-side view of one auxiliary grid with a vertex table (Triangulation).
 #define SL_TRI_CODES   64      // 2^(pairs of coordinates), d <= 4

@@ -253,6 +253,10 @@ extern "C" int sl_decrease_gradient(sl_ctx* ctx, int64_t n, const double* d_poin
     if (md.value.kind == SL_V_NETWORK)
         return sl_fail(ctx, SL_ERR_UNSUPPORTED, "sl_decrease_gradient: a network Lyapunov function (SL_V_NETWORK) is "
                        "not differentiated; use a quadratic form or a table");
+    if (md.value.kind == SL_V_POLYNOMIAL)
+        return sl_fail(ctx, SL_ERR_UNSUPPORTED, "sl_decrease_gradient: a polynomial Lyapunov function "
+                       "(SL_V_POLYNOMIAL) is not differentiated: the derivative of |grad V| needs second "
+                       "derivatives; use a quadratic form or a table");
     const int d = md.grid.d, m = md.policy.m, p = ctx->h_model.in_dim;
     if (md.value.kind == SL_V_TRI && (!ctx->h_tri[0].set || ctx->h_tri[0].grid.d != d))
         return sl_fail(ctx, SL_ERR_INVALID, "sl_decrease_gradient: the Lyapunov table must be slot 0, on %d dimensions", d);

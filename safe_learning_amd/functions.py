@@ -48,7 +48,7 @@ __all__ = ['GridWorld', 'DimensionError', 'DeterministicFunction', 'UncertainFun
            'QuadraticFunction', 'LinearSystem', 'Saturation', 'AbsFunction', 'Norm1Function',
            'AbsGradient', 'Gradient', 'ConstantFunction', 'RBF', 'Matern32', 'Linear', 'GPRCached', 'GaussianProcess',
            'FunctionStack', 'Triangulation', 'InvertedPendulum', 'CartPole', 'PolynomialSystem', 'VanDerPol',
-           'LyapunovNetwork',
+           'PolynomialFunction', 'monomial_exponents', 'LyapunovNetwork',
            'NeuralNetwork']
 
 
@@ -1022,6 +1022,120 @@ class VanDerPol(PolynomialSystem):
     def linearize(self):
         """``Ad`` of the discretised linearisation in normalised coordinates (``examples/utilities.py:471-487``)."""
         return super(VanDerPol, self).linearize()[0]
+
+
+# ----------------------------------------------------------------------------------------------
+# polynomial Lyapunov / value function
+# ----------------------------------------------------------------------------------------------
+
+def monomial_exponents(input_dim, degree):
+    """Exponent rows of the monomial basis ``m(z)`` of total degree 1 .. ``degree`` (no constant term):
+    graded, the first variable's power descending inside a degree.  Two variables, degree 3:
+    ``x, y, x^2, xy, y^2, x^3, x^2 y, x y^2, y^3`` - the column order of ``examples/utilities.py:753-782``."""
+    input_dim, degree = int(input_dim), int(degree)
+    if input_dim < 1 or degree < 1:
+        raise ValueError('monomial_exponents: input_dim and degree must be at least 1')
+
+    def rows(n, total):
+        if n == 1:
+            return [(total,)]
+        return [(first,) + rest for first in range(total, -1, -1) for rest in rows(n - 1, total - first)]
+
+    return np.array([row for total in range(1, degree + 1) for row in rows(input_dim, total)], dtype=np.int64)
+
+
+class PolynomialFunction(DeterministicFunction):
+    """A Lyapunov / value function that is a polynomial in the state, given as data: the way to state a
+    candidate of one's own (a sum-of-squares certificate, a Taylor model) where a quadratic form is too
+    little, without a callable.
+
+    ``terms`` is a list of ``(coefficient, exponents)`` with one non-negative integer exponent per state:
+    ``V(x) = sum_t c_t * prod_q (x_q * T_q) ** e_tq`` with ``T = normalization`` (``None``: no scaling) - the
+    argument is scaled UP by ``T``, as ``x *= state_norm`` in ``lyapunov_function_learning.ipynb`` cell 17.
+    ``V(points)`` and ``V.gradient(points)`` (with respect to the argument: the chain factor ``T_k`` is
+    included) run on the device; ``-V`` is supported.  ``Gradient(V)`` inside ``AbsFunction`` /
+    ``Norm1Function`` is the local Lipschitz constant.  Limits: ``input_dim <= MAX_STATE_DIM`` (6), total degree
+    of a term ``<= POLY_MAX_DEGREE`` (8), and ``POLYV_MAX_ENTRIES`` (256) entries in the device table, which
+    holds the value row and one row per partial derivative (a term counts once, and once more for every
+    variable it contains).  The engine evaluates every term by repeated multiplication in the order given
+    (``csrc/sl_poly_value.h``)."""
+
+    _role = 'value'
+
+    def __init__(self, terms, input_dim, normalization=None, name='polynomial_function'):
+        self.input_dim = self.ndim = int(input_dim)
+        self.output_dim = 1
+        self.name = name
+        d = self.input_dim
+        if not 1 <= d <= _hip.MAX_STATE_DIM:
+            raise ValueError('PolynomialFunction: input_dim = %d, the engine takes 1..MAX_STATE_DIM = %d'
+                             % (d, _hip.MAX_STATE_DIM))
+        coef, expo = [], []
+        for t, (coefficient, exponents) in enumerate(terms):
+            exponents = list(np.atleast_1d(np.asarray(exponents)).tolist())
+            if len(exponents) != d:
+                raise ValueError('PolynomialFunction: term %d has %d exponents, input_dim = %d'
+                                 % (t, len(exponents), d))
+            if any(isinstance(e, bool) or e != int(e) for e in exponents):
+                raise ValueError('PolynomialFunction: term %d has a non-integer exponent %r' % (t, exponents))
+            exponents = [int(e) for e in exponents]
+            if min(exponents) < 0:
+                raise ValueError('PolynomialFunction: term %d has a negative exponent %r' % (t, exponents))
+            if sum(exponents) > _hip.POLY_MAX_DEGREE:
+                raise ValueError('PolynomialFunction: term %d has total degree %d, the engine takes POLY_MAX_DEGREE = %d'
+                                 % (t, sum(exponents), _hip.POLY_MAX_DEGREE))
+            coef.append(float(coefficient))
+            expo.append(exponents)
+        entries = len(coef) + sum(1 for e in expo for v in e if v > 0)
+        if entries > _hip.POLYV_MAX_ENTRIES:
+            raise ValueError('PolynomialFunction: %d terms need %d entries of the device table (value row and '
+                             'gradient rows), the engine takes POLYV_MAX_ENTRIES = %d'
+                             % (len(coef), entries, _hip.POLYV_MAX_ENTRIES))
+        self.terms = [(c, tuple(e)) for c, e in zip(coef, expo)]
+        self._coef = np.array(coef, dtype=np.float64)
+        self._expo = np.array(expo, dtype=np.uint8).reshape(len(coef), d)
+        if normalization is None:
+            self.normalization = None
+        else:
+            self.normalization = np.array(normalization, dtype=np.float64).reshape(-1)
+            if self.normalization.shape != (d,):
+                raise ValueError('PolynomialFunction: normalization holds %d scales, input_dim = %d'
+                                 % (len(self.normalization), d))
+        self._version = next(_TOKENS)          # a spec is immutable: one upload per context
+
+    @classmethod
+    def from_gram(cls, Q, degree, input_dim, normalization=None, name='polynomial_function'):
+        """``m(z)^T Q m(z)`` with ``m`` the basis of :func:`monomial_exponents`, expanded into a term table
+        on the host: one term per distinct monomial in order of first appearance over ``(i, j)`` row-major,
+        its coefficient the sum of the ``Q_ij`` that produce it, added in that order.  ``Q`` need not be
+        symmetric or definite."""
+        basis = monomial_exponents(input_dim, degree)
+        Q = np.asarray(Q, dtype=np.float64)
+        if Q.shape != (len(basis), len(basis)):
+            raise ValueError('PolynomialFunction.from_gram: Q is %s, the basis of degree %d in %d variables has %d '
+                             'monomials' % (Q.shape, degree, input_dim, len(basis)))
+        coefficients = {}
+        for i in range(len(basis)):
+            for j in range(len(basis)):
+                key = tuple(int(e) for e in basis[i] + basis[j])
+                coefficients[key] = Q[i, j] if key not in coefficients else coefficients[key] + Q[i, j]
+        return cls([(float(c), key) for key, c in coefficients.items()], input_dim, normalization, name=name)
+
+    def gradient(self, points):
+        """``dV/dx`` at ``points`` ``[n, input_dim]`` -> ``[n, input_dim]`` (device tensors stay on the
+        device), evaluated on the GPU."""
+        from . import _evaluate
+        return _evaluate.value_gradient(self, points)
+
+    def _write_value(self, desc, builder):
+        if builder.grid.ndim != self.input_dim:
+            raise ValueError('%s takes %d inputs, the grid has %d dimensions'
+                             % (type(self).__name__, self.input_dim, builder.grid.ndim))
+        desc.kind = _hip.V_POLYNOMIAL
+        desc.negate = int(self.negate)
+        if builder._polyv_signature != self._version:
+            builder.ctx.value_polynomial_set(self.input_dim, self._coef, self._expo, self.normalization)
+            builder._polyv_signature = self._version
 
 
 # ----------------------------------------------------------------------------------------------

@@ -342,6 +342,7 @@ class Lyapunov(object):
         import torch
         from . import _evaluate
         from .functions import CartPole, InvertedPendulum, LyapunovNetwork, PolynomialSystem, UncertainFunction
+        self._refuse_polynomial_value('decrease_gradient')
         if isinstance(self.lyapunov_function, LyapunovNetwork):
             raise TypeError('the gradient of the Lyapunov penalty is implemented for a quadratic or table '
                             'Lyapunov function, not for a LyapunovNetwork')
@@ -373,6 +374,15 @@ class Lyapunov(object):
         constraint = torch.empty((n, 1), dtype=torch.float64, device=ctx.torch_device)
         ctx.decrease_gradient(n, d_states, d_actions, grad, constraint)
         return (grad, constraint) if keep else (grad.cpu().numpy(), constraint.cpu().numpy())
+
+    def _refuse_polynomial_value(self, what):
+        from .functions import PolynomialFunction
+        fun = getattr(self, '_lyapunov_function', None)
+        if isinstance(fun, PolynomialFunction):
+            raise NotImplementedError('%s (and with it policy_gradient / action_gradient(lyapunov=...)) with a '
+                                      'PolynomialFunction (%s) as the Lyapunov function is not implemented: the '
+                                      'derivative of |grad V| needs second derivatives of the polynomial'
+                                      % (what, fun.name))
 
     @property
     def values(self):

@@ -33,6 +33,12 @@ class PolicyIteration(object):
     """See ``reinforcement_learning.py:26-63`` for the argument meanings."""
 
     def __init__(self, policy, dynamics, reward_function, value_function, gamma=0.98):
+        from .functions import PolynomialFunction
+        for role, spec in (('value_function', value_function), ('reward_function', reward_function)):
+            if isinstance(spec, PolynomialFunction):
+                raise NotImplementedError('a PolynomialFunction (%s) as the %s of PolicyIteration is not implemented: '
+                                          'dynamic programming takes a Triangulation value function and a '
+                                          'QuadraticFunction reward' % (spec.name, role))
         if not isinstance(value_function, Triangulation):
             raise TypeError('value_function must be a Triangulation')
         self.policy = policy

@@ -101,6 +101,10 @@ def roa_classification_step(lyapunov, states, roa_labels, class_weights, safe_le
     from . import _evaluate
     _check_single_process()
     network = lyapunov.lyapunov_function
+    from .functions import PolynomialFunction
+    if isinstance(network, PolynomialFunction):
+        raise NotImplementedError('roa_classification_step trains a LyapunovNetwork; a PolynomialFunction (%s) has '
+                                  'no trainable parameters in the engine' % network.name)
     if not hasattr(network, '_kernel_gradient') or network.negate:
         raise TypeError('lyapunov.lyapunov_function must be a LyapunovNetwork')
     ctx = _evaluate._ctx()

@@ -151,6 +151,11 @@ def main():
              "* `polynomial_dynamics.md`, `polynomial_probe.jsonl`: polynomial dynamics (`SL_DYN_POLYNOMIAL`, csrc/sl_polynomial.h): registers "
              "and scratch of the new instantiations, Van der Pol against the pendulum in the same kernels, and the eight entries of "
              "`pmc_valu.json` before and after the edit of the shared headers (`tools/polynomial_probe.py`; DESIGN.md 4.2c).",
+             "* `polynomial_value.md`, `polynomial_value_probe.jsonl`: polynomial Lyapunov functions (`SL_V_POLYNOMIAL`, csrc/sl_poly_value.h, "
+             "csrc/sl_poly_value.hip): registers, scratch and LDS of the seven new instantiations and of `k_eval_simple` before and after, the "
+             "notebook's SOS candidate beside the LQR quadratic and a 101^2 table on the 2001 x 1501 pendulum grid, a quartic at 64^4 under "
+             "the cart-pole, and `bench.py` against the parent's library on one box (`tools/polynomial_value_probe.py`, "
+             "`tools/kernel_resources.py`; DESIGN.md 4.2d).",
              "* `gp_posterior_truth.md`: the GP posterior of `k_gp_sweep4`, `k_gp_sweep` and `k_gp_small` against the posterior in "
              "extended precision (`tests/np_gp_truth.py`): per case cond(K), the oracle's own error, a NumPy restatement of the "
              "engine's formula and the engine's measured error (`tests/test_gpu_gp_truth.py`; DESIGN.md 6 (iv)).",
