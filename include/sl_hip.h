@@ -302,6 +302,13 @@ SL_API int  sl_gp4_halves_configure(sl_ctx* ctx, int enable);
  * enable = 0 switches the pass off (A/B runs and tests); spacing = 0 keeps the spacing (default 8).
  * Belongs to the context, takes effect at its next sweep. */
 SL_API int  sl_gp4_predecide_configure(sl_ctx* ctx, int enable, int spacing);
+/* The blocks that pass left open, as the list the mean pass of the context's LAST sweep worked through:
+ * 32-bit block numbers 4 tile + jb in ascending order (tile t of the shard starts at cell lo + 64 t,
+ * block jb 16 jb cells further).  *count = the list's length; the first min(cap, *count) entries
+ * go to out (cap = 0: the length only); *used = 1 when the mean pass ran from the list
+ * (k_gp_mean_open), 0 when the sweep had none - no deciding pass, or a shard of 2^29 tiles or more -
+ * and then *count = 0.  Waits for the context's stream.  For tests and diagnostics. */
+SL_API int  sl_gp4_open_list(sl_ctx* ctx, uint32_t* out, int64_t cap, unsigned long long* count, int* used);
 
 /* Auxiliary grid #slot with a per-vertex table (Triangulation: functions.py:1002-1032,
  * 1064-1101): slot 0 = value function, slot 1 = policy.  h_simplices [nsimplex][d+1] are the

@@ -160,6 +160,7 @@ SIGNATURES = {
     "sl_gp4_segment_configure": (_int, (_vp, _int)),
     "sl_gp4_halves_configure": (_int, (_vp, _int)),
     "sl_gp4_predecide_configure": (_int, (_vp, _int, _int)),
+    "sl_gp4_open_list": (_int, (_vp, C.POINTER(C.c_uint32), _i64, C.POINTER(C.c_ulonglong), C.POINTER(_int))),
     "sl_tri_set": (_int, (_vp, _int, C.POINTER(GridDesc), _int, _int32_p, c_double_p, c_double_p, _int, _int,
                           _vp)),
     "sl_tri_set_table": (_int, (_vp, _int, _vp)),
@@ -791,6 +792,21 @@ class Context(object):
         """Name of the kernel(s) the last sweep of this context launched (``sl_last_kernel``)."""
         name = self.lib.sl_last_kernel(self.handle)
         return name.decode() if name else ""
+
+    def gp4_open_list(self, entries=True):
+        """``(list, used)`` of the last sweep (``sl_gp4_open_list``): the 16-cell blocks its deciding pass
+        left open as a ``uint32`` array of block numbers (``entries=False``: only their number, an int), and
+        whether the mean pass ran from that list."""
+        import numpy as np
+        count, used = C.c_ulonglong(0), C.c_int(0)
+        self.lib.sl_gp4_open_list(self.handle, None, 0, C.byref(count), C.byref(used))
+        if not entries:
+            return int(count.value), bool(used.value)
+        out = np.zeros(int(count.value), dtype=np.uint32)
+        if len(out):
+            self.lib.sl_gp4_open_list(self.handle, out.ctypes.data_as(C.POINTER(C.c_uint32)), len(out),
+                                      C.byref(count), C.byref(used))
+        return out, bool(used.value)
 
     # ---- RCCL collectives of the C ABI (the package itself uses torch.distributed) ---------
     @staticmethod

@@ -131,6 +131,29 @@ SL_HD bool sure_fail(const sl_value_desc& v, int d, int p, const PreConst& k, co
 
 #if defined(__HIPCC__)
 #include "sl_common.h"
+#include "sl_gp4_open.h"
+
+// The open-block list of the pass (sl_gp4_open.h) lies in ctx->d_gp4_pre around the tile bytes: a head
+// of gp4o::HEAD_BYTES in front of them, behind them one count per chunk of tiles and then the list
+// itself, sized for every block open.  Everything follows from the address of the tile bytes and the
+// number of tiles, so the context carries nothing new.
+struct Gp4OpenView {
+    unsigned long long* head;        // [gp4o::HEAD_LENGTH], [gp4o::HEAD_NTILES], [gp4o::HEAD_BUILT]
+    unsigned* counts;                // open blocks of every chunk
+    unsigned* list;                  // block numbers 4 tile + jb, ascending
+};
+inline Gp4OpenView sl_gp4_open_view(const unsigned char* tiles, long long ntiles) {
+    unsigned char* t = const_cast<unsigned char*>(tiles);
+    Gp4OpenView v;
+    v.head = reinterpret_cast<unsigned long long*>(t - gp4o::HEAD_BYTES);
+    v.counts = reinterpret_cast<unsigned*>(t + gp4o::tile_bytes(ntiles));
+    v.list = reinterpret_cast<unsigned*>(t + gp4o::tile_bytes(ntiles) + gp4o::count_bytes(ntiles));
+    return v;
+}
+// May the mean pass of a shard of ntiles tiles run from the list?  (block numbers and list positions are 32 bits)
+inline bool sl_gp4_open_fits(long long ntiles) { return 4 * ntiles < (1ll << 31); }
+// k_gp_open_count and k_gp_open_scatter over the tile bytes k_gp_predecide has just written, on the context's stream
+int sl_gp4_open_build(sl_ctx* ctx, const unsigned char* tiles, long long ntiles);
 
 struct Gp4PreLaunch {
     int workgroups;                  // one key per wavefront: 4 workgroups keys, written (not folded)

@@ -12,6 +12,12 @@
 //    gp4p::sure_fail against the nearest lattice point.  A 16-cell block whose valid cells are all
 //    sure to fail writes its 16 mask bits (zeros) with the 2-byte store, folds the key of its cells
 //    outside the initial set and sets its bit in the tile's byte.
+//  * k_gp_open_count and k_gp_open_scatter, directly behind it: the blocks the pass left open as an
+//    ascending list of block numbers (sl_gp4_open.h), which k_gp_mean_open (sl_gp4_mean.hip) works
+//    through instead of walking every tile.  One workgroup per chunk of 4096 tiles counts the chunk's
+//    open blocks; in the second kernel it adds up the counts of the chunks before its own and writes
+//    its entries behind them.  No workgroup waits for another; both kernels do not depend on the
+//    state dimension and are compiled once.
 // Compiled once per state dimension like sl_gp4_mean.hip.
 #include "sl_common.h"
 #include "sl_gp4_predecide.h"
@@ -155,6 +161,89 @@ __global__ __launch_bounds__(256) void k_gp_predecide(
     }
 }
 
+#if !defined(SL_GP4_DIM) || SL_GP4_DIM == 4
+namespace gp4o {
+constexpr int LANES = 256;                                   // of a workgroup of the two list kernels
+constexpr int ROUNDS = CHUNK_TILES / (4 * LANES);            // words per lane, one a round
+static_assert(ROUNDS * 4 * LANES == CHUNK_TILES, "a chunk is a whole number of rounds");
+
+// the open mask of the lane's word of round r of chunk `chunk` (0 behind the shard's last tile); t: its first tile
+__device__ __forceinline__ uint32_t lane_mask(const unsigned* __restrict__ words, long long ntiles, long long chunk,
+                                              int r, long long& t) {
+    t = chunk * CHUNK_TILES + 4 * (long long)(r * LANES + (int)threadIdx.x);
+    if (t >= ntiles) return 0u;
+    const long long left = ntiles - t;
+    return open_mask16(words[t >> 2], left < 4 ? (int)left : 4);
+}
+// sum of v over the workgroup, on every lane (part: one word per wavefront; two barriers)
+__device__ __forceinline__ unsigned group_sum(unsigned v, unsigned* part) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    __syncthreads();                                         // (the last readers of part are done)
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return part[0] + part[1] + part[2] + part[3];
+}
+}  // namespace gp4o
+
+// counts[c] = open blocks of chunk c of the tile bytes (read as words: sl_gp4_open.h)
+__global__ __launch_bounds__(256) void k_gp_open_count(const unsigned* __restrict__ words, long long ntiles,
+                                                       unsigned* __restrict__ counts) {
+    __shared__ unsigned part[4];
+    unsigned c = 0u;
+#pragma unroll
+    for (int r = 0; r < gp4o::ROUNDS; ++r) {
+        long long t;
+        c += (unsigned)__popc(gp4o::lane_mask(words, ntiles, blockIdx.x, r, t));
+    }
+    c = gp4o::group_sum(c, part);
+    if (threadIdx.x == 0) counts[blockIdx.x] = c;
+}
+
+// The entries of chunk c at position sum(counts[0 .. c)) of the list, ascending; the workgroup of the
+// last chunk writes the head.  (At most 4 ntiles entries, what the list is sized for.)
+// Every workgroup adds up the counts before its own: chunks^2 / 2 word reads in all - 2 MB from L2 for
+// the headline's 1 024 chunks, nothing beside the 4 MB of bytes; at the 2^29-tile limit (131 072 chunks)
+// it would be 34 GB, not measured, and a shard of that size wants a prefix kernel of its own in between.
+__global__ __launch_bounds__(256) void k_gp_open_scatter(const unsigned* __restrict__ words, long long ntiles,
+                                                         const unsigned* __restrict__ counts,
+                                                         unsigned* __restrict__ list,
+                                                         unsigned long long* __restrict__ head) {
+    __shared__ unsigned part[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned before = 0u;
+    for (unsigned i = threadIdx.x; i < blockIdx.x; i += gp4o::LANES) before += counts[i];
+    unsigned base = gp4o::group_sum(before, part);
+    for (int r = 0; r < gp4o::ROUNDS; ++r) {
+        long long t;
+        uint32_t m = gp4o::lane_mask(words, ntiles, blockIdx.x, r, t);
+        const unsigned n = (unsigned)__popc(m);
+        unsigned incl = n;                                   // inclusive scan over the wavefront
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const unsigned up = __shfl_up(incl, off);
+            if (lane >= off) incl += up;
+        }
+        __syncthreads();
+        if (lane == 63) part[wave] = incl;
+        __syncthreads();
+        unsigned at = base + incl - n;
+        for (int w = 0; w < wave; ++w) at += part[w];
+        while (m) {
+            const int i = __builtin_ctz(m);
+            m &= m - 1u;
+            list[at++] = (unsigned)(4 * t) + (unsigned)i;
+        }
+        base += part[0] + part[1] + part[2] + part[3];
+    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+        head[gp4o::HEAD_LENGTH] = base;
+        head[gp4o::HEAD_NTILES] = (unsigned long long)ntiles;
+        head[gp4o::HEAD_BUILT] = 1ull;
+    }
+}
+#endif
+
 // =============================================================================================
 // host side
 // =============================================================================================
@@ -196,6 +285,43 @@ extern "C" int sl_gp4_predecide_configure(sl_ctx* ctx, int enable, int spacing) 
     if (spacing > 0) ctx->gp4_pre_spacing = spacing;        // (0: keep)
     return SL_OK;
 }
+int sl_gp4_open_build(sl_ctx* ctx, const unsigned char* tiles, long long ntiles) {
+    const Gp4OpenView v = sl_gp4_open_view(tiles, ntiles);
+    const unsigned nchunks = (unsigned)gp4o::chunks(ntiles);
+    const unsigned* words = reinterpret_cast<const unsigned*>(tiles);
+    hipLaunchKernelGGL(k_gp_open_count, dim3(nchunks), dim3(gp4o::LANES), 0, ctx->stream, words, ntiles, v.counts);
+    SL_HIP_CHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_gp_open_scatter, dim3(nchunks), dim3(gp4o::LANES), 0, ctx->stream, words, ntiles, v.counts,
+                       v.list, v.head);
+    SL_HIP_CHECK(ctx, hipGetLastError());
+    return SL_OK;
+}
+
+extern "C" int sl_gp4_open_list(sl_ctx* ctx, uint32_t* out, int64_t cap, unsigned long long* count, int* used) {
+    if (!ctx) return sl_fail(nullptr, SL_ERR_INVALID, "sl_gp4_open_list: NULL context");
+    if (cap < 0 || (cap && !out)) return sl_fail(ctx, SL_ERR_INVALID, "sl_gp4_open_list: bad output (cap %lld)", (long long)cap);
+    if (count) *count = 0ull;
+    if (used) *used = 0;
+    // The last sweep ran the pass and the mean kernel behind it.  gp4_pre_tiles alone does not say so - only
+    // the first segment of a segmented sweep resets it, a later sweep on another path leaves it standing -
+    // so the sweep's note is asked too: sl_sweep_any clears it for every sweep, and only launch4's
+    // segmented path writes "after k_gp_mean_blocks" (those words name the mean pass whichever of its two
+    // kernels ran; the tests hold the note to them).  Whoever rewords that note changes this line with it.
+    // HEAD_BUILT then says whether THIS allocation holds a list (a shard of 2^29 tiles or more has none).
+    if (!ctx->gp4_pre_tiles || !strstr(ctx->last_kernel, "after k_gp_mean_blocks")) return SL_OK;
+    SL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    SL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    unsigned long long head[3] = {0ull, 0ull, 0ull};
+    SL_HIP_CHECK(ctx, hipMemcpy(head, ctx->gp4_pre_tiles - gp4o::HEAD_BYTES, sizeof(head), hipMemcpyDeviceToHost));
+    if (head[gp4o::HEAD_BUILT] != 1ull) return SL_OK;
+    const Gp4OpenView v = sl_gp4_open_view(ctx->gp4_pre_tiles, (long long)head[gp4o::HEAD_NTILES]);
+    const unsigned long long n = head[gp4o::HEAD_LENGTH];
+    if (count) *count = n;
+    if (used) *used = 1;
+    const size_t take = n < (unsigned long long)cap ? (size_t)n : (size_t)cap;
+    if (take) SL_HIP_CHECK(ctx, hipMemcpy(out, v.list, take * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return SL_OK;
+}
 #endif
 
 template <int DT, int MT>
@@ -214,9 +340,12 @@ static int launch_predecide(sl_ctx* ctx, const SlDevModel& model, const SlSweepA
     pc.sdev = sqrt(ctx->h_gp.head[0].variance) * (1.0 + 0x1p-50);
     const int64_t ntiles = (a.hi - a.lo + 63) / 64;
     const size_t table_bytes = ((size_t)npoints * gp4p::row_doubles(DT, DT + MT) * sizeof(double) + 255) & ~(size_t)255;
-    SL_HIP_CHECK(ctx, sl_grow(ctx, &ctx->d_gp4_pre, &ctx->gp4_pre_bytes, table_bytes + (size_t)ntiles + 4));   // (the bytes are read as words)
+    // behind the table: the open-block list's head, the tile bytes (read as words), the list's chunk
+    // counts and the list itself, 16 bytes per tile for every block open (sl_gp4_open_view)
+    SL_HIP_CHECK(ctx, sl_grow(ctx, &ctx->d_gp4_pre, &ctx->gp4_pre_bytes, table_bytes + gp4o::total_bytes(ntiles)));
     double* table = reinterpret_cast<double*>(ctx->d_gp4_pre);
-    unsigned char* tiles = reinterpret_cast<unsigned char*>(ctx->d_gp4_pre) + table_bytes;
+    unsigned char* tiles = reinterpret_cast<unsigned char*>(ctx->d_gp4_pre) + table_bytes + gp4o::HEAD_BYTES;
+    SL_HIP_CHECK(ctx, hipMemsetAsync(tiles - gp4o::HEAD_BYTES, 0, gp4o::HEAD_BYTES, ctx->stream));   // (no list yet)
     SlAux aux{ctx->d_tri, ctx->d_net};
     hipLaunchKernelGGL((k_gp_mean_lattice<DT, MT>), dim3((unsigned)((npoints + 255) / 256)), dim3(256), 0, ctx->stream,
                        model, ctx->h_gp, aux, pc, npoints, table);
@@ -226,6 +355,8 @@ static int launch_predecide(sl_ctx* ctx, const SlDevModel& model, const SlSweepA
                        m.decided);
     SL_HIP_CHECK(ctx, hipGetLastError());
     *tiles_out = tiles;
+    // the blocks left open as a list for k_gp_mean_open (32-bit block numbers: larger shards walk the bytes)
+    if (sl_gp4_open_fits(ntiles)) return sl_gp4_open_build(ctx, tiles, ntiles);
     return SL_OK;
 }
 

@@ -14,7 +14,8 @@ P = os.path.join(ROOT, "profiles")
 
 # kernel -> (source, configuration that measures it, files with the evidence)
 KERNELS = [
-    ("k_gp_predecide + k_gp_mean_blocks + k_gp_sweep4", "csrc/sl_gp4_predecide.hip, csrc/sl_gp4_mean.hip, csrc/sl_gp4.hip", "C4", "predecide.md (blocks decided before the mean from a "
+    ("k_gp_predecide + k_gp_mean_open + k_gp_sweep4", "csrc/sl_gp4_predecide.hip, csrc/sl_gp4_mean.hip, csrc/sl_gp4.hip", "C4", "open_list.md (the mean pass from a compacted list of the open "
+     "blocks: resources, listings, A/B open_list_ab.jsonl, trace open_list_kernel_stats.md); predecide.md (blocks decided before the mean from a "
      "first-order Taylor expansion with an RKHS bound of its remainder: CPU counts, listings, A/B predecide_ab.jsonl); variance_floor.md (the variance floor in the lower bound: listings, CPU prediction floor_cpu_counts.txt, device stage counts, "
      "A/B variance_floor_ab.jsonl, kernel trace, upload cost); shared_block_source.md (one source for both kernels' block arithmetic); meanpass_ab_headline.jsonl (parent / mean kernel, alternating on one box), meanpass_before.md (the source pass of the parent split), "
      "meanpass_kernel_stats.md (both kernels, matrix pipe, stage counts, flush cost), meanpass_other_lines.txt; packed 16-cell blocks before it: blocks_ab_headline.jsonl (parent / 16-cell blocks, alternating on one box), blocks_other_lines.txt, blocks_kernel_stats.md, "
@@ -123,6 +124,8 @@ def main():
              "`k_gp_sweep4`'s early decision against the parent commit, one visit of one box (DESIGN.md 4.1).",
              "* `predecide.md`, `predecide_ab.jsonl`, `predecide_kernel_stats.md`: `k_gp_mean_lattice` / `k_gp_predecide` in front of `k_gp_mean_blocks` against the "
              "parent commit, alternating on one box, `predecide_kernel_stats.md`: the kernel traces of both sides (DESIGN.md 4.1 \"Deciding before the mean\").",
+             "* `open_list.md`, `open_list_ab.jsonl`, `open_list_kernel_stats.md`: the open-block list behind `k_gp_predecide` and `k_gp_mean_open` against the "
+             "parent commit, alternating on one box; the kernel traces of both sides (DESIGN.md 4.1 \"The open-block list\").",
              "* `r06_shard_balance.md`: the N = 2 / 4 / 8 shards of C4 and C5 timed one by one on one GPU (`tools/shard_balance.py`).",
              "* `r06_parity_report.md`: what the parity claims rest on, what is a definition, what is unpinned.",
              "* `r06_box_variance_ab.txt`: the round-5 library and the tree alternating on ONE box (C3, C4-lin, C4-det): boxes of the pool "
