@@ -794,6 +794,46 @@ SL_API int  sl_dense_param_grad(sl_ctx* ctx, int nlayers, const int32_t* h_dims,
                     const int32_t* h_has_bias, double output_scale, const double* d_params, int64_t n, int d,
                     const double* d_points, const double* d_coeff, double* d_out);
 
+/* ---- sample paths of a Gaussian process on a discretization (sample_gp_function, functions.py:1586-1662) and
+ * the dense FP64 linear algebra behind them.  Device buffers belong to the caller unless marked h_; matrices are
+ * row-major with a leading dimension.  Limits: N <= SL_GP_SAMPLE_MAX_N points, k <= SL_GP_SAMPLE_MAX_K columns,
+ * p <= SL_MAX_INPUT_DIM, n <= SL_GP_SAMPLE_MAX_TRAIN observations (SL_ERR_UNSUPPORTED above them); N = 1 and
+ * k = 1 work.  The calls use the context's scratch area and nothing else of it: the model, the GP heads, the
+ * tables and the caches stay as they are.  No atomics: the same input gives the same bits at every call.
+ * sl_gp_posterior_cov: GPRCached.build_predict with full_cov=True (functions.py:438-448) at the N points d_Z
+ *   [N][p], with the explicit inverse factor this engine uses everywhere: a = h_Linv K(h_X, Z) on the matrix
+ *   cores, d_mean [N] = a^T h_alpha + Z h_prior (h_prior [p] or NULL), d_cov [N][ld] = K(Z, Z) - a^T a + jitter I
+ *   (a^T a on the matrix cores; the reference's 1E-8 is the caller's jitter).  The lower triangle is computed and
+ *   mirrored: d_cov equals its transpose bit for bit.  h_X [n][p], h_Linv [n][n], h_alpha [n] and h_kernel as
+ *   sl_gp_set_head_kernel takes them (one output column; a plain RBF is a one-leaf description); n = 0: the prior.
+ * sl_cholesky: in-place lower Cholesky factor of d_A [N][ld] (its lower triangle is read), blocked 64 wide: the
+ *   diagonal block is factored by one workgroup in LDS, the block rows below it are solved against it by
+ *   substitution, the rest loses panel x panel^T on the matrix cores.  The strict upper triangle is zero
+ *   afterwards.  A pivot that is not > 0 (a NaN included) ends the factorization: *h_info (may be NULL) = its
+ *   1-based index (0 on success) and the call returns SL_ERR_INVALID; the matrix is then partly factored.  The
+ *   index travels in a device word that every later kernel of the call reads before it does anything.
+ * sl_tri_solve: d_B [N][k] = L^-1 d_B (transpose = 0) or L^-T d_B, block by block: one right-hand side per lane
+ *   against the diagonal block, the other block rows updated on the matrix cores.
+ * sl_tri_mult: d_out [N][k] = d_mean + L d_Zn (d_mean [N] or NULL; d_out must not be d_Zn), the sum over
+ *   ascending k: the sample values for standard normal d_Zn.
+ * sl_gp_sample_eval: d_out [M][k] = d_points h_prior + K(d_points, d_D) d_Alpha for d_points [M][p], d_D [N][p],
+ *   d_Alpha [N][k]: D and Alpha are streamed through LDS and the sum over j is taken in ascending order, so a
+ *   point's result does not depend on M or on the launch shape. */
+#define SL_GP_SAMPLE_MAX_N 16384
+#define SL_GP_SAMPLE_MAX_K 1024
+#define SL_GP_SAMPLE_MAX_TRAIN 4096
+SL_API int  sl_gp_posterior_cov(sl_ctx* ctx, int n, int p, const double* h_X, const double* h_Linv,
+                    const double* h_alpha, const sl_gp_kernel* h_kernel, const double* h_prior, int64_t N,
+                    const double* d_Z, double jitter, double* d_mean, double* d_cov, int64_t ld);
+SL_API int  sl_cholesky(sl_ctx* ctx, int64_t N, double* d_A, int64_t ld, int32_t* h_info);
+SL_API int  sl_tri_solve(sl_ctx* ctx, int64_t N, int64_t k, const double* d_L, int64_t ld, int transpose,
+                    double* d_B);
+SL_API int  sl_tri_mult(sl_ctx* ctx, int64_t N, int64_t k, const double* d_L, int64_t ld, const double* d_Zn,
+                    const double* d_mean, double* d_out);
+SL_API int  sl_gp_sample_eval(sl_ctx* ctx, const sl_gp_kernel* h_kernel, const double* h_prior, int p, int64_t N,
+                    const double* d_D, int64_t k, const double* d_Alpha, int64_t M, const double* d_points,
+                    double* d_out);
+
 /* ---- multi-GPU collectives directly on RCCL ----------------------------- *
  * For callers without torch.distributed (the Python package issues the same exchanges through
  * torch.distributed, backend "nccl" = RCCL).  One communicator per context, one rank per GPU; every

@@ -228,6 +228,13 @@ SIGNATURES = {
     "sl_critic_batch": (_int, (_vp, _int, _int32_p, _int32_p, _int32_p, _dbl, _vp, _i64, _vp, _vp, _int, _vp, _vp, _vp,
                                _vp, _vp, _vp)),
     "sl_dense_param_grad": (_int, (_vp, _int, _int32_p, _int32_p, _int32_p, _dbl, _vp, _i64, _int, _vp, _vp, _vp)),
+    # GP sample paths: posterior covariance, Cholesky, triangular solves and products, sample functions
+    "sl_gp_posterior_cov": (_int, (_vp, _int, _int, c_double_p, c_double_p, c_double_p, C.POINTER(GpKernel), c_double_p,
+                                   _i64, _vp, _dbl, _vp, _vp, _i64)),
+    "sl_cholesky": (_int, (_vp, _i64, _vp, _i64, _int32_p)),
+    "sl_tri_solve": (_int, (_vp, _i64, _i64, _vp, _i64, _int, _vp)),
+    "sl_tri_mult": (_int, (_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp)),
+    "sl_gp_sample_eval": (_int, (_vp, C.POINTER(GpKernel), c_double_p, _int, _i64, _vp, _i64, _vp, _i64, _vp, _vp)),
     # RCCL collectives
     "sl_comm_unique_id": (_int, (C.c_char_p,)),
     "sl_comm_init": (_int, (_vp, C.c_char_p, _int, _int)),
@@ -760,6 +767,69 @@ class Context(object):
         keep, (pd, pa, pb) = self._dense_description(dims, activations, has_bias)
         self.lib.sl_dense_param_grad(self.handle, len(keep[1]), pd, pa, pb, float(output_scale), _ptr(d_params),
                                      int(n), int(d), _ptr(d_points), _ptr(d_coeff), _ptr(d_out))
+
+    # ---- GP sample paths (sl_gp_sample.hip) ---------------------------------------------------
+    @staticmethod
+    def _kernel_spec(factors, p):
+        """``sl_gp_kernel`` of ``[(kind, product, variance[p], inv_lengthscales[p])]`` (``Kern._factors``)."""
+        if len(factors) > KERNEL_MAX_FACTORS:
+            raise ValueError("kernel with %d leaf factors (engine limit %d)" % (len(factors), KERNEL_MAX_FACTORS))
+        if not 1 <= p <= MAX_INPUT_DIM:
+            raise ValueError("input dimension %d (engine limit %d)" % (p, MAX_INPUT_DIM))
+        spec = GpKernel()
+        spec.nfactors = len(factors)
+        for f, (kind, product, variance, inv_ls) in enumerate(factors):
+            spec.factor[f].kind, spec.factor[f].product = int(kind), int(product)
+            for q in range(p):
+                spec.factor[f].variance[q] = float(variance[q])
+                spec.factor[f].inv_lengthscales[q] = float(inv_ls[q])
+        return spec
+
+    def gp_posterior_cov(self, X, Linv, alpha, factors, prior, d_Z, jitter, d_mean, d_cov):
+        """``sl_gp_posterior_cov``: mean ``[N]`` and covariance ``[N, N]`` (plus ``jitter`` on the diagonal) of a
+        one-output GP with the host factors ``X [n, p]``, ``Linv [n, n]``, ``alpha [n]`` at the device points
+        ``d_Z [N, p]``; ``prior [p]`` (the row of a linear mean function) or ``None``."""
+        N, p = d_Z.shape
+        X, pX = _as_c(np.reshape(X, (-1, p)))
+        Linv, pL = _as_c(Linv)
+        alpha, pA = _as_c(np.reshape(alpha, -1))
+        spec = self._kernel_spec(factors, p)
+        pp = None
+        if prior is not None:
+            prior, pp = _as_c(np.reshape(prior, -1))
+        self.lib.sl_gp_posterior_cov(self.handle, len(X), p, pX, pL, pA, C.byref(spec), pp, N, _ptr(d_Z),
+                                     float(jitter), _ptr(d_mean), _ptr(d_cov), d_cov.stride(0))
+
+    def cholesky(self, d_A):
+        """``sl_cholesky`` in place of the square device matrix ``d_A`` -> 0, or the 1-based index of the first
+        pivot that is not positive (the engine's error for that case is the answer here, not an exception)."""
+        info = C.c_int32(0)
+        try:
+            self.lib.sl_cholesky(self.handle, d_A.shape[0], _ptr(d_A), d_A.stride(0), C.byref(info))
+        except HipEngineError:
+            if info.value == 0:
+                raise
+        return int(info.value)
+
+    def tri_solve(self, d_L, d_B, transpose=False):
+        """``sl_tri_solve``: ``d_B [N, k]`` becomes ``L^-1 d_B`` (``transpose``: ``L^-T d_B``)."""
+        self.lib.sl_tri_solve(self.handle, d_B.shape[0], d_B.shape[1], _ptr(d_L), d_L.stride(0), int(bool(transpose)),
+                              _ptr(d_B))
+
+    def tri_mult(self, d_L, d_Zn, d_mean, d_out):
+        """``sl_tri_mult``: ``d_out [N, k] = d_mean [N] + L d_Zn`` (``d_mean=None``: no mean)."""
+        self.lib.sl_tri_mult(self.handle, d_Zn.shape[0], d_Zn.shape[1], _ptr(d_L), d_L.stride(0), _ptr(d_Zn),
+                             _ptr(d_mean), _ptr(d_out))
+
+    def gp_sample_eval(self, factors, prior, d_D, d_alpha, d_points, d_out):
+        """``sl_gp_sample_eval``: ``d_out [M, k] = d_points prior + K(d_points, d_D) d_alpha``."""
+        N, p = d_D.shape
+        spec = self._kernel_spec(factors, p)
+        pp = None
+        if prior is not None:
+            prior, pp = _as_c(np.reshape(prior, -1))
+        self.lib.sl_gp_sample_eval(self.handle, C.byref(spec), pp, p, N, _ptr(d_D), d_alpha.shape[1], _ptr(d_alpha),
+                                   d_points.shape[0], _ptr(d_points), _ptr(d_out))
 
     def nn_train_scratch(self):
         """``sl_debug_nn_train_scratch`` -> (bytes of the scratch area, its guard zones are intact)."""

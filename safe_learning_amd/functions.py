@@ -49,7 +49,7 @@ __all__ = ['GridWorld', 'DimensionError', 'DeterministicFunction', 'UncertainFun
            'AbsGradient', 'Gradient', 'ConstantFunction', 'RBF', 'Matern32', 'Linear', 'GPRCached', 'GaussianProcess',
            'FunctionStack', 'Triangulation', 'InvertedPendulum', 'CartPole', 'PolynomialSystem', 'VanDerPol',
            'PolynomialFunction', 'monomial_exponents', 'LyapunovNetwork',
-           'NeuralNetwork']
+           'NeuralNetwork', 'sample_gp_function', 'GPSampleFunction']
 
 
 class DimensionError(Exception):
@@ -1423,3 +1423,160 @@ class LyapunovNetwork(DeterministicFunction):
         out = torch.empty(total, dtype=torch.float64, device=ctx.torch_device)
         ctx.nn_param_grad(d_points.shape[0], d_points.shape[1], d_points, d_coeff, out)
         return out.cpu().numpy()
+
+
+# ----------------------------------------------------------------------------------------------
+# sample paths of a Gaussian process
+# ----------------------------------------------------------------------------------------------
+
+SAMPLE_JITTER = 1e-8            # added to the diagonal of the covariance before it is factored (functions.py:1630)
+
+
+def _sample_setup(discretization, gpfun, who):
+    """The checked arguments of the sampling functions -> the ``[N, p]`` discretization and the GP model."""
+    from . import distributed as dist_utils
+    if dist_utils.rank_and_world()[1] > 1:
+        raise NotImplementedError('%s runs on one GPU; under torch.distributed call it on one rank and broadcast '
+                                  'the samples' % who)
+    if isinstance(discretization, GridWorld):
+        discretization = discretization.all_points
+    if not isinstance(gpfun, GaussianProcess):
+        raise TypeError('%s: gpfun must be a GaussianProcess, not %s' % (who, type(gpfun).__name__))
+    if gpfun.output_dim != 1:
+        raise ValueError('%s samples one-output Gaussian processes; gpfun has output_dim %d (sample the members of a '
+                         'FunctionStack one by one)' % (who, gpfun.output_dim))
+    points = np.ascontiguousarray(np.asarray(discretization, dtype=config.np_dtype))
+    if points.ndim != 2 or points.shape[0] < 1 or points.shape[1] != gpfun.input_dim:
+        raise ValueError('%s: the discretization must be [N, %d] with N >= 1, got %s'
+                         % (who, gpfun.input_dim, points.shape))
+    return points, gpfun.gaussian_process
+
+
+def _gp_prior_row(gp):
+    return None if gp.mean_function is None else np.asarray(gp.mean_function.matrix, dtype=config.np_dtype)[0]
+
+
+def _sample_factor(ctx, points, gp, who):
+    """Posterior mean ``[N]`` and the lower Cholesky factor of ``cov + 1e-8 I`` at ``points``, on the device."""
+    import torch
+    n_points, p = points.shape
+    d_points = torch.from_numpy(points).to(ctx.torch_device)
+    d_mean = torch.empty(n_points, dtype=torch.float64, device=ctx.torch_device)
+    d_cov = torch.empty((n_points, n_points), dtype=torch.float64, device=ctx.torch_device)
+    ctx.gp_posterior_cov(gp.X, gp.cholesky_inverse, gp.alpha, gp.kern._factors(p), _gp_prior_row(gp), d_points,
+                         SAMPLE_JITTER, d_mean, d_cov)
+    pivot = ctx.cholesky(d_cov)
+    if pivot:
+        raise np.linalg.LinAlgError('%s: the covariance of the %d points (plus %g on its diagonal) is not positive '
+                                    'definite: pivot %d is not positive' % (who, n_points, SAMPLE_JITTER, pivot))
+    return d_points, d_mean, d_cov
+
+
+class GPSampleFunction(object):
+    """One sample path of a GP as a function: ``f(states, actions, ..., noise=True) -> [M, 1]``.
+
+    As in the reference (``functions.py:1641-1649``) the path is evaluated as ``mean_function(x) +
+    K(x, discretization) . alpha`` with the PRIOR kernel and ``alpha = (cov + 1e-8 I)^-1 . values`` - also when the
+    GP holds observations, whose posterior the values were drawn from (bug-compatible).  The kernel, the mean
+    function and the noise variance are read from the GP at every call.  The inputs are concatenated;
+    NumPy in gives NumPy out, device tensors in give device tensors out.  ``noise=True`` adds
+    ``sqrt(likelihood_variance) * np.random.standard_normal`` (NumPy's global generator).
+
+    Attributes: ``alpha [N]``, ``discretization [N, p]``, ``values [N]`` (the sample at the discretization)."""
+
+    def __init__(self, discretization, gpfun, alpha, values):
+        self.discretization, self.gpfun = discretization, gpfun
+        self.alpha = np.ascontiguousarray(alpha, dtype=config.np_dtype).reshape(-1)
+        self.values = np.ascontiguousarray(values, dtype=config.np_dtype).reshape(-1)
+        if len(self.alpha) != len(discretization) or len(self.values) != len(discretization):
+            raise ValueError('alpha and values need one entry per point of the discretization')
+        self._device = None
+
+    @classmethod
+    def from_values(cls, discretization, gpfun, values):
+        """The sample functions whose values at the discretization are the rows of ``values [number, N]`` (one
+        row: ``[N]``) -> a list, like ``sample_gp_function`` returns."""
+        from . import _evaluate
+        import torch
+        who = 'GPSampleFunction.from_values'
+        points, gp = _sample_setup(discretization, gpfun, who)
+        values = np.atleast_2d(np.asarray(values, dtype=config.np_dtype))
+        if values.shape[1] != len(points):
+            raise ValueError('%s: values must be [number, %d], got %s' % (who, len(points), values.shape))
+        ctx = _evaluate._ctx()
+        _, _, d_chol = _sample_factor(ctx, points, gp, who)
+        d_alpha = torch.from_numpy(np.ascontiguousarray(values.T)).to(ctx.torch_device)
+        ctx.tri_solve(d_chol, d_alpha, False)
+        ctx.tri_solve(d_chol, d_alpha, True)
+        alpha = d_alpha.cpu().numpy()
+        return [cls(points, gpfun, alpha[:, i], values[i]) for i in range(len(values))]
+
+    def __call__(self, *points, **kwargs):
+        from . import _evaluate
+        import torch
+        noise = kwargs.pop('noise', True)
+        if kwargs:
+            raise TypeError('unexpected keyword arguments %s' % sorted(kwargs))
+        if not points:
+            raise TypeError('a sample function needs the points to evaluate')
+        ctx = _evaluate._ctx()
+        on_device = any(isinstance(x, torch.Tensor) for x in points)
+        parts = [_evaluate._to_device(ctx, x) for x in points]
+        d_points = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1).contiguous()
+        p = self.discretization.shape[1]
+        if d_points.shape[1] != p:
+            raise ValueError('the sample function expects %d inputs, the points have %d columns' % (p, d_points.shape[1]))
+        if self._device is None or self._device[0] is not ctx:
+            self._device = (ctx, torch.from_numpy(self.discretization).to(ctx.torch_device),
+                            torch.from_numpy(self.alpha[:, None].copy()).to(ctx.torch_device))
+        gp = self.gpfun.gaussian_process
+        d_out = torch.empty((d_points.shape[0], 1), dtype=torch.float64, device=ctx.torch_device)
+        ctx.gp_sample_eval(gp.kern._factors(p), _gp_prior_row(gp), self._device[1], self._device[2], d_points, d_out)
+        if noise:
+            draws = np.sqrt(gp.likelihood_variance) * np.random.standard_normal(tuple(d_out.shape))
+            d_out += torch.from_numpy(draws).to(ctx.torch_device)
+        return d_out if on_device else d_out.cpu().numpy()
+
+
+def sample_gp_function(discretization, gpfun, number=1, return_function=True, standard_normal=None):
+    """Sample paths of a GP on a discretization (``functions.py:1586-1662``), factored on the GPU.
+
+    ``discretization`` is a ``GridWorld`` (its ``all_points``) or an ``[N, p]`` array, ``gpfun`` a
+    ``GaussianProcess`` with one output.  The samples are ``mean + L z`` with ``mean``, ``cov`` the GP's posterior
+    at the discretization (``build_predict(..., full_cov=True)``), ``L`` the Cholesky factor of ``cov + 1e-8 I`` and
+    ``z = np.random.standard_normal((number, N))`` from NumPy's global generator (``np.random.seed`` makes a run
+    repeatable), or the ``standard_normal [number, N]`` given.  The reference draws the same distribution through
+    ``np.random.multivariate_normal`` (an SVD of ``cov``), so after the same seed its NUMBERS differ from these; only
+    the distribution is the same.
+
+    ``return_function=False`` returns the ``[number, N]`` array of samples; otherwise a list of ``number``
+    :class:`GPSampleFunction` objects, ``f(states, actions, ..., noise=True)``.  A covariance that cannot be factored
+    raises ``np.linalg.LinAlgError`` naming the pivot.  One GPU only: ``NotImplementedError`` under
+    ``torch.distributed`` with more than one rank."""
+    from . import _evaluate
+    import torch
+    who = 'sample_gp_function'
+    points, gp = _sample_setup(discretization, gpfun, who)
+    number = int(number)
+    if number < 1:
+        raise ValueError('%s: number must be at least 1, got %d' % (who, number))
+    n_points = len(points)
+    if standard_normal is None:
+        standard_normal = np.random.standard_normal((number, n_points))
+    else:
+        standard_normal = np.asarray(standard_normal, dtype=config.np_dtype)
+        if standard_normal.shape != (number, n_points):
+            raise ValueError('%s: standard_normal must be [%d, %d], got %s'
+                             % (who, number, n_points, standard_normal.shape))
+    ctx = _evaluate._ctx()
+    _, d_mean, d_chol = _sample_factor(ctx, points, gp, who)
+    d_normal = torch.from_numpy(np.ascontiguousarray(standard_normal.T)).to(ctx.torch_device)
+    d_values = torch.empty_like(d_normal)
+    ctx.tri_mult(d_chol, d_normal, d_mean, d_values)
+    values = np.ascontiguousarray(d_values.cpu().numpy().T)
+    if not return_function:
+        return values
+    ctx.tri_solve(d_chol, d_values, False)
+    ctx.tri_solve(d_chol, d_values, True)
+    alpha = d_values.cpu().numpy()
+    return [GPSampleFunction(points, gpfun, alpha[:, i], values[i]) for i in range(number)]

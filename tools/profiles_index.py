@@ -159,6 +159,11 @@ def main():
              "notebook's SOS candidate beside the LQR quadratic and a 101^2 table on the 2001 x 1501 pendulum grid, a quartic at 64^4 under "
              "the cart-pole, and `bench.py` against the parent's library on one box (`tools/polynomial_value_probe.py`, "
              "`tools/kernel_resources.py`; DESIGN.md 4.2d).",
+             "* `gp_sample.md`: GP sample paths (`sl_gp_posterior_cov`, `sl_cholesky`, `sl_tri_solve`, `sl_tri_mult`, "
+             "`sl_gp_sample_eval`, csrc/sl_gp_sample.hip): a first measurement of the four stages of `sample_gp_function` at "
+             "N = 1 024 / 4 096 / 16 384 and of one sample function on 10^6 points beside `scipy.linalg.cholesky`, registers / LDS / "
+             "scratch of the twelve new kernels, and the figures of the GPU tests against their allowances "
+             "(`tools/gp_sample_probe.py`, `tools/kernel_resources.py`; DESIGN.md 4.2e).",
              "* `gp_posterior_truth.md`: the GP posterior of `k_gp_sweep4`, `k_gp_sweep` and `k_gp_small` against the posterior in "
              "extended precision (`tests/np_gp_truth.py`): per case cond(K), the oracle's own error, a NumPy restatement of the "
              "engine's formula and the engine's measured error (`tests/test_gpu_gp_truth.py`; DESIGN.md 6 (iv)).",
