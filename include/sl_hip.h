@@ -834,6 +834,26 @@ SL_API int  sl_gp_sample_eval(sl_ctx* ctx, const sl_gp_kernel* h_kernel, const d
                     const double* d_D, int64_t k, const double* d_Alpha, int64_t M, const double* d_points,
                     double* d_out);
 
+/* ---- hyper-parameters of GP regression: the log marginal likelihood and its gradient (gpflow 0.4.0
+ * GPR.build_likelihood; GPRCached.compute_log_likelihood / log_likelihood_gradient / optimize).  With the residuals
+ * h_R = Y - m(X) [n][dout] (the columns share the kernel), K = k(h_X, h_X) + noise_variance I = L L^T, B = K^-1 R and
+ * W = B B^T - dout K^-1:
+ *   *h_lml = -1/2 sum(R o B) - dout sum_i log L_ii - n dout / 2 log 2 pi
+ *   h_grad_variance [SL_KERNEL_MAX_FACTORS][SL_MAX_INPUT_DIM], h_grad_inv_ls (the same shape): d lml / d theta =
+ *     1/2 sum_ij W_ij dK_ij / d theta for theta = variance[q] / inv_lengthscales[q] of every factor of the
+ *     description (entries that are zero in the description keep a zero derivative; at most 32 entries may be
+ *     non-zero, SL_ERR_UNSUPPORTED above), *h_grad_noise = 1/2 tr W.  All three may be NULL: then only the value is
+ *     computed, and nothing of order n^3 runs beyond the factorization.
+ * Stateless like the calls above: the context's scratch area, and device buffers the call allocates and frees.
+ * K is formed by sl_gp_posterior_cov without observations, factored by sl_cholesky (a pivot that is not > 0:
+ * *h_info (may be NULL) = its 1-based index, SL_ERR_INVALID), B and L^-1 come from sl_tri_solve, K^-1 = L^-T L^-1
+ * from the matrix cores, and the sum over (i, j) from one workgroup per lower 64 x 64 tile, the tiles added in
+ * ascending order.  No atomics: the same input gives the same bits at every call.  n = 0: 0 and a zero gradient;
+ * n > SL_GP_SAMPLE_MAX_TRAIN: SL_ERR_UNSUPPORTED. */
+SL_API int  sl_gp_likelihood(sl_ctx* ctx, int n, int p, int dout, const double* h_X, const double* h_R,
+                    const sl_gp_kernel* h_kernel, double noise_variance, double* h_lml, double* h_grad_variance,
+                    double* h_grad_inv_ls, double* h_grad_noise, int32_t* h_info);
+
 /* ---- multi-GPU collectives directly on RCCL ----------------------------- *
  * For callers without torch.distributed (the Python package issues the same exchanges through
  * torch.distributed, backend "nccl" = RCCL).  One communicator per context, one rank per GPU; every
@@ -866,6 +886,11 @@ SL_API int  sl_debug_mfma4(sl_ctx* ctx, int nwaves, const double* h_a, const dou
 /* Sustained FP64 rate probes: which = 0 MFMA, 1 VALU FMA, 2 both interleaved.
  * h_out[3] = {TFLOP/s, sustained shader clock in MHz, shader cycles per MFMA slot per SIMD}. */
 SL_API int  sl_debug_fp64_rate(sl_ctx* ctx, int which, int iters, double* h_out);
+/* The last two stages of sl_gp_likelihood alone (the sum over the tiles and its reduction) on a B [n][dout] and a
+ * K^-1 [n][n] from the host (its lower triangle is read): the gradient tables as sl_gp_likelihood fills them. */
+SL_API int  sl_debug_gp_lml_grad(sl_ctx* ctx, int n, int p, int dout, const double* h_X, const double* h_B,
+                    const double* h_Kinv, const sl_gp_kernel* h_kernel, double* h_grad_variance,
+                    double* h_grad_inv_ls, double* h_grad_noise);
 /* The scaled training inputs X / lengthscales of an uploaded GP head as the kernels read them,
  * h_xs [p][n] (row q = input dimension q): lets the tests compare an incrementally extended head
  * (sl_gp_append_point) with a fresh upload bit for bit. */

@@ -235,6 +235,9 @@ SIGNATURES = {
     "sl_tri_solve": (_int, (_vp, _i64, _i64, _vp, _i64, _int, _vp)),
     "sl_tri_mult": (_int, (_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp)),
     "sl_gp_sample_eval": (_int, (_vp, C.POINTER(GpKernel), c_double_p, _int, _i64, _vp, _i64, _vp, _i64, _vp, _vp)),
+    # GP hyper-parameters: log marginal likelihood and gradient
+    "sl_gp_likelihood": (_int, (_vp, _int, _int, _int, c_double_p, c_double_p, C.POINTER(GpKernel), _dbl, c_double_p,
+                                c_double_p, c_double_p, c_double_p, _int32_p)),
     # RCCL collectives
     "sl_comm_unique_id": (_int, (C.c_char_p,)),
     "sl_comm_init": (_int, (_vp, C.c_char_p, _int, _int)),
@@ -247,6 +250,8 @@ SIGNATURES = {
     "sl_debug_mfma": (_int, (_vp, c_double_p, c_double_p, c_double_p)),
     "sl_debug_mfma4": (_int, (_vp, _int, c_double_p, c_double_p, c_double_p, _int, c_double_p)),
     "sl_debug_fp64_rate": (_int, (_vp, _int, _int, c_double_p)),
+    "sl_debug_gp_lml_grad": (_int, (_vp, _int, _int, _int, c_double_p, c_double_p, c_double_p, C.POINTER(GpKernel),
+                                    c_double_p, c_double_p, c_double_p)),
     "sl_debug_gp_inputs": (_int, (_vp, _int, c_double_p)),
     "sl_debug_nn_train_scratch": (_int, (_vp, C.POINTER(_i64), C.POINTER(_int))),
 }
@@ -830,6 +835,54 @@ class Context(object):
             prior, pp = _as_c(np.reshape(prior, -1))
         self.lib.sl_gp_sample_eval(self.handle, C.byref(spec), pp, p, N, _ptr(d_D), d_alpha.shape[1], _ptr(d_alpha),
                                    d_points.shape[0], _ptr(d_points), _ptr(d_out))
+
+    # ---- GP hyper-parameters (sl_gp_likelihood.hip) --------------------------------------------
+    GP_LIKELIHOOD_MAX_TRAIN = 4096          # SL_GP_SAMPLE_MAX_TRAIN
+
+    def gp_likelihood(self, X, R, factors, noise_variance, gradient=True):
+        """``sl_gp_likelihood`` -> ``(lml, grad_variance [nfactors, p], grad_inv_ls [nfactors, p], grad_noise,
+        pivot)``: the log marginal likelihood of the residuals ``R [n, D]`` at the inputs ``X [n, p]`` and its
+        derivatives with respect to ``variance[q]`` / ``inv_lengthscales[q]`` of every factor of ``factors``
+        (``Kern._factors``) and to ``noise_variance`` (``gradient=False``: ``None`` for the three).  ``pivot`` is 0,
+        or the 1-based index of the first pivot of ``K`` that is not positive; ``lml`` is then ``None``."""
+        X = np.asarray(X, dtype=np.float64)
+        n, p = X.shape
+        if n > self.GP_LIKELIHOOD_MAX_TRAIN:
+            raise ValueError("gp_likelihood: %d observations (engine limit %d)" % (n, self.GP_LIKELIHOOD_MAX_TRAIN))
+        X, pX = _as_c(X)
+        R, pR = _as_c(np.reshape(R, (n, 1)) if np.ndim(R) < 2 else R)
+        spec = self._kernel_spec(factors, p)
+        lml, noise, info = _dbl(0.0), _dbl(0.0), C.c_int32(0)
+        gv = np.zeros((KERNEL_MAX_FACTORS, MAX_INPUT_DIM))
+        gl = np.zeros((KERNEL_MAX_FACTORS, MAX_INPUT_DIM))
+        grads = (gv.ctypes.data_as(c_double_p), gl.ctypes.data_as(c_double_p), C.byref(noise)) if gradient \
+            else (None, None, None)
+        try:
+            self.lib.sl_gp_likelihood(self.handle, n, p, R.shape[1], pX, pR, C.byref(spec), float(noise_variance),
+                                      C.byref(lml), grads[0], grads[1], grads[2], C.byref(info))
+        except HipEngineError:
+            if info.value == 0:
+                raise
+            return None, None, None, None, int(info.value)
+        if not gradient:
+            return float(lml.value), None, None, None, 0
+        return float(lml.value), gv[:len(factors), :p].copy(), gl[:len(factors), :p].copy(), float(noise.value), 0
+
+    def gp_lml_grad_stage(self, X, B, Kinv, factors):
+        """``sl_debug_gp_lml_grad``: the tile sum of ``sl_gp_likelihood`` on a given ``B [n, D]`` and ``K^-1 [n, n]``
+        -> ``(grad_variance, grad_inv_ls, grad_noise)``."""
+        X = np.asarray(X, dtype=np.float64)
+        n, p = X.shape
+        X, pX = _as_c(X)
+        B, pB = _as_c(np.reshape(B, (n, 1)) if np.ndim(B) < 2 else B)
+        Kinv, pK = _as_c(np.reshape(Kinv, (n, n)))
+        spec = self._kernel_spec(factors, p)
+        noise = _dbl(0.0)
+        gv = np.zeros((KERNEL_MAX_FACTORS, MAX_INPUT_DIM))
+        gl = np.zeros((KERNEL_MAX_FACTORS, MAX_INPUT_DIM))
+        self.lib.sl_debug_gp_lml_grad(self.handle, n, p, B.shape[1], pX, pB, pK, C.byref(spec),
+                                      gv.ctypes.data_as(c_double_p), gl.ctypes.data_as(c_double_p), C.byref(noise))
+        return gv[:len(factors), :p].copy(), gl[:len(factors), :p].copy(), float(noise.value)
 
     def nn_train_scratch(self):
         """``sl_debug_nn_train_scratch`` -> (bytes of the scratch area, its guard zones are intact)."""

@@ -22,10 +22,8 @@
 // reads first; those return at once, and the host reads the word when the call ends.
 #include "sl_common.h"
 #include "sl_gp_sample.h"
+#include "sl_gp_strip.h"
 
-typedef double sl_gs4 __attribute__((ext_vector_type(4)));
-
-#define SL_GS_THREADS 256
 // head of the context's scratch area: the pivot word, the kernel description, the prior row
 #define SL_GS_INFO_OFF 0
 #define SL_GS_KERNEL_OFF 64
@@ -34,25 +32,6 @@ typedef double sl_gs4 __attribute__((ext_vector_type(4)));
 static_assert(SL_MAX_INPUT_DIM * sizeof(double) <= 64, "the prior row has 64 bytes");
 static_assert(SL_GS_MAX_N == SL_GP_SAMPLE_MAX_N && SL_GS_MAX_K == SL_GP_SAMPLE_MAX_K &&
               SL_GS_MAX_TRAIN == SL_GP_SAMPLE_MAX_TRAIN, "the limits of sl_hip.h are those of sl_gp_sample.h");
-
-// acc[t] += a(rows 0..15, k) b(k, columns 16 t .. 16 t + 15) over k in [0, kend): a(r, k) and b(k, c) return the
-// operand or 0 outside their matrix (kend need not be a multiple of 4)
-template <class FA, class FB>
-__device__ __forceinline__ void gs_strip(int kend, FA a, FB b, sl_gs4 (&acc)[4]) {
-    const int lane = threadIdx.x & 63, l15 = lane & 15, lk = lane >> 4;
-    for (int kk = 0; kk < kend; kk += 4) {
-        const double av = a(l15, kk + lk);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const double bv = b(kk + lk, 16 * t + l15);
-            acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc[t], 0, 0, 0);
-        }
-    }
-}
-
-#define GS_ZERO_ACC(acc)                                                      \
-    sl_gs4 acc[4];                                                            \
-    _Pragma("unroll") for (int t_ = 0; t_ < 4; ++t_) acc[t_] = (sl_gs4){0.0, 0.0, 0.0, 0.0}
 
 // ---- sl_cholesky ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(SL_BLOCK) void k_gs_zero_upper(int64_t N, double* __restrict__ A, int64_t ld) {

@@ -564,6 +564,222 @@ class GPRCached(object):
                                      self.alpha[n].copy()))
 
 
+def _likelihood_engine(X, R, factors, noise_variance, gradient):
+    """One ``sl_gp_likelihood`` call (``Context.gp_likelihood``): the only way the hyper-parameter methods of
+    :class:`GPRCached` reach the engine."""
+    from . import _evaluate
+    return _evaluate._ctx().gp_likelihood(X, R, factors, noise_variance, gradient)
+
+
+class _Hyperparameters(object):
+    """The free numbers of a :class:`GPRCached` by name, and the chain rule from the engine's derivatives (with
+    respect to ``variance[q]`` / ``inv_lengthscales[q]`` of every factor of ``Kern._factors``) to them."""
+
+    def __init__(self, model):
+        self.model = model
+        self.leaves, self.factor_leaf = [], []
+        for product in model.kern._products():
+            for leaf in product:
+                if not any(leaf is known for known in self.leaves):
+                    self.leaves.append(leaf)
+                self.factor_leaf.append([leaf is known for known in self.leaves].index(True))
+        self.entries = []                                  # (name, owner, attribute)
+        for number, leaf in enumerate(self.leaves):
+            self.entries.append(('kern.%d.variance' % number, leaf, 'variance'))
+            if isinstance(leaf, _Stationary):
+                self.entries.append(('kern.%d.lengthscales' % number, leaf, 'lengthscales'))
+        self.entries.append(('likelihood_variance', model, 'likelihood_variance'))
+        self.names = [name for name, _, _ in self.entries]
+
+    @staticmethod
+    def _is_vector(owner, attribute):
+        return isinstance(owner, Kern) and owner.ARD and (attribute == 'lengthscales' or isinstance(owner, Linear))
+
+    def is_vector(self, name):
+        return any(self._is_vector(owner, attribute) for known, owner, attribute in self.entries if known == name)
+
+    def get(self):
+        out = []
+        for name, owner, attribute in self.entries:
+            value = np.asarray(getattr(owner, attribute), dtype=config.np_dtype)
+            out.append((name, value.copy() if self._is_vector(owner, attribute) else value.reshape(-1)[0]))
+        return out
+
+    def set(self, values):
+        """``{name: value}`` into the kernel objects and the model (no ``update_cache``)."""
+        for name, owner, attribute in self.entries:
+            if name not in values:
+                continue
+            value = np.asarray(values[name], dtype=config.np_dtype)
+            current = getattr(owner, attribute)
+            if isinstance(current, np.ndarray):
+                current[:] = value
+            else:
+                setattr(owner, attribute, float(value))
+
+    def natural_gradient(self, grad_variance, grad_inv_ls, grad_noise):
+        """``{name: ndarray}`` from the engine's ``[nfactors, p]`` tables: ``d/dl_q = -a_q^2 d/da_q``, a leaf
+        without ``ARD`` sums over its dimensions, a leaf in several products sums over its factors."""
+        out = {}
+        for number, leaf in enumerate(self.leaves):
+            dims = leaf.active_dims
+            gv = sum(grad_variance[f] for f, owner in enumerate(self.factor_leaf) if owner == number)
+            if isinstance(leaf, Linear):
+                value = gv[dims]
+                out['kern.%d.variance' % number] = value.copy() if leaf.ARD else np.array(value.sum())
+                continue
+            out['kern.%d.variance' % number] = np.array(gv[0])
+            gl = sum(grad_inv_ls[f] for f, owner in enumerate(self.factor_leaf) if owner == number)
+            value = -gl[dims] / np.square(leaf.lengthscales)
+            out['kern.%d.lengthscales' % number] = value if leaf.ARD else np.array(value.sum())
+        out['likelihood_variance'] = np.array(grad_noise)
+        return out
+
+
+def _gpr_hyperparameters(self):
+    """The hyper-parameters in order, ``[(name, value)]``: per leaf kernel object, in the order of its first
+    appearance in ``kern._products()``, ``kern.<i>.variance`` and (RBF, Matern32) ``kern.<i>.lengthscales``, then
+    ``likelihood_variance``.  Lengthscales, and the variance of a ``Linear`` leaf, are a vector for ``ARD=True``
+    and one scalar otherwise."""
+    return _Hyperparameters(self).get()
+
+
+def _gpr_likelihood(self, gradient):
+    from . import distributed as dist_utils
+    if dist_utils.rank_and_world()[1] > 1:
+        raise NotImplementedError('the GP marginal likelihood runs on one GPU; under torch.distributed fit on one '
+                                  'rank and broadcast the hyper-parameters')
+    n, p = self.X.shape
+    if n > _hip.Context.GP_LIKELIHOOD_MAX_TRAIN:
+        raise ValueError('the GP marginal likelihood takes at most %d observations, the model has %d'
+                         % (_hip.Context.GP_LIKELIHOOD_MAX_TRAIN, n))
+    resid = self.Y if self.mean_function is None else self.Y - self.X.dot(self.mean_function.matrix.T)
+    return _likelihood_engine(self.X, resid, self.kern._factors(p), self.likelihood_variance, gradient)
+
+
+def _gpr_not_factored(pivot, n):
+    return np.linalg.LinAlgError('the kernel matrix of the %d observations plus the noise variance is not positive '
+                                 'definite: pivot %d is not positive' % (n, pivot))
+
+
+def _gpr_compute_log_likelihood(self):
+    """Log marginal likelihood of the observations (gpflow 0.4.0 ``GPR.build_likelihood``), on the GPU:
+    ``-1/2 sum_d r_d^T K^-1 r_d - D sum_i log L_ii - n D / 2 log 2 pi`` with ``K = k(X, X) + sigma_n^2 I = L L^T``
+    and ``R = Y - m(X)``.  ``np.linalg.LinAlgError`` (naming the pivot) when ``K`` cannot be factored."""
+    lml, _, _, _, pivot = _gpr_likelihood(self, False)
+    if pivot:
+        raise _gpr_not_factored(pivot, len(self.X))
+    return lml
+
+
+def _gpr_log_likelihood_gradient(self):
+    """``{name: ndarray}``: the derivative of :meth:`compute_log_likelihood` with respect to every entry of
+    :meth:`hyperparameters` (variances, lengthscales, ``likelihood_variance`` - the natural parameters)."""
+    _, gv, gl, gn, pivot = _gpr_likelihood(self, True)
+    if pivot:
+        raise _gpr_not_factored(pivot, len(self.X))
+    return _Hyperparameters(self).natural_gradient(gv, gl, gn)
+
+
+def _gpr_optimize(self, method='L-BFGS-B', maxiter=1000, tol=None, fixed=(), bounds=None, callback=None, **options):
+    """Fit the hyper-parameters: minimise ``-log marginal likelihood`` over the LOGARITHMS of the free parameters
+    with ``scipy.optimize.minimize(jac=True)`` (signature after gpflow 0.4.0's ``Model.optimize``); every
+    evaluation of the objective is one ``sl_gp_likelihood`` call on the GPU.  gpflow searches through a softplus
+    transform instead of the logarithm, so its iterates differ from these; the optimum does not.
+
+    ``fixed``: names (:meth:`hyperparameters`) that keep their value.  ``bounds``: ``{name: (lo, hi)}`` in natural
+    units (``None`` for an open end).  A parameter vector whose kernel matrix cannot be factored is a rejected
+    point (objective ``+inf``, gradient zeros).  A search that met one is not trusted to have converged (``L-BFGS-B``
+    reads the zero gradient as convergence, or stops one evaluation later): it is taken up again from the best
+    point seen, with the iterations that are left, as long as that raises the likelihood, so the search that ends
+    the call met no rejected point.  Otherwise the result has ``success = False`` and says so in ``message``;
+    ``result.rejected`` counts the rejected points.  A model that
+    cannot be factored at the start raises ``np.linalg.LinAlgError`` naming the pivot and is left as it was.
+    Otherwise the best point seen is assigned to the kernel objects and ``likelihood_variance`` at the end and
+    ``update_cache()`` is called once, so every engine follows.  Returns the ``scipy.optimize.OptimizeResult``
+    (``x`` in logarithms, ``fun`` the negative log likelihood; both of the best point)."""
+    import scipy.optimize
+    table = _Hyperparameters(self)
+    unknown = [name for name in list(fixed) + list(bounds or {}) if name not in table.names]
+    if unknown:
+        raise ValueError('optimize: unknown hyper-parameter(s) %s; the model has %s' % (unknown, table.names))
+    free = [(name, np.atleast_1d(value)) for name, value in table.get() if name not in set(fixed)]
+    if not free:
+        raise ValueError('optimize: every hyper-parameter is fixed')
+    for name, value in free:
+        if not np.all(value > 0):
+            raise ValueError('optimize searches over logarithms: %s = %s is not positive' % (name, value))
+    sizes = [len(value) for _, value in free]
+    x0 = np.log(np.concatenate([value for _, value in free]))
+    box = None
+    if bounds:
+        box = []
+        for name, value in free:
+            lo, hi = bounds.get(name, (None, None))
+            box += [(None if lo is None else np.log(lo), None if hi is None else np.log(hi))] * len(value)
+
+    def assign(x):
+        parts = np.split(np.exp(x), np.cumsum(sizes)[:-1])
+        table.set({name: part if table.is_vector(name) else part[0] for (name, _), part in zip(free, parts)})
+
+    best = {'fun': np.inf, 'x': x0.copy()}
+    state = {'accepted': False, 'search_rejected': False, 'rejected': 0}
+
+    def objective(x):
+        assign(x)
+        lml, gv, gl, gn, pivot = _gpr_likelihood(self, True)
+        if pivot or not np.isfinite(lml):
+            if not state['accepted']:
+                assign(x0)
+                raise _gpr_not_factored(pivot, len(self.X))
+            state['search_rejected'] = True
+            state['rejected'] += 1
+            return np.inf, np.zeros_like(x)
+        state['accepted'] = True
+        natural = table.natural_gradient(gv, gl, gn)
+        grad = np.concatenate([np.atleast_1d(natural[name]) for name, _ in free]) * np.exp(x)
+        if -lml < best['fun']:
+            best['fun'], best['x'] = -lml, np.array(x, copy=True)
+        return -lml, -grad
+
+    # A search that met a rejected point cannot be trusted to have converged: L-BFGS-B reads the zero gradient as
+    # convergence, or stops one evaluation later on a small relative reduction.  Such a search is taken up again from
+    # the best point seen, with the iterations that are left, as long as that raises the likelihood; the search that
+    # ends the call met no rejected point, or it is reported as not successful.
+    start, remaining, searches = x0, int(maxiter), 0
+    try:
+        while True:
+            before, state['search_rejected'] = best['fun'], False
+            result = scipy.optimize.minimize(objective, start, jac=True, method=method, tol=tol, bounds=box,
+                                             callback=callback, options=dict(options, maxiter=remaining))
+            searches += 1
+            remaining -= max(int(getattr(result, 'nit', 0)), 1)
+            if (not state['search_rejected'] or not best['fun'] < before or remaining <= 0
+                    or searches >= _OPTIMIZE_SEARCHES):
+                break
+            start = best['x'].copy()
+    finally:
+        if state['accepted']:                      # (a model that was never factored keeps its cache as it was)
+            assign(best['x'])
+            self.update_cache()
+    if state['search_rejected']:
+        result.success = False
+        result.message = ('the last of %d searches met a parameter vector whose kernel matrix cannot be factored (%d '
+                          'rejected in all) and could not be taken up again; the best point seen is kept'
+                          % (searches, state['rejected']))
+    result.x, result.fun, result.rejected = best['x'].copy(), best['fun'], state['rejected']
+    return result
+
+
+_OPTIMIZE_SEARCHES = 20            # searches of one optimize() call: the first and those taken up after a rejected point
+
+
+GPRCached.hyperparameters = _gpr_hyperparameters
+GPRCached.compute_log_likelihood = _gpr_compute_log_likelihood
+GPRCached.log_likelihood_gradient = _gpr_log_likelihood_gradient
+GPRCached.optimize = _gpr_optimize
+
+
 class GaussianProcess(UncertainFunction):
     """``(mean, beta * sqrt(var))`` of a GP model (``functions.py:461-546``)."""
 
@@ -590,6 +806,10 @@ class GaussianProcess(UncertainFunction):
         rank-one update instead of being rebuilt."""
         self.gaussian_process.append_data(x, y)
 
+    def optimize(self, **kw):
+        """Fit the model's hyper-parameters (:meth:`GPRCached.optimize`)."""
+        return self.gaussian_process.optimize(**kw)
+
 
 class FunctionStack(UncertainFunction):
     """One uncertain function per output column (``functions.py:254-307``)."""
@@ -606,6 +826,10 @@ class FunctionStack(UncertainFunction):
     def add_data_point(self, x, y):
         for fun, yi in zip(self.functions, np.asarray(y).squeeze()):
             fun.add_data_point(x, yi)
+
+    def optimize(self, **kw):
+        """``optimize(**kw)`` of every member, one result per head."""
+        return [fun.optimize(**kw) for fun in self.functions]
 
 
 def _gp_heads(dynamics):

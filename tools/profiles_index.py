@@ -164,6 +164,10 @@ def main():
              "N = 1 024 / 4 096 / 16 384 and of one sample function on 10^6 points beside `scipy.linalg.cholesky`, registers / LDS / "
              "scratch of the twelve new kernels, and the figures of the GPU tests against their allowances "
              "(`tools/gp_sample_probe.py`, `tools/kernel_resources.py`; DESIGN.md 4.2e).",
+             "* `gp_likelihood.md`: GP hyper-parameters (`sl_gp_likelihood`, csrc/sl_gp_likelihood.hip): registers, private memory "
+             "and LDS of the four new kernels, first timings of one likelihood call with and without the gradient at n = 130 / 1 024 / "
+             "4 096, the gap between the two restatement searches that sets the allowance of the `optimize()` test, and figures of "
+             "the GPU tests against their allowances (`tools/gp_likelihood_probe.py`, `tools/kernel_resources.py`; DESIGN.md 4.2f).",
              "* `gp_posterior_truth.md`: the GP posterior of `k_gp_sweep4`, `k_gp_sweep` and `k_gp_small` against the posterior in "
              "extended precision (`tests/np_gp_truth.py`): per case cond(K), the oracle's own error, a NumPy restatement of the "
              "engine's formula and the engine's measured error (`tests/test_gpu_gp_truth.py`; DESIGN.md 6 (iv)).",
