@@ -667,6 +667,31 @@ SL_API int  sl_reward_rollout(sl_ctx* ctx, int64_t lo, int64_t hi, const double*
                     const double* d_weights, double tol, int steps_per_launch, double* d_sum,
                     double* d_state, int64_t* h_steps, int* h_converged);
 
+/* ---- the posterior mean of GP dynamics as a deterministic model (functions.py:209-230
+ * UncertainFunction.to_mean_function) --------------------------------------------------------- *
+ * The model's dynamics must be SL_DYN_GP with its heads configured (sl_gp_configure); any other kind:
+ * SL_ERR_UNSUPPORTED (the deterministic kinds belong to sl_rollout / sl_reward_rollout).  The mean is
+ *     prior(z) + sum_heads sum_j k(z, x_j) alpha'_j,  z = [x, u]
+ * one training point at a time in the operations and order of the Bellman sweeps' successor and of
+ * sl_action_gradient's d_next: O(n p) per point, no triangular product, no variance.
+ * sl_gp_mean_points: d_mean [n][d] = the mean at the explicit rows d_inputs [n][d + m] (d, m: the
+ *   model's; the policy is not evaluated).  One thread per row.
+ * sl_rollout_mean: sl_rollout's contract word for word - ranges, grid cells or explicit start
+ *   states, step-major d_traj / d_actions, steps = 0, steps_per_launch (0: chosen from (hi - lo) x
+ *   training points so that a launch stays near a second), the policies (TRI needs slot 1, a per-vertex
+ *   TABLE one step only, NETWORK step by step) - with the GP mean as f.
+ * sl_reward_rollout_mean: sl_reward_rollout's signature and contract (weights table, global stopping
+ *   rule, the launch holding the stopping step run once more cut there, *h_steps, *h_converged) with
+ *   the GP mean as f.
+ * All three are deterministic: the same inputs give the same bits.                                */
+SL_API int  sl_gp_mean_points(sl_ctx* ctx, int64_t n, const double* d_inputs /* [n][d + m] */,
+                    double* d_mean /* [n][d] */);
+SL_API int  sl_rollout_mean(sl_ctx* ctx, int64_t lo, int64_t hi, const double* d_start, int steps,
+                    int steps_per_launch, double* d_state, double* d_traj, double* d_actions);
+SL_API int  sl_reward_rollout_mean(sl_ctx* ctx, int64_t lo, int64_t hi, const double* d_start, int horizon,
+                    const double* d_weights, double tol, int steps_per_launch, double* d_sum,
+                    double* d_state, int64_t* h_steps, int* h_converged);
+
 /* ---- training a LyapunovNetwork (examples/lyapunov_function_learning.ipynb cells 25 and 30: the
  * two optimizer.minimize(..., var_list=lyapunov_function.parameters)) -------------------------- *
  * Both calls work on the network of sl_network_set alone (no sl_model_set needed); d is the width

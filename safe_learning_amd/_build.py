@@ -30,7 +30,8 @@ UNITS = [("sl_kernels", "sl_kernels.hip", []), ("sl_gp", "sl_gp.hip", []),
          ("sl_policy_solve", "sl_policy_solve.hip", []), ("sl_rollout", "sl_rollout.hip", []),
          ("sl_policy_grad", "sl_policy_grad.hip", []), ("sl_safe_grad", "sl_safe_grad.hip", []),
          ("sl_critic", "sl_critic.hip", []), ("sl_poly_value", "sl_poly_value.hip", []),
-         ("sl_gp_sample", "sl_gp_sample.hip", []), ("sl_gp_likelihood", "sl_gp_likelihood.hip", [])]
+         ("sl_gp_sample", "sl_gp_sample.hip", []), ("sl_gp_likelihood", "sl_gp_likelihood.hip", []),
+         ("sl_gp_rollout", "sl_gp_rollout.hip", ["-save-temps=obj"])]
 UNITS += [("sl_gp4_d%d" % dim, "sl_gp4.hip", GP4_FLAGS + ["-DSL_GP4_DIM=%d" % dim]) for dim in (1, 2, 3, 4)]
 # k_gp_mean_blocks (the source pass of k_gp_sweep4's block mode), once per dimension as well
 UNITS += [("sl_gp4_mean_d%d" % dim, "sl_gp4_mean.hip", ["-DSL_GP4_DIM=%d" % dim]) for dim in (1, 2, 3, 4)]

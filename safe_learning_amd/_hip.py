@@ -215,6 +215,11 @@ SIGNATURES = {
     "sl_rollout_mask": (_int, (_vp, _i64, _int, _vp, c_double_p, _dbl, _vp, _vp)),
     "sl_reward_rollout": (_int, (_vp, _i64, _i64, _vp, _int, _vp, _dbl, _int, _vp, _vp, C.POINTER(_i64),
                                  C.POINTER(_int))),
+    # the posterior mean of GP dynamics as a deterministic model
+    "sl_gp_mean_points": (_int, (_vp, _i64, _vp, _vp)),
+    "sl_rollout_mean": (_int, (_vp, _i64, _i64, _vp, _int, _int, _vp, _vp, _vp)),
+    "sl_reward_rollout_mean": (_int, (_vp, _i64, _i64, _vp, _int, _vp, _dbl, _int, _vp, _vp, C.POINTER(_i64),
+                                      C.POINTER(_int))),
     # training a LyapunovNetwork
     "sl_nn_param_grad": (_int, (_vp, _i64, _int, _vp, _vp, _vp)),
     "sl_nn_loss": (_int, (_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _vp, _vp, _vp)),
@@ -710,6 +715,24 @@ class Context(object):
         self.lib.sl_reward_rollout(self.handle, lo, hi, _ptr(d_start), int(horizon), _ptr(d_weights), float(tol),
                                    int(steps_per_launch), _ptr(d_sum), _ptr(d_state), C.byref(steps),
                                    C.byref(converged))
+        return int(steps.value), bool(converged.value)
+
+    def gp_mean_points(self, n, d_inputs, d_mean):
+        """``sl_gp_mean_points``: the mean of the model's GP dynamics at ``n`` explicit ``[x, u]`` rows."""
+        self.lib.sl_gp_mean_points(self.handle, int(n), _ptr(d_inputs), _ptr(d_mean))
+
+    def rollout_mean(self, lo, hi, d_start, steps, d_state, d_traj=None, d_actions=None, steps_per_launch=0):
+        """``sl_rollout_mean``: :meth:`rollout` with the posterior mean of the model's GP dynamics."""
+        self.lib.sl_rollout_mean(self.handle, lo, hi, _ptr(d_start), int(steps), int(steps_per_launch),
+                                 _ptr(d_state), _ptr(d_traj), _ptr(d_actions))
+
+    def reward_rollout_mean(self, lo, hi, d_start, horizon, d_weights, tol, d_sum, d_state, steps_per_launch=0):
+        """``sl_reward_rollout_mean``: :meth:`reward_rollout` with the posterior mean of the model's GP
+        dynamics -> ``(steps, converged)``."""
+        steps, converged = _i64(0), _int(0)
+        self.lib.sl_reward_rollout_mean(self.handle, lo, hi, _ptr(d_start), int(horizon), _ptr(d_weights),
+                                        float(tol), int(steps_per_launch), _ptr(d_sum), _ptr(d_state),
+                                        C.byref(steps), C.byref(converged))
         return int(steps.value), bool(converged.value)
 
     def nn_param_grad(self, m, d, d_points, d_coeff, d_grad_kernels):

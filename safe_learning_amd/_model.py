@@ -9,7 +9,7 @@ table / network payloads are uploaded once (and again only when they change).
 import numpy as np
 
 from . import _hip
-from .functions import (AbsFunction, CartPole, ConstantFunction, FunctionStack,
+from .functions import (AbsFunction, CartPole, ConstantFunction, FunctionStack, GPMeanFunction,
                         GaussianProcess, Gradient, InvertedPendulum, LinearSystem, LyapunovNetwork,
                         NeuralNetwork,
                         Norm1Function, PolynomialFunction, PolynomialSystem, QuadraticFunction, Saturation, Triangulation, _gp_heads,
@@ -131,6 +131,8 @@ class ModelBuilder(object):
     def _write_dynamics(self, desc, dynamics, m):
         d = self.grid.ndim
         dd = desc.dynamics
+        if isinstance(dynamics, GPMeanFunction):
+            dynamics = dynamics.parent                   # the same heads: upload and caching as for the parent
         if isinstance(dynamics, LinearSystem):
             if dynamics.matrix.shape != (d, d + m):
                 raise ValueError('linear dynamics must be %d x %d' % (d, d + m))

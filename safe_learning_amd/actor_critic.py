@@ -20,7 +20,7 @@ import numpy as np
 from . import _hip
 from . import distributed as dist_utils
 from ._model import ModelBuilder
-from .functions import (CartPole, ConstantFunction, InvertedPendulum, LinearSystem, NeuralNetwork,
+from .functions import (CartPole, ConstantFunction, GPMeanFunction, InvertedPendulum, LinearSystem, NeuralNetwork,
                         PolynomialSystem, QuadraticFunction, Triangulation)
 
 __all__ = ['ActorCritic', 'CriticEvaluation']
@@ -65,6 +65,11 @@ class ActorCritic(object):
         elif isinstance(dynamics, PolynomialSystem):
             raise TypeError('dynamics must be InvertedPendulum, CartPole or LinearSystem: a PolynomialSystem (%s) has '
                             'no action tangent in the engine yet' % type(dynamics).__name__)
+        elif isinstance(dynamics, GPMeanFunction):
+            raise TypeError('dynamics must be InvertedPendulum, CartPole or LinearSystem: the TD batches of '
+                            'sl_critic_batch have no GP path, so a GPMeanFunction (%s) cannot be the model of an '
+                            'ActorCritic (GP models: PolicyIteration with a Triangulation value function)'
+                            % dynamics.name)
         else:
             raise TypeError('dynamics must be InvertedPendulum, CartPole or LinearSystem, not %s (GP models: '
                             'PolicyIteration.action_gradient with a Triangulation value function)'

@@ -73,6 +73,14 @@ def make_case(name, num_points=None, n_gp=None, dynamics=None, seed=0, stack=Fal
                     dynamics={'kind': 'linear', 'matrix': np.array([[1., 1.]])},
                     P=np.array([[1.]]), lv=('const', 0.3), lf=0.4, tau=0.5 * tau_scale,
                     initial_set=np.array([n // 2]))
+        if dynamics == 'gp':
+            # one RBF head over [x, u] on noisy samples of x' = x + u around the exact linear prior
+            n_gp = 20 if n_gp is None else n_gp
+            X = np.random.default_rng(seed).uniform(-1, 1, (n_gp, 2))
+            Y = X @ np.array([[1.], [1.]]) + np.random.default_rng(seed + 1).normal(0, noise_std, (n_gp, 1))
+            case['dynamics'] = {'kind': 'gp', 'X': X, 'Y': Y, 'variance': signal_std ** 2,
+                                'lengthscales': np.full(2, lengthscale), 'noise_variance': noise_std ** 2,
+                                'prior': np.array([[1., 1.]]), 'beta': 2.0}
         return case
 
     if name == 'pendulum':

@@ -47,7 +47,7 @@ _TOKENS = itertools.count(1)
 __all__ = ['GridWorld', 'DimensionError', 'DeterministicFunction', 'UncertainFunction',
            'QuadraticFunction', 'LinearSystem', 'Saturation', 'AbsFunction', 'Norm1Function',
            'AbsGradient', 'Gradient', 'ConstantFunction', 'RBF', 'Matern32', 'Linear', 'GPRCached', 'GaussianProcess',
-           'FunctionStack', 'Triangulation', 'InvertedPendulum', 'CartPole', 'PolynomialSystem', 'VanDerPol',
+           'FunctionStack', 'GPMeanFunction', 'Triangulation', 'InvertedPendulum', 'CartPole', 'PolynomialSystem', 'VanDerPol',
            'PolynomialFunction', 'monomial_exponents', 'LyapunovNetwork',
            'NeuralNetwork', 'sample_gp_function', 'GPSampleFunction']
 
@@ -810,6 +810,10 @@ class GaussianProcess(UncertainFunction):
         """Fit the model's hyper-parameters (:meth:`GPRCached.optimize`)."""
         return self.gaussian_process.optimize(**kw)
 
+    def to_mean_function(self):
+        """The model without its error bars (``functions.py:209-230``): a :class:`GPMeanFunction`."""
+        return GPMeanFunction(self)
+
 
 class FunctionStack(UncertainFunction):
     """One uncertain function per output column (``functions.py:254-307``)."""
@@ -831,6 +835,10 @@ class FunctionStack(UncertainFunction):
         """``optimize(**kw)`` of every member, one result per head."""
         return [fun.optimize(**kw) for fun in self.functions]
 
+    def to_mean_function(self):
+        """The stacked means as one deterministic function: a :class:`GPMeanFunction`."""
+        return GPMeanFunction(self)
+
 
 def _gp_heads(dynamics):
     """Flatten a GaussianProcess / FunctionStack into ``[(model, beta, col0)]``."""
@@ -845,6 +853,53 @@ def _gp_heads(dynamics):
     if len(betas) != 1:
         raise ValueError('all GP heads must share the same beta')
     return heads, betas.pop()
+
+
+class GPMeanFunction(DeterministicFunction):
+    """The posterior mean of GP dynamics as a deterministic function: what
+    ``UncertainFunction.to_mean_function()`` returns (``functions.py:209-230``).
+
+    A live view of ``parent`` (a ``GaussianProcess`` or a ``FunctionStack`` of them), not a copy: after
+    ``add_data_point`` or ``optimize()`` on the parent it evaluates the new model.  As the dynamics of a
+    ``(dynamics, policy)`` pair it takes ``compute_trajectory``, ``compute_roa`` and ``reward_rollout`` to
+    the fused kernels of ``csrc/sl_gp_rollout.hip``; ``PolicyIteration`` treats it as its parent (it only
+    ever uses the mean).  ``Lyapunov`` and ``ActorCritic`` refuse it."""
+
+    _role = 'dynamics'
+
+    def __init__(self, parent, name=None):
+        if not isinstance(parent, (GaussianProcess, FunctionStack)):
+            raise TypeError('to_mean_function needs a GaussianProcess or a FunctionStack of them, not %s'
+                            % type(parent).__name__)
+        _gp_heads(parent)                              # (a stack of anything else is refused here)
+        self.parent = parent
+        self.name = name if name is not None else parent.name + '_mean'
+
+    @property
+    def input_dim(self):
+        return self.parent.input_dim
+
+    @property
+    def output_dim(self):
+        return self.parent.output_dim
+
+    def __call__(self, *points):
+        """``f(states, actions)`` (or the concatenated ``[x, u]`` rows) -> the mean ``[n, d]``
+        (``sl_gp_mean_points``: the sum over the training points alone, no variance).  NumPy in gives
+        NumPy out, device tensors in give device tensors out."""
+        import torch
+        from . import _evaluate
+        keep = any(isinstance(p, torch.Tensor) for p in points)
+        d, p = self.output_dim, self.input_dim
+        ctx, builder = _evaluate._builder(d)
+        parts = [_evaluate._to_device(ctx, q) for q in points]
+        inputs = (parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)).contiguous()
+        if inputs.shape[1] != p:
+            raise ValueError('%s expects %d inputs [x, u], got %d columns' % (self.name, p, inputs.shape[1]))
+        builder.upload(ConstantFunction(np.zeros(p - d)), self, QuadraticFunction(np.eye(d)))
+        mean = torch.empty((inputs.shape[0], d), dtype=torch.float64, device=ctx.torch_device)
+        ctx.gp_mean_points(inputs.shape[0], inputs, mean)
+        return mean if keep else mean.cpu().numpy()
 
 
 # ----------------------------------------------------------------------------------------------

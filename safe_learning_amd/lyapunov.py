@@ -85,6 +85,11 @@ class Lyapunov(object):
 
     def __init__(self, discretization, lyapunov_function, dynamics, lipschitz_dynamics,
                  lipschitz_lyapunov, tau, policy, initial_set=None, adaptive=False):
+        from .functions import GPMeanFunction
+        if isinstance(dynamics, GPMeanFunction):
+            raise TypeError('Lyapunov needs the uncertain dynamics themselves, not their mean function (%s): the '
+                            'certificate of the decrease condition is built on the error bound that '
+                            'to_mean_function() drops; pass its parent' % dynamics.name)
         self._setup_engine(discretization)
         self.policy = policy
         self.tau = tau

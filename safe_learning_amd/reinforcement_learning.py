@@ -41,6 +41,9 @@ class PolicyIteration(object):
                                           'QuadraticFunction reward' % (spec.name, role))
         if not isinstance(value_function, Triangulation):
             raise TypeError('value_function must be a Triangulation')
+        from .functions import GPMeanFunction
+        if isinstance(dynamics, GPMeanFunction):
+            dynamics = dynamics.parent                   # only the mean is ever used (:98-99): the same model
         self.policy = policy
         self.dynamics = dynamics
         self.reward_function = reward_function

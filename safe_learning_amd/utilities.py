@@ -46,20 +46,29 @@ def _check_single_process():
 
 def _check_pair(dynamics, policy):
     """The (dynamics, policy) specs the fused kernel takes."""
-    from .functions import (CartPole, ConstantFunction, InvertedPendulum, LinearSystem, NeuralNetwork,
-                            PolynomialSystem, Saturation, Triangulation, UncertainFunction)
+    from .functions import (CartPole, ConstantFunction, GPMeanFunction, InvertedPendulum, LinearSystem,
+                            NeuralNetwork, PolynomialSystem, Saturation, Triangulation, UncertainFunction)
     if isinstance(dynamics, UncertainFunction):
         raise ValueError('the fused rollout needs deterministic dynamics; %s returns (mean, error): pass '
                          'a callable instead of the pair, e.g. `lambda x: dynamics(x, policy(x))[0]`'
                          % type(dynamics).__name__)
-    if not isinstance(dynamics, (LinearSystem, InvertedPendulum, CartPole, PolynomialSystem)):
+    if not isinstance(dynamics, (LinearSystem, InvertedPendulum, CartPole, PolynomialSystem, GPMeanFunction)):
         raise TypeError('unsupported dynamics spec %r: use LinearSystem, InvertedPendulum, CartPole, '
-                        'PolynomialSystem, VanDerPol, or pass a callable on states' % (dynamics,))
+                        'PolynomialSystem, VanDerPol, the to_mean_function() of a GP model, or pass a callable '
+                        'on states' % (dynamics,))
     inner = policy.fun if isinstance(policy, Saturation) else policy
     if not isinstance(inner, (LinearSystem, ConstantFunction, Triangulation, NeuralNetwork)):
         raise TypeError('unsupported policy spec %r: use LinearSystem, ConstantFunction, a Saturation of '
                         'either, a Triangulation or a NeuralNetwork, or pass a callable on states'
                         % (policy,))
+
+
+def _fused(ctx, dynamics, reward=False):
+    """The context's rollout (``reward``: reward rollout) for the dynamics spec: the kernels of
+    ``csrc/sl_gp_rollout.hip`` for a ``GPMeanFunction``, those of ``csrc/sl_rollout.hip`` otherwise."""
+    from .functions import GPMeanFunction
+    name = 'reward_rollout' if reward else 'rollout'
+    return getattr(ctx, name + '_mean' if isinstance(dynamics, GPMeanFunction) else name)
 
 
 def _start_points(ctx, grid):
@@ -101,14 +110,15 @@ def _rollout(dynamics, policy, grid, steps, trajectory=False, actions=False, ste
     dev = ctx.torch_device
     end = torch.empty((n, d), dtype=torch.float64, device=dev)
     states = acts = None
+    rollout = _fused(ctx, dynamics)
     if trajectory:
         states = torch.empty((steps + 1, n, d), dtype=torch.float64, device=dev)
-        ctx.rollout(0, n, start, 0, states[0])                     # row 0: the start states
+        rollout(0, n, start, 0, states[0])                         # row 0: the start states
         start = states[0]
     if actions:
         acts = torch.empty((steps, n, m), dtype=torch.float64, device=dev)
-    ctx.rollout(0, n, start, steps, end, states[1:] if trajectory and steps else None,
-                acts if actions and steps else None, steps_per_launch)
+    rollout(0, n, start, steps, end, states[1:] if trajectory and steps else None,
+            acts if actions and steps else None, steps_per_launch)
     return end, states, acts
 
 
@@ -131,8 +141,8 @@ def compute_trajectory(dynamics, policy, initial_state, num_steps, steps_per_lau
     Returns ``states [num_steps, d]`` (row 0 the initial state) and ``actions [num_steps - 1, m]``;
     for ``[n, d]`` initial states with n > 1 ``[n, num_steps, d]`` and ``[n, num_steps - 1, m]``,
     every row simulated on its own.  ``dynamics`` and ``policy`` are specs (``LinearSystem``,
-    ``InvertedPendulum``, ``CartPole``; ``LinearSystem``, ``ConstantFunction``, ``Saturation``,
-    ``Triangulation``, ``NeuralNetwork``): the whole simulation is one kernel per chunk of steps
+    ``InvertedPendulum``, ``CartPole``, the ``to_mean_function()`` of a GP model; ``LinearSystem``,
+    ``ConstantFunction``, ``Saturation``, ``Triangulation``, ``NeuralNetwork``): the whole simulation is one kernel per chunk of steps
     (``steps_per_launch``, 0 = chosen by the library; the result does not depend on it) with the
     state in registers.  A device tensor as ``initial_state`` keeps the results on the device."""
     import torch
@@ -283,8 +293,8 @@ def reward_rollout(grid, closed_loop_dynamics, reward_function, discount, horizo
         rollout = torch.empty((n,), dtype=torch.float64, device=dev)
         state = torch.empty((n, d), dtype=torch.float64, device=dev)
         d_weights = torch.from_numpy(weights).to(dev)
-        steps, converged = ctx.reward_rollout(0, n, start, horizon, d_weights, tol, rollout, state,
-                                              steps_per_launch)
+        run = _fused(ctx, dynamics, reward=True)
+        steps, converged = run(0, n, start, horizon, d_weights, tol, rollout, state, steps_per_launch)
     else:
         _check_single_process()
         ctx = _evaluate._ctx()

@@ -168,6 +168,10 @@ def main():
              "and LDS of the four new kernels, first timings of one likelihood call with and without the gradient at n = 130 / 1 024 / "
              "4 096, the gap between the two restatement searches that sets the allowance of the `optimize()` test, and figures of "
              "the GPU tests against their allowances (`tools/gp_likelihood_probe.py`, `tools/kernel_resources.py`; DESIGN.md 4.2f).",
+             "* `gp_rollout.md`: closed-loop rollouts of a GP's posterior mean (`k_gp_rollout`, `k_gp_reward_rollout`, `k_gp_mean_points`, "
+             "csrc/sl_gp_rollout.hip): registers, LDS and scratch of the new kernels, the fused `compute_roa` against the callable "
+             "form, the measured (trajectory x step x training point) rate beside the derived one of the chunk rule, and the figures "
+             "of the tests against their bounds (`tools/gp_rollout_probe.py`, `tools/kernel_resources.py`; DESIGN.md 4.2g).",
              "* `gp_posterior_truth.md`: the GP posterior of `k_gp_sweep4`, `k_gp_sweep` and `k_gp_small` against the posterior in "
              "extended precision (`tests/np_gp_truth.py`): per case cond(K), the oracle's own error, a NumPy restatement of the "
              "engine's formula and the engine's measured error (`tests/test_gpu_gp_truth.py`; DESIGN.md 6 (iv)).",
